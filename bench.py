@@ -32,6 +32,10 @@ catalogue-shaped workloads); `neighbours` = the NW and seeded-stutter-path kerne
 a roofline block.  `library.source_id` = hash of the sources + flags libltr_gpu.so is built from, matched against
 profiles/<round>/pmc_traffic*.json before its counters are attached (`roofline.counters_from`).  Other workloads:
 --workload catalogue | config3skew | config5 | config5hifi | config2.
+
+--dump-outputs DIR: rank 0 writes what the timed path computed in its last step, DIR/log_likelihoods.npy (float64, the LL
+vector in locus order; --end-to-end: DIR/log_aln_probs.npy + DIR/seed_positions.npy).  The inputs are a function of the
+arguments alone (fixed seeds), so two builds run with the same arguments are compared output for output.
 """
 import argparse
 import json
@@ -92,7 +96,36 @@ def parse():
     ap.add_argument("--one-gpu", action="store_true",
                     help="N > 1 on a single-GPU box (verification, not a measurement): every rank scores its shard on cuda:0 with the "
                          "real kernels, the exchange runs over gloo with host tensors; the line carries debug_one_gpu = true")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, rank 0 writes what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float64; at most 64 MB in all, a fixed seeded sample of a larger output): two builds compared output for output; "
+                         "bench_outputs/<name> in the tree is ignored by git")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20250225
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array of `arrays` (name -> values) flattened to float64 as DIR/<name>.npy.  An array larger than its
+    share of DUMP_LIMIT_BYTES is cut to a sample whose positions depend on its size and a fixed seed only (sorted, so that the
+    same positions are taken from the same output of two builds).  Returns {name: {"size", "dumped"}}."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(len(arrays), 1)
+    written = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        n = a.size
+        if a.nbytes > share:
+            keep = share // a.itemsize
+            a = a[np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, keep, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        written[name] = {"size": int(n), "dumped": int(a.size)}
+    return written
 
 
 # ------------------------------------------------------------------------------------------------
@@ -544,6 +577,15 @@ def expected_global_offsets(batch, gids, world, xdev, group=None):
     return allp[0][order], off
 
 
+def control_barrier():
+    """Barrier of the default group (gloo, the control plane) as an all-reduce of one host scalar.  torch.distributed.barrier()
+    asks the runtime for an accelerator first, which brings the GPU runtime up in the calling process: a --dry-run rank
+    would hold the GPU open."""
+    import torch
+    import torch.distributed as dist
+    dist.all_reduce(torch.zeros(1))
+
+
 # ------------------------------------------------------------------------------------------------
 def main():
     args = parse()
@@ -666,13 +708,13 @@ def main():
             step(run)
         dev_sync()
         if world > 1:
-            dist.barrier()
+            control_barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
             step(run)
         dev_sync()
         if world > 1:
-            dist.barrier()
+            control_barrier()
         el = time.perf_counter() - t0
         mark_stage("step")
         c = torch.tensor([run["plan"].cells, float(run["batch"].n_loci), float(run["plan"].num_pairs), el], dtype=torch.float64)
@@ -688,6 +730,11 @@ def main():
     run = make_run(full, np.asarray(my_ids, dtype=np.int64) + id_base)
     res = timed(run)
     plan, batch = run["plan"], run["batch"]
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the LL vector of the last timed step, before any later pass writes the buffer again (N > 1: the gathered, locus-ordered one)
+        ll_last = run["glob"] if world > 1 else run["out"][:plan.ll_size]
+        dumped = dump_outputs(args.dump_outputs, {"log_likelihoods": ll_last.cpu().numpy()})
     # the LAST step of the timed region between the plan's own HIP events (first launch .. last launch done, on its launch stream):
     # when the plan is one launch this IS that kernel's duration, taken from the very passes ms_per_step is taken from
     last_ms, last_launches = (None, None) if dry else plan.last_kernel_ms()
@@ -921,6 +968,8 @@ def main():
             detail["weak_scaling" if strong else "strong_scaling"] = other
         if args.one_gpu:
             line["debug_one_gpu"] = True         # every rank on cuda:0, exchange over gloo: a check of the N > 1 code path, not a rate
+        if dumped is not None:
+            detail["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         for k, v in checks.items():
             detail[k] = v
             line[k] = {kk: v[kk] for kk in ("order_ok", "offsets_ok", "loci", "checked_pairs", "pairs", "mismatches", "classes_covered", "ranks_covered") if kk in v}
@@ -962,7 +1011,7 @@ def main():
     if ctx is not None:
         ctx.close()
     if world > 1:
-        dist.barrier()
+        control_barrier()
         dist.destroy_process_group()
     return 0
 
@@ -1002,15 +1051,21 @@ def end_to_end_ranks(args, ctx, dry, rank, world, strong, my_ids, id_base, n_tot
     if ctx is not None:
         ctx.timers(reset=True)
     if world > 1:
-        dist.barrier()
+        control_barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     dev_sync()
     if world > 1:
-        dist.barrier()
+        control_barrier()
     el = time.perf_counter() - t0
     mark_stage("step")
+    if args.dump_outputs and rank == 0:
+        # what the call handed back in the last timed step: the per-read rows (N > 1: gathered, in global locus order) and, N = 1, the seed positions
+        arrays = {"log_aln_probs": state["glob"].cpu().numpy() if og is not None else flat[:int(off[-1])]}
+        if world == 1 and not dry:
+            arrays["seed_positions"] = np.concatenate([s for _, s in packed["outs"]] + [np.zeros(0, dtype=np.int32)])
+        dump_outputs(args.dump_outputs, arrays)
     tm = ctx.timers() if ctx is not None else {"dp_cells": 0.0, "dp_pairs": 0, "dp_kernel_ms": 0.0}
     c = torch.tensor([tm["dp_cells"] / max(args.steps, 1), float(len(items)), float(tm["dp_pairs"]) / max(args.steps, 1), el, float(threads)], dtype=torch.float64)
     per_rank = [torch.zeros_like(c) for _ in range(world)]
@@ -1071,7 +1126,7 @@ def end_to_end_ranks(args, ctx, dry, rank, world, strong, my_ids, id_base, n_tot
     if ctx is not None:
         ctx.close()
     if world > 1:
-        dist.barrier()
+        control_barrier()
         dist.destroy_process_group()
     return 0
 

@@ -300,16 +300,21 @@ def test_bench_parent_retries_with_gloo_when_ranks_die_before_the_first_step():
     assert rc2 == 7 and lines2 == [] and "fresh ranks" not in err2
 
 
+NO_GPU = {"HIP_VISIBLE_DEVICES": "-1"}       # no device visible to the HIP runtime (an invalid index ends the list)
+
+
 def test_bench_rank_falls_back_to_gloo_when_the_rccl_probe_fails():
     """Under the driver's launch line there is no parent of ours: every rank asks a CHILD process whether RCCL comes up between
-    the ranks (here it cannot: no GPU), the ranks agree on the answer over the gloo control group, and the exchange runs on gloo
-    with `backend` saying why.  --exchange nccl makes the same answer an error (exit 5) on every rank."""
+    the ranks (here it cannot: no GPU is visible to the launch line, on a GPU host too), the ranks agree on the answer over the
+    gloo control group, and the exchange runs on gloo with `backend` saying why.  --exchange nccl makes the same answer an error
+    (exit 5) on every rank."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env["LTR_BENCH_TEST_PROBE"] = "run"
+    env["HIP_VISIBLE_DEVICES"] = NO_GPU["HIP_VISIBLE_DEVICES"]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
            "--dry-run", "--loci", "24"]
@@ -323,10 +328,10 @@ def test_bench_rank_falls_back_to_gloo_when_the_rccl_probe_fails():
     assert ln["devices"] == ["", ""] and ln["distinct_devices"] == 0       # (a dry run holds no GPU)
     # a probe that hangs costs its time-out, not the run
     rc, lines, err = _run_bench(["--gpus", "2", "--dry-run", "--loci", "24", "--steps", "1", "--warmup", "0"],
-                                env_extra={"LTR_BENCH_TEST_PROBE": "hang", "LTR_BENCH_PROBE_TIMEOUT_S": "3"}, timeout=600)
+                                env_extra={"LTR_BENCH_TEST_PROBE": "hang", "LTR_BENCH_PROBE_TIMEOUT_S": "3", **NO_GPU}, timeout=600)
     assert rc == 0 and len(lines) == 1, err[-1500:]
     assert "RCCL probe did not finish within 3 s" in lines[0]["backend"]
     # RCCL demanded: every rank leaves with 5 before the first step, and the parent's one retry is the host exchange
-    rc, lines, err = _run_bench(["--gpus", "2", "--dry-run", "--loci", "24", "--steps", "1", "--warmup", "0", "--exchange", "nccl"], timeout=600)
+    rc, lines, err = _run_bench(["--gpus", "2", "--dry-run", "--loci", "24", "--steps", "1", "--warmup", "0", "--exchange", "nccl"], env_extra=NO_GPU, timeout=600)
     assert "--exchange nccl but RCCL probe" in err and "starting fresh ranks with --exchange gloo" in err
     assert rc == 0 and len(lines) == 1 and lines[0]["backend"].startswith("gloo (fallback: launcher retry")

@@ -243,27 +243,38 @@ def test_bench_two_ranks_on_one_gpu():
 
 
 @pytest.mark.gpu
-def test_bench_eight_ranks_on_one_gpu():
-    """The driver's N = 8 shape on the one-GPU box: eight ranks' resident plans side by side on cuda:0 (exchange over
-    gloo), 2000 loci cost-sharded eight ways: shard sizes, the ordered gather, the single-GPU recomputation and the
-    oracle at N = 8."""
-    d = _run_bench(["--gpus", "8", "--one-gpu", "--loci", "2000", "--steps", "1", "--warmup", "1", "--no-weak"], timeout=1500)
-    assert d["n_gpus"] == 8 and d["debug_one_gpu"] is True and d["scaling"] == "strong"
+def test_bench_four_ranks_on_one_gpu():
+    """More than two ranks on the one-GPU box: four ranks' resident plans side by side on cuda:0 (exchange over gloo),
+    2000 loci cost-sharded four ways: shard sizes, the ordered gather, the single-GPU recomputation and the oracle at
+    N = 4.  Four ranks plus this test process keep a shared GPU at no more than six processes holding it at once; the
+    launch line at N = 8 is covered by the dry-run tests (test_distributed_gloo.py)."""
+    d = _run_bench(["--gpus", "4", "--one-gpu", "--loci", "2000", "--steps", "1", "--warmup", "1", "--no-weak"], timeout=1500)
+    assert d["n_gpus"] == 4 and d["debug_one_gpu"] is True and d["scaling"] == "strong"
     assert d["config"]["total_loci"] == 2000
     sizes = d["config"]["shard_loci"]
-    assert len(sizes) == 8 and sum(sizes) == 2000 and min(sizes) >= 150          # cost-balanced: no rank starves
+    assert len(sizes) == 4 and sum(sizes) == 2000 and min(sizes) >= 300          # cost-balanced: no rank starves
     sg = d["single_gpu_check"]
-    assert sg["order_ok"] and sg["mismatches"] == 0 and sg["loci"] == 250 and sg["ranks_covered"] == 8
+    assert sg["order_ok"] and sg["mismatches"] == 0 and sg["loci"] == 250 and sg["ranks_covered"] == 4
     assert d["oracle_check"]["mismatches"] == 0 and d["oracle_check"]["checked_pairs"] > 100
 
 
 @pytest.mark.gpu
 def test_bench_two_gpus_over_rccl():
     """Where the box has two GPUs: the same path on the `nccl` backend (RCCL), one rank per GPU, device tensors in
-    the ordered gather.  Skipped on one-GPU boxes."""
+    the ordered gather.  Where it has one, RCCL cannot put two ranks on it (it refuses a duplicate device): the same
+    launch line with RCCL demanded must then stop before any step with the probe's reason -- no line, no two ranks
+    sharing the device, no hang."""
     import torch
     if torch.cuda.device_count() < 2:
-        pytest.skip("needs two GPUs")
+        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--loci", "600", "--steps", "2", "--warmup", "1",
+                            "--no-weak", "--exchange", "nccl", "--no-cpu-baseline", "--no-end-to-end", "--no-neighbours"],
+                           env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode != 0 and not [l for l in r.stdout.splitlines() if l.startswith("{")], r.stdout[-2000:]
+        assert "--exchange nccl but RCCL probe" in r.stderr and "LOCAL_RANK 1 but 1 visible GPUs" in r.stderr, r.stderr[-3000:]
+        assert "exited" in r.stderr and "before first step" in r.stderr, r.stderr[-3000:]
+        return
     d = _run_bench(["--gpus", "2", "--loci", "600", "--steps", "2", "--warmup", "1", "--no-weak"])
     assert d["n_gpus"] == 2 and "debug_one_gpu" not in d and d["scaling"] == "strong"
     sg = d["single_gpu_check"]

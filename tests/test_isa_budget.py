@@ -19,7 +19,7 @@ import pytest
 
 import isa_util
 
-CACHE = os.path.join("/tmp", "ltr_isa_cache")
+CACHE = os.path.join(isa_util.CSRC, "build", "isa")       # in this tree (ignored with the objects): never shared with another checkout
 TUS = ["ltr_k_one.hip", "ltr_k_pack.hip", "ltr_k_plan.hip", "ltr_k_wg.hip", "ltr_k_wgt.hip", "ltr_k_exact.hip"]
 
 
