@@ -12,11 +12,16 @@ A "step" = one pass of the hot path over the rank's loci (every pooled read x ca
 DP, inputs already resident in HBM) + the one exchange step of the path: the gather of the per-locus
 log-likelihood blocks to rank 0 in GLOBAL locus order (longtr_amd/shard.py::OrderedGather; N > 1
 only).  Loci shard with no data-path collective.  The headline line is strong scaling (total work
-fixed = config 4); the weak-scaling figure (every rank its own 10k loci) is measured in the same run
-and reported under "weak_scaling".
+fixed = config 4); with --full the weak-scaling figure (every rank its own 10k loci) is measured in
+the same run and reported under "weak_scaling".
+
+A plain run does what the headline needs and nothing else: set-up, warm-up, the timed steps, --dump-outputs, the line.  Its
+`roofline` is the timed pass itself (cells of a step x FP64 add/max per cell over ms_per_step, against the peak of the GPUs
+that ran it): no run of its own.  Everything below that takes runs of its own -- per-launch timings, counters, the checks, the
+end-to-end call, the neighbour kernels, the CPU baselines, the other scaling curve -- is measured with --full only.
 
 Rank 0 prints ONE compact JSON line (< 4 KB: fit_line) as the LAST line of stdout and writes everything else to
-bench_detail.json next to this script (path under "detail").  `roofline` prices the dominant DP launch against the FP64
+bench_detail.json next to this script (path under "detail").  With --full, `roofline` prices the dominant DP launch against the FP64
 vector-ALU peak at the FP64 add/max the recurrence needs (11 per cell for a symmetric indel model, 13 otherwise); this path
 is a scalar max-plus recurrence, VALU-bound by ~3 orders of magnitude over its HBM traffic, and the HBM
 figure sits next to it (`roofline.hbm`).  `cpu_baseline` times the reference's own align_seq_to_hap (oracle/_ref, built
@@ -26,7 +31,7 @@ scale-out model, README.md:78-82).  After the timed region the LL buffer of the 
 on a strip-class-stratified sample (`oracle_check`) and, for N > 1, with a single-GPU recomputation on rank 0
 (`single_gpu_check`); for N > 1 the line carries `backend` / `world_size` as torch.distributed reports them.
 
-In the detail file (N == 1): `end_to_end` = ltr_calc_hap_aln_probs on raw alignments, host to host; `kernels` = every launch
+In the detail file (N == 1, --full): `end_to_end` = ltr_calc_hap_aln_probs on raw alignments, host to host; `kernels` = every launch
 class of the pass with its own time; `roofline_most_pairs` = the class that holds most pairs (the packed kernels on
 catalogue-shaped workloads); `neighbours` = the NW and seeded-stutter-path kernels on bounded batches of their own, each with
 a roofline block.  `library.source_id` = hash of the sources + flags libltr_gpu.so is built from, matched against
@@ -63,12 +68,12 @@ def parse():
     ap.add_argument("--workload", default="config3", choices=WORKLOADS)
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
                     help="N > 1: strong = config 4 (the same loci sharded); weak = every rank its own batch")
-    ap.add_argument("--no-weak", action="store_true", help="N > 1: skip the additional weak-scaling measurement")
-    ap.add_argument("--cpu-budget-s", type=float, default=15.0, help="CPU baseline sample budget per core (rank 0, N=1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify", action="store_true", help="skip the post-timing oracle / single-GPU checks")
-    ap.add_argument("--no-neighbours", action="store_true", help="skip the NW / seeded-stutter-path kernel measurements (N = 1 only)")
-    ap.add_argument("--no-end-to-end", action="store_true", help="skip the ltr_calc_hap_aln_probs (raw alignments) measurement")
+    ap.add_argument("--no-weak", action="store_true", help="N > 1, --full: skip the additional weak-scaling measurement")
+    ap.add_argument("--cpu-budget-s", type=float, default=15.0, help="CPU baseline sample budget per core (rank 0, N=1, --full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the post-timing oracle / single-GPU checks")
+    ap.add_argument("--no-neighbours", action="store_true", help="--full: skip the NW / seeded-stutter-path kernel measurements (N = 1 only)")
+    ap.add_argument("--no-end-to-end", action="store_true", help="--full: skip the ltr_calc_hap_aln_probs (raw alignments) measurement")
     ap.add_argument("--end-to-end", action="store_true",
                     help="the timed step is the DROP-IN call itself: every rank runs ltr_calc_hap_aln_probs on the raw alignments of its shard "
                          "(pooling, trimming, planning, upload, DP, download, fan-out: seq_stutter_genotyper.cpp:514-563), then the ordered gather "
@@ -100,6 +105,11 @@ def parse():
                     help="after the timed steps, rank 0 writes what the timed path computed in its last step as DIR/<name>.npy "
                          "(float64; at most 64 MB in all, a fixed seeded sample of a larger output): two builds compared output for output; "
                          "bench_outputs/<name> in the tree is ignored by git")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: per-launch kernel times and the dominant launch's "
+                         "roofline, the other scaling curve (N > 1), the post-timing oracle / single-GPU checks, the end-to-end call, the "
+                         "neighbour kernels and the CPU baselines (each still subject to its --no-* switch).  Without it a run sets up, "
+                         "warms up, times the steps, dumps (--dump-outputs) and prints the line")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -743,7 +753,7 @@ def main():
     # per-launch device times (HIP events on the launch stream): extra, untimed passes so that reading
     # the events never sits inside the timed region
     kms, kms2 = [], []
-    if not dry:
+    if args.full and not dry:
         plan.set_timing(1)                       # every launch as it is launched (one stream)
         for _ in range(min(3, max(1, args.steps))):
             plan.execute(run["out"].data_ptr(), stream)
@@ -756,7 +766,7 @@ def main():
 
     # ---- N > 1: the other scaling curve, same run ----------------------------------------------
     other = None
-    if world > 1 and not args.no_weak:
+    if world > 1 and args.full and not args.no_weak:
         if strong:       # weak: every rank a whole configuration of its own
             wl = synth.config_loci(args.workload, seed=synth.CONFIG_SEED + rank, n_loci=n_total, workers=gen_workers)[0]
             run2 = make_run(synth.pack_loci(wl)[0], np.arange(n_total, dtype=np.int64) + rank * n_total)
@@ -775,7 +785,7 @@ def main():
     # ---- checks, outside the timed region ---------------------------------------------------------
     checks = {}
     exp_ids = exp_off = None
-    if world > 1:
+    if world > 1 and (dry or args.full):           # (a dry run's line is its gather check)
         exp_ids, exp_off = expected_global_offsets(batch, run["ids"], world, xdev, xgroup)
 
     def offsets_ok(og):
@@ -792,10 +802,10 @@ def main():
             checks["dry_run_gather"] = {
                 "total_loci": int(res["loci"]), "gathered_loci": len(off) - 1, "misplaced_loci": bad,
                 "order_ok": bool(len(off) - 1 == (n_total if strong else n_total * world)) and (world == 1 or offsets_ok(run["og"]))}
-        # a stand-in per-launch table of a realistic size (45 classes), so that the line below is assembled exactly as on a GPU
+        # --full: a stand-in per-launch table of a realistic size (45 classes), so that the line below is assembled exactly as on a GPU
         kms = [[{"strip_width": 4 + k % 17, "lanes_per_pair": 2 << (k % 6), "family": ("packed", "one-per-wave", "workgroup", "exact")[k % 4],
-                 "pairs": 1000 + k, "cells": 1.0e9 + k, "ms": 1.0 + 0.01 * k} for k in range(45)]]
-    if not args.no_verify and not dry:
+                 "pairs": 1000 + k, "cells": 1.0e9 + k, "ms": 1.0 + 0.01 * k} for k in range(45)]] if args.full else []
+    if args.full and not args.no_verify and not dry:
         # rank 0 holds the global, locus-ordered LL vector of the last step (N == 1: its own buffer)
         if world > 1:
             step(run)
@@ -835,15 +845,15 @@ def main():
         symtxt = "true" if sym else "false"
         clock_hz = info["clock_mhz"] * 1e6
         peak = (info["n_cu"] * 64 * clock_hz / 1e12) or 1.0       # FP64 add/max lane-ops/s: 4 SIMD x 16 lanes/clk per CU
-        all_ms = float(np.mean([sum(k["ms"] for k in s) for s in kms]))
-        # rocprofv3 --pmc summaries of the latest round (profiles/): HBM traffic per launch, VALU issue share.  They
+        all_ms = float(np.mean([sum(k["ms"] for k in s) for s in kms])) if kms else None
+        # --full: rocprofv3 --pmc summaries of the latest round (profiles/): HBM traffic per launch, VALU issue share.  They
         # are counters of an EARLIER run of profiles/collect.sh: used only when that run loaded this very library.
         import glob as _glob
         import hashlib
         lib_id = {"version": _lib.lib().ltr_version().decode(), "source_id": _lib.source_id(),
                   "so_sha256_16": hashlib.sha256(open(_lib.LIB_PATH, "rb").read()).hexdigest()[:16]}
         tj, tj_path = None, None
-        for cand in sorted(_glob.glob(os.path.join(ROOT, "profiles", "r*", "pmc_traffic*.json")))[::-1]:
+        for cand in sorted(_glob.glob(os.path.join(ROOT, "profiles", "r*", "pmc_traffic*.json")))[::-1] if kms else []:
             try:
                 j = json.load(open(cand))
             except Exception:
@@ -889,21 +899,32 @@ def main():
                     # the committed counter summary these two fields come from (null: none collected with the library that ran here)
                     "counters_from": tj_path}
 
-        dom = max(range(len(kms[0])), key=lambda k: kms[0][k]["cells"])
-        roof = class_roofline(dom)
-        if last_launches == 1 and last_ms:
-            # one launch = the whole plan: its duration from the timed region itself (not from the extra per-launch passes)
-            roof["kernel_ms_extra_passes"] = roof["kernel_ms"]
-            roof["kernel_ms"] = float(last_ms)
-            roof["kernel_ms_from"] = "the timed region's last step (the plan's own HIP events; ms_per_step is the wall-clock mean of all its steps)"
-            roof["achieved"] = roof["kernel_cells"] * roof["ops_per_cell"] / (roof["kernel_ms"] * 1e-3) / 1e12
-            roof["frac"] = roof["achieved"] / peak if peak else None
+        if kms:
+            dom = max(range(len(kms[0])), key=lambda k: kms[0][k]["cells"])
+            roof = class_roofline(dom)
+            if last_launches == 1 and last_ms:
+                # one launch = the whole plan: its duration from the timed region itself (not from the extra per-launch passes)
+                roof["kernel_ms_extra_passes"] = roof["kernel_ms"]
+                roof["kernel_ms"] = float(last_ms)
+                roof["kernel_ms_from"] = "the timed region's last step (the plan's own HIP events; ms_per_step is the wall-clock mean of all its steps)"
+                roof["achieved"] = roof["kernel_cells"] * roof["ops_per_cell"] / (roof["kernel_ms"] * 1e-3) / 1e12
+                roof["frac"] = roof["achieved"] / peak if peak else None
+            fast = [k for k in range(len(kms[0])) if kms[0][k].get("family") != "exact"]
+            most = max(fast, key=lambda k: kms[0][k]["pairs"]) if fast else dom
+            hbm = {"algorithmic_bytes_per_step": plan.input_bytes,
+                   "achieved_GBps": plan.input_bytes / (all_ms * 1e-3) / 1e9 if all_ms > 0 else None, "peak_GBps": 8000.0}
+        else:
+            # a plain run: the timed pass itself (every rank's cells of a step over ms_per_step) against the peak of the GPUs
+            # that ran it -- no run of its own; the dominant launch, its counters and the HBM figure are --full's
+            pass_ms = res["elapsed"] / args.steps * 1e3
+            ops = 11.0 if sym else 13.0
+            ach = res["cells"] * ops / (pass_ms * 1e-3) / 1e12 if pass_ms > 0 else 0.0
+            roof = {"bound": "valu-fp64", "achieved": ach, "peak": peak * world, "unit": "Tlane-op/s (FP64 add/max)", "frac": ach / (peak * world),
+                    "traffic": None, "kernel": "every launch of the timed pass (kernel_ms = ms_per_step; per-launch figures: --full)",
+                    "kernel_ms": pass_ms, "kernel_cells": res["cells"], "ops_per_cell": ops}
+            hbm = None
         dom_ms, dom_cells, fp64_pc = roof["kernel_ms"], roof["kernel_cells"], roof["ops_per_cell"]
-        fast = [k for k in range(len(kms[0])) if kms[0][k].get("family") != "exact"]
-        most = max(fast, key=lambda k: kms[0][k]["pairs"]) if fast else dom
         value = res["cells"] * args.steps / res["elapsed"]
-        hbm = {"algorithmic_bytes_per_step": plan.input_bytes,
-               "achieved_GBps": plan.input_bytes / (all_ms * 1e-3) / 1e9 if all_ms > 0 else None, "peak_GBps": 8000.0}
         # ---- the ONE stdout line (compact: the driver keeps a bounded tail) ----
         line = {
             "metric": "read x haplotype DP cells/s",
@@ -936,28 +957,32 @@ def main():
             line["roofline"]["note"] = "nominal cells: pairs abort early (row-maximum rule), frac is not a roofline fraction; see config5hifi"
         # the whole timed pass against the same peak (its launches overlap on several streams: ms_per_step, not the per-launch sum)
         line["roofline"]["whole_pass_frac"] = plan.cells * fp64_pc / (res["elapsed"] / args.steps) / 1e12 / peak if world == 1 else None
-        line["roofline"]["hbm"] = hbm
+        if hbm is not None:
+            line["roofline"]["hbm"] = hbm
         # ---- everything else: bench_detail.json next to this script ----
         detail = {
             "pairs_per_s": res["pairs"] * args.steps / res["elapsed"],
             "generator": "every locus from its own PCG64 stream keyed by (seed, configuration, locus index); every rank generates its shard only; not std::mt19937",
-            # SURVEY 8d prices the recurrence as the reference writes it (22 lane-ops per cell); the kernel needs 11 (certificate
-            # instead of the per-cell row maximum, LUT emission), so this ratio can exceed 1 -- it is not a roofline fraction
-            "algorithmic_vs_reference_formulation": dom_cells * 22.0 / (dom_ms * 1e-3) / 1e12 / peak if dom_ms > 0 else None,
-            "all_dp_kernels_ms": all_ms,      # sum of the per-launch times of an extra pass with every launch on one stream
-            "roofline_dominant": roof,
-            # the certificate class that holds most PAIRS (catalogue-shaped workloads: short repeats), priced the same way
-            "roofline_most_pairs": class_roofline(most),
-            # per launch as launched; then with the multi-width launch class by class (set_timing level 2)
-            "kernels_by_class": [{"W": k["strip_width"], "lanes_per_pair": k.get("lanes_per_pair", 64), "family": k.get("family"), "pairs": k["pairs"], "cells": k["cells"],
-                                  "ms": float(np.mean([s[i]["ms"] for s in kms2]))} for i, k in enumerate(kms2[0]) if k["pairs"] or k["family"] == "exact"] if kms2 else None,
-            "kernels": [{"W": k["strip_width"], "lanes_per_pair": k.get("lanes_per_pair", 64), "family": k.get("family"), "pairs": k["pairs"], "cells": k["cells"],
-                         "ms": float(np.mean([s[i]["ms"] for s in kms])), **({"ranges": k["ranges"]} if "ranges" in k else {})}
-                        for i, k in enumerate(kms[0]) if k["pairs"] or k["family"] == "exact"],
             "device": info,
             "gen_s": t_gen,
             "plan_create_s": run["t_plan"],      # host packing + binning + H2D upload of rank 0's plan (outside the timed region)
         }
+        if kms:
+            detail.update({
+                # SURVEY 8d prices the recurrence as the reference writes it (22 lane-ops per cell); the kernel needs 11 (certificate
+                # instead of the per-cell row maximum, LUT emission), so this ratio can exceed 1 -- it is not a roofline fraction
+                "algorithmic_vs_reference_formulation": dom_cells * 22.0 / (dom_ms * 1e-3) / 1e12 / peak if dom_ms > 0 else None,
+                "all_dp_kernels_ms": all_ms,      # sum of the per-launch times of an extra pass with every launch on one stream
+                "roofline_dominant": roof,
+                # the certificate class that holds most PAIRS (catalogue-shaped workloads: short repeats), priced the same way
+                "roofline_most_pairs": class_roofline(most),
+                # per launch as launched; then with the multi-width launch class by class (set_timing level 2)
+                "kernels_by_class": [{"W": k["strip_width"], "lanes_per_pair": k.get("lanes_per_pair", 64), "family": k.get("family"), "pairs": k["pairs"], "cells": k["cells"],
+                                      "ms": float(np.mean([s[i]["ms"] for s in kms2]))} for i, k in enumerate(kms2[0]) if k["pairs"] or k["family"] == "exact"] if kms2 else None,
+                "kernels": [{"W": k["strip_width"], "lanes_per_pair": k.get("lanes_per_pair", 64), "family": k.get("family"), "pairs": k["pairs"], "cells": k["cells"],
+                             "ms": float(np.mean([s[i]["ms"] for s in kms])), **({"ranges": k["ranges"]} if "ranges" in k else {})}
+                            for i, k in enumerate(kms[0]) if k["pairs"] or k["family"] == "exact"],
+            })
         if world > 1:
             line["backend"] = backend_txt                 # of the data exchange (the control plane is gloo whatever this says)
             line["world_size"] = dist.get_world_size()
@@ -973,7 +998,7 @@ def main():
         for k, v in checks.items():
             detail[k] = v
             line[k] = {kk: v[kk] for kk in ("order_ok", "offsets_ok", "loci", "checked_pairs", "pairs", "mismatches", "classes_covered", "ranks_covered") if kk in v}
-        if world == 1 and not args.no_end_to_end and not dry:
+        if world == 1 and args.full and not args.no_end_to_end and not dry:
             try:
                 e2e = end_to_end(ctx, args, params)
                 # (the raw loci are their own draw of the generator: compare by the cells the call's plans scored, not by loci)
@@ -983,12 +1008,12 @@ def main():
                 line["end_to_end_frac_of_resident"] = e2e["frac_of_resident_rate"]
             except Exception as e:
                 detail["end_to_end"] = {"error": repr(e)}
-        if world == 1 and not args.no_neighbours and not dry:
+        if world == 1 and args.full and not args.no_neighbours and not dry:
             try:
                 detail["neighbours"] = neighbours(ctx, peak)
             except Exception as e:
                 detail["neighbours"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 one, many = cpu_baselines(batch, params, min(args.cpu_budget_s, 0.3) if dry else args.cpu_budget_s)
                 line["cpu_baseline"] = one
@@ -1000,7 +1025,9 @@ def main():
             except Exception as e:  # the baseline is reporting, never the product path
                 line["cpu_baseline"] = {"error": repr(e)[:200]}
         if dry:
-            line["dry_run"], line["value"], line["roofline"]["kernel"] = True, None, "stand-in table (no GPU)"
+            line["dry_run"], line["value"] = True, None
+            if kms:
+                line["roofline"]["kernel"] = "stand-in table (no GPU)"
             line.update(checks["dry_run_gather"])
             line["shard_sizes"] = line["config"]["shard_loci"]
             if other is not None:
@@ -1075,9 +1102,10 @@ def end_to_end_ranks(args, ctx, dry, rank, world, strong, my_ids, id_base, n_tot
         per_rank = [c]
     el = max(float(x[3]) for x in per_rank)
     cells, nloci, npairs = (sum(float(x[i]) for x in per_rank) for i in (0, 1, 2))
-    # the gathered rows in global locus order: every locus against a one-rank recomputation of a sample on rank 0
+    # the gathered rows in global locus order: every locus against a one-rank recomputation of a sample on rank 0 (--full; a dry
+    # run's line is its gather check)
     check = None
-    if rank == 0 and not args.no_verify:
+    if rank == 0 and not args.no_verify and (dry or args.full):
         glob = state["glob"].cpu().numpy() if og is not None else flat[:int(off[-1])]
         goff = og.global_off if og is not None else off
         n_glob = len(goff) - 1

@@ -27,7 +27,7 @@ def main(out, flt, args):
             for r in rows:
                 k = short(r["Kernel_Name"]); i = pos[k][int(r["Dispatch_Id"])]
                 seq[k][i][r["Counter_Name"]] = seq[k][i].get(r["Counter_Name"], 0.0) + float(r["Counter_Value"])
-    print(f"# rocprofv3 per dispatch: python3 bench.py {args} --no-cpu-baseline --no-end-to-end --no-verify --steps 1 --warmup 0 --debug fan_lanes=1")
+    print(f"# rocprofv3 per dispatch: python3 bench.py {args} --full --no-cpu-baseline --no-end-to-end --no-verify --steps 1 --warmup 0 --debug fan_lanes=1")
     print(f"# library sha256_16 {hashlib.sha256(open(so, 'rb').read()).hexdigest()[:16] if os.path.exists(so) else None}; kernel filter /{flt}/")
     print("# valu_issue = SQ_INSTS_VALU x 4 cycles / (1024 SIMDs x GRBM_GUI_ACTIVE / 8 XCDs); wait = SQ_WAIT_INST_ANY / SQ_WAVE_CYCLES; bytes = FETCH_SIZE / WRITE_SIZE (KiB x 1024, no x2)")
     print("kernel dispatch workgroups us VALU SALU LDS waves valu_issue wait fetch_bytes write_bytes")

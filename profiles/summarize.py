@@ -24,7 +24,7 @@ def lib_id():
 
 
 def main(out, workload="config3"):
-    res = {"source": f"rocprofv3 (profiles/collect.sh): python3 bench.py --workload {workload} --no-cpu-baseline --no-end-to-end --steps 2 --warmup 1 --debug fan_lanes=1 (one stream: every launch of a kernel is the launch bench.py times)",
+    res = {"source": f"rocprofv3 (profiles/collect.sh): python3 bench.py --workload {workload} --full --no-cpu-baseline --no-end-to-end --steps 2 --warmup 1 --debug fan_lanes=1 (one stream: every launch of a kernel is the launch bench.py times)",
            "library": lib_id(), "kernels": {}, "counters": {}}
     for f in glob.glob(os.path.join(out, "trace", "**", "*kernel_stats.csv"), recursive=True):
         for r in csv.DictReader(open(f)):

@@ -138,7 +138,7 @@ def _run_bench(args, env_extra=None, timeout=300):
 def test_bench_launches_its_own_ranks_dry_run():
     """`python bench.py --gpus 2` with no WORLD_SIZE starts two ranks itself; the dry run drives the
     bench's own sharding + ordered-gather code on gloo with a stand-in execute and prints ONE line."""
-    rc, lines, err = _run_bench(["--gpus", "2", "--dry-run", "--loci", "36", "--steps", "2", "--warmup", "1"])
+    rc, lines, err = _run_bench(["--gpus", "2", "--dry-run", "--loci", "36", "--steps", "2", "--warmup", "1", "--full"])
     assert rc == 0, err
     assert len(lines) == 1
     ln = lines[0]
@@ -229,8 +229,8 @@ def test_bench_line_is_one_compact_json_line(n):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--dry-run", "--loci", "40", "--steps", "2", "--warmup", "1"],
-                       env=env, capture_output=True, text=True, timeout=600)
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--dry-run", "--loci", "40", "--steps", "2", "--warmup", "1",
+                        "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     raw = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(raw) == 1 and p.stdout.rstrip().splitlines()[-1] == raw[0]        # and it is the LAST line of stdout
@@ -244,6 +244,32 @@ def test_bench_line_is_one_compact_json_line(n):
         assert ln["backend"] == "gloo" and ln["world_size"] == 2 and "cpu_baseline" not in ln
     detail = json.load(open(os.path.join(root, ln["detail"]) if not os.path.isabs(ln["detail"]) else ln["detail"]))
     assert len(detail["kernels"]) == 45 and detail["value"] == ln["value"]
+
+
+@pytest.mark.parametrize("n", [1, 2])
+def test_plain_bench_run_measures_the_headline_only(n):
+    """Without --full a run sets up, warms up, times the steps and prints the line: no CPU baseline, no per-launch table, no
+    post-timing checks, no other scaling curve.  Its roofline is the timed pass itself against the peak of the GPUs that ran it."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--dry-run", "--loci", "40", "--steps", "2", "--warmup", "1"],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    raw = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(raw) == 1 and p.stdout.rstrip().splitlines()[-1] == raw[0]
+    ln = json.loads(raw[0])
+    assert LINE_KEYS <= set(ln) and ROOFLINE_KEYS <= set(ln["roofline"])
+    assert ln["steps"] == 2 and ln["warmup"] == 1 and ln["n_gpus"] == n and ln["ms_per_step"] > 0
+    assert ln["roofline"]["kernel_ms"] == pytest.approx(ln["ms_per_step"], rel=1e-5)          # (nested floats: 6 digits in the line)
+    assert ln["roofline"]["kernel_cells"] == pytest.approx(ln["config"]["total_cells"], rel=1e-5)
+    for k in ("cpu_baseline", "speedup_vs_cpu_1thread", "oracle_check", "single_gpu_check", "weak_scaling", "other", "loci_per_s_end_to_end"):
+        assert k not in ln, k
+    assert "hbm" not in ln["roofline"] and ln["gathered_loci"] == 40 and ln["misplaced_loci"] == 0 and ln["order_ok"] is True
+    detail = json.load(open(os.path.join(root, ln["detail"]) if not os.path.isabs(ln["detail"]) else ln["detail"]))
+    assert "kernels" not in detail and "cpu_baseline_ncores" not in detail and detail["value"] == ln["value"]
 
 
 def test_fit_line_drops_optional_keys_only():

@@ -217,13 +217,37 @@ def _run_bench(args, timeout=900):
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + args + ["--no-cpu-baseline", "--no-end-to-end", "--no-neighbours"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + args + ["--full", "--no-cpu-baseline", "--no-end-to-end", "--no-neighbours"],
                        env=env, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1                                        # one JSON line, from rank 0
     assert len(lines[0]) < 4096 and r.stdout.rstrip().splitlines()[-1] == lines[0]     # compact, and the last line of stdout
     return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_on_one_gpu(gpu_ctx, tmp_path):
+    """A run without --full: the headline and nothing else (no checks, no CPU baseline, no per-launch passes).  What it dumps
+    is the LL vector of the last timed step, bit for bit what the library computes for the same loci."""
+    import json
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--loci", "300", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1 and r.stdout.rstrip().splitlines()[-1] == lines[0]
+    d = json.loads(lines[0])
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["config"]["total_loci"] == 300
+    assert 0.0 < d["roofline"]["frac"] <= 1.0
+    for k in ("cpu_baseline", "oracle_check", "loci_per_s_end_to_end"):
+        assert k not in d, k
+    loci, _ = synth.config_loci("config3", n_loci=300)
+    batch, _ = synth.pack_loci(loci)
+    ll, _ = gpu_ctx.align_batch(batch)
+    got = np.load(tmp_path / "log_likelihoods.npy")
+    assert np.array_equal(got.view(np.uint64), ll.view(np.uint64))
 
 
 @pytest.mark.gpu
