@@ -7,12 +7,14 @@
                                                      base some read matches ('=') is known; see rebuild_reference)
   left_align_reads   -> ltr_left_align_reads
   candidate alleles  -> ltr_build_haplotype         (exact alleles, no POA)
+                        or, with --ref-vcf, ltr_vcf_read_alleles + ltr_build_vcf_haplotype (a bgzipped, tabix-indexed
+                        panel's alleles in the panel's order; ltr_vcf_index writes the index)
   read x haplotype   -> ltr_calc_hap_aln_probs      (GPU; every locus in one call)
   phasing priors     -> ltr_phasing_priors          (the HP tags, process_phased_reads' rule: --phased-bam)
   posteriors, GT     -> ltr_posteriors
   VCF                -> ltr_vcf_header, ltr_vcf_record, ltr_vcf_writer_*
 
-    python examples/real_reads_trio.py [out.vcf.gz]
+    python examples/real_reads_trio.py [out.vcf.gz] [--ref-vcf panel.vcf.gz]
 
 run(...) returns the per-locus results (used by tests/test_gpu_real_reads.py, which also bit-compares the
 LL matrices with the CPU oracle and checks the trio for Mendelian consistency)."""
@@ -74,7 +76,10 @@ def phasing_priors(sample, hp):
     return p1, p2
 
 
-def run(ctx, vcf_path=None, max_loci=None, tmp_dir="/tmp"):
+def run(ctx, vcf_path=None, max_loci=None, tmp_dir="/tmp", ref_vcf=None):
+    """ref_vcf: a bgzipped, tabix-indexed VCF whose records give the candidate alleles (--ref-vcf: read_vcf_alleles,
+    add_vcf_haplotype_block); a locus without a record gets the status "no panel record".  No allele is pruned in
+    either mode."""
     bed = os.path.join(tmp_dir, f"ltr_regions_{os.getpid()}.bed")
     convert_bed(os.path.join(DATA, "test_regions_hg38.bed"), bed)
     regions, _ = _lib.read_regions(bed, order=True)
@@ -84,6 +89,7 @@ def run(ctx, vcf_path=None, max_loci=None, tmp_dir="/tmp"):
     bam = _lib.Bam([os.path.join(DATA, f"{s}_sample_reads.bam") for s in SAMPLES])
     sample_of_file = {rg["file"]: SAMPLES.index(rg["sample"]) for rg in bam.read_groups()}
     chrom_len = dict(bam.refs())
+    panel = _lib.VcfPanel(ref_vcf) if ref_vcf else None
     loci = []
     for reg in regions:
         if reg["period"] < 1:
@@ -99,7 +105,12 @@ def run(ctx, vcf_path=None, max_loci=None, tmp_dir="/tmp"):
         if b"N" in ref[PAD - 250:len(ref) - PAD + 250]:
             loc["status"] = "reference not covered by matching reads"; continue
         rs = _lib.ReadSet(raw, len(SAMPLES), reg["start"], reg["stop"], ref, lo)
-        hb = rs.build_haplotype(reg["start"], reg["stop"], reg["period"], lo, chrom_len[reg["chrom"]])
+        if panel is None:
+            hb = rs.build_haplotype(reg["start"], reg["stop"], reg["period"], lo, chrom_len[reg["chrom"]])
+        else:
+            rec = panel.alleles(reg["chrom"], reg["start"], reg["stop"])
+            hb = dict(blocks=None, failure="no panel record") if rec is None else \
+                rs.build_vcf_haplotype(rec[0], rec[1], reg["period"], lo, chrom_len[reg["chrom"]])
         reads = [r for r in rs.reads if not r["deleted"]]
         n_p1s, n_p2s = rs.n_p1s, rs.n_p2s
         rs.close()
@@ -108,6 +119,8 @@ def run(ctx, vcf_path=None, max_loci=None, tmp_dir="/tmp"):
         loc.update(blocks=hb["blocks"], alns=[dict(start=r["start"], stop=r["stop"], seq=r["seq"], cigar=r["cigar"]) for r in reads],
                    sample=[r["sample"] for r in reads], hp=[raw[r["source"]]["hp"] for r in reads], ref=ref, ref_start=lo, n_p1s=n_p1s, n_p2s=n_p2s)
     bam.close()
+    if panel is not None:
+        panel.close()
     todo = [l for l in loci if l["status"] == "ok"]
     res = ctx.calc_hap_aln_probs([(l["blocks"], l["alns"], None) for l in todo])              # one GPU pass for every locus
     writer = _lib.VcfWriter(vcf_path) if vcf_path else None
@@ -139,9 +152,13 @@ def run(ctx, vcf_path=None, max_loci=None, tmp_dir="/tmp"):
 
 
 def main():
+    import argparse
+    ap = argparse.ArgumentParser(description="The chain on the bundled trio reads.")
+    ap.add_argument("out", nargs="?", default=None, help="VCF to write (BGZF for *.gz)")
+    ap.add_argument("--ref-vcf", default=None, metavar="PATH", help="bgzipped, tabix-indexed VCF of candidate alleles (LongTR's --ref-vcf)")
+    args = ap.parse_args()
     ctx = _lib.Context(0)
-    out = sys.argv[1] if len(sys.argv) > 1 else None
-    loci = run(ctx, out)
+    loci = run(ctx, args.out, ref_vcf=args.ref_vcf)
     for l in loci:
         if l["status"] != "ok":
             print(f"{l['region']['name']:>16} {l['region']['chrom']}:{l['region']['start']}-{l['region']['stop']}  skipped: {l['status']}")

@@ -501,6 +501,18 @@ typedef struct ltr_hap_result ltr_hap_result;
 int ltr_build_haplotype(ltr_ctx* ctx, const ltr_read_set* rs, int32_t n_samples, int32_t region_start, int32_t region_stop, int32_t period,
                         const uint8_t* chrom_seq, int64_t chrom_seq_start, int64_t chrom_seq_len, int64_t chrom_len,
                         int32_t indel_flank_len, ltr_hap_result** out);
+/*
+ * The same with the alleles of a --ref-vcf panel (ltr_vcf_read_alleles): HaplotypeGenerator::add_vcf_haplotype_block
+ * (HaplotypeGenerator.cpp:497-525) and fuse_haplotype_blocks (:580-607).  The repeat block is [pos, pos+len(REF)) with the
+ * panel's alleles uppercased in panel order (no indel-flank padding, sorting or trimming); the flanks are those of
+ * ltr_build_haplotype, bounded by all reads of rs.  Failures are texts, as there: the reference's "Haplotype blocks are too
+ * near to the chromosome ends", and -- where the reference asserts or would misbehave -- a REF that differs from the
+ * reference bases and a symbolic allele (<...>, '*').  The one exception is an ALT "<DEL>": ltr_vcf_record writes it for a
+ * block allele with no bases, and it is read back as that empty allele.  unplaced_reads / samples_needing_clustering are 0.
+ */
+int ltr_build_vcf_haplotype(ltr_ctx* ctx, const ltr_read_set* rs, int32_t pos, const char* alleles, const int64_t* allele_off,
+                            int32_t n_alleles, int32_t period, const uint8_t* chrom_seq, int64_t chrom_seq_start,
+                            int64_t chrom_seq_len, int64_t chrom_len, ltr_hap_result** out);
 const ltr_haplotype_blocks* ltr_hap_result_blocks(const ltr_hap_result* r);
 const char* ltr_hap_result_failure(const ltr_hap_result* r);
 int32_t     ltr_hap_result_unplaced_reads(const ltr_hap_result* r);
@@ -636,6 +648,31 @@ int ltr_vcf_writer_open(const char* path, ltr_vcf_writer** out);
 int ltr_vcf_writer_header(ltr_vcf_writer* w, const char* text);
 int ltr_vcf_writer_add_record(ltr_vcf_writer* w, const char* chrom, int32_t record_pos, const char* record_text);
 int ltr_vcf_writer_close(ltr_vcf_writer* w);
+
+/* Tabix-indexed VCF input without htslib (ltr_vcf_in.cpp), the --ref-vcf panel of candidate alleles.
+ * ltr_vcf_reader_open = VCFReader::open (src/vcf_reader.cpp:74-105): a BGZF VCF and its <path>.tbi (magic "TBI\1": the BAI
+ * binning and linear index behind format, col_seq / beg / end, meta char, skip and the reference names); an unreadable file,
+ * a missing or damaged index return LTR_ERR_INVALID with the reference's message.  The # header lines are read past, not kept.
+ * ltr_vcf_read_alleles = read_vcf_alleles (src/vcf_input.cpp:21-50): the records overlapping [max(0, start-50), stop+50),
+ * those whose INFO lacks START or END skipped, the first with START == region_start+1 and END == region_stop taken, the scan
+ * ended by a record with POS > region_start+50.  1 = found: *pos = POS-1, the alleles REF first then the ALTs in file order,
+ * laid out like ltr_get_alleles (allele_off has n_alleles + 1 entries, at most cap + 1: no allele is empty); 0 = not found
+ * (an unknown chromosome included), *pos = -1; < 0 = a malformed record or too small a buffer.
+ * ltr_vcf_index = tabix -p vcf: writes <path>.tbi (format 2, columns 1 / 2 / 0, meta '#', skip 0) for a position-sorted
+ * BGZF VCF; a record is binned by [POS-1, max(POS-1+len(REF), INFO END)), the interval a query tests, so that no query
+ * misses it.  The bins need not match htslib's byte for byte.  Not read: .csi indexes, plain-text VCFs. */
+typedef struct ltr_vcf_reader ltr_vcf_reader;
+int  ltr_vcf_reader_open(const char* path, ltr_vcf_reader** out, char* err, int err_cap);
+void ltr_vcf_reader_close(ltr_vcf_reader* r);
+int  ltr_vcf_read_alleles(ltr_vcf_reader* r, const char* chrom, int32_t region_start, int32_t region_stop, int32_t* pos,
+                          char* out, int64_t cap, int64_t* allele_off, int32_t* n_alleles);
+int  ltr_vcf_index(const char* path);
+/* Test hooks.  ltr_debug_vcf_query: the lines (each + '\n') of the records overlapping [start, end); returns their length.
+ * ltr_debug_tbi_parse: a .tbi on its own; header[6] = format, col_seq, col_beg, col_end, meta, skip; counts[2r], counts[2r+1]
+ * = bins and chunks of reference r (the metadata pseudo-bin excluded); names back to back, NUL-terminated; returns the number
+ * of references, LTR_ERR_INVALID for an unreadable index or a chunk whose start lies after its end. */
+int64_t ltr_debug_vcf_query(ltr_vcf_reader* r, const char* chrom, int64_t start, int64_t end, char* out, int64_t cap);
+int32_t ltr_debug_tbi_parse(const char* tbi_path, int32_t* header, int64_t* counts, int32_t cap_refs, char* names, int64_t names_cap);
 
 /* Indexed BAM input without htslib (ltr_bam.cpp): one or more position-sorted *.bam files, each with its *.bam.bai
  * (or *.bai), read as ONE stream like BamCramMultiReader (src/bam_io.h:520-583, src/bam_io.cpp:201-244):

@@ -15,9 +15,9 @@ from . import _abi
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("LTR_GPU_LIB") or os.path.join(CSRC, "libltr_gpu.so")   # override: A/B builds only
-SOURCES = ["ltr_gpu.hip", "ltr_short.hip", "ltr_nw.hip", "ltr_host.cpp", "ltr_genotype.cpp", "ltr_vcf.cpp", "ltr_prep.cpp", "ltr_io.cpp", "ltr_bam.cpp"]
+SOURCES = ["ltr_gpu.hip", "ltr_short.hip", "ltr_nw.hip", "ltr_host.cpp", "ltr_genotype.cpp", "ltr_vcf.cpp", "ltr_prep.cpp", "ltr_io.cpp", "ltr_bam.cpp", "ltr_vcf_in.cpp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-honor-nans", "-std=c++17", "-fPIC", "-shared", "-pthread", "-Wall"]
-LINK_LIBS = ["-lz"]                                         # BGZF blocks of the VCF writer (ltr_io.cpp)
+LINK_LIBS = ["-lz"]                                         # BGZF blocks (ltr_bgzf.h: BAM, VCF writer, tabix-indexed VCF input)
 
 # every symbol include/ltr_gpu.h declares
 EXPORTS = [
@@ -29,7 +29,7 @@ EXPORTS = [
     "ltr_remap_aln_probs", "ltr_default_vcf_options", "ltr_get_alleles", "ltr_vcf_record", "ltr_vcf_header", "ltr_haplotype_aln_info_capacity",
     "ltr_haplotype_align_to_ref", "ltr_left_align_reads", "ltr_phasing_priors", "ltr_read_set_size", "ltr_read_set_alignments",
     "ltr_read_set_alignment_strings", "ltr_read_set_deleted", "ltr_read_set_source", "ltr_read_set_sample", "ltr_read_set_n_p1s",
-    "ltr_read_set_n_p2s", "ltr_read_set_fail_count", "ltr_read_set_free", "ltr_extract_sequence", "ltr_build_haplotype",
+    "ltr_read_set_n_p2s", "ltr_read_set_fail_count", "ltr_read_set_free", "ltr_extract_sequence", "ltr_build_haplotype", "ltr_build_vcf_haplotype",
     "ltr_hap_result_blocks", "ltr_hap_result_failure", "ltr_hap_result_unplaced_reads", "ltr_hap_result_samples_needing_clustering",
     "ltr_hap_result_free", "ltr_version", "ltr_abi_version", "ltr_ctx_timers_n", "ltr_ctx_short_kernel_split", "ltr_ctx_set_host_threads", "ltr_ctx_host_threads", "ltr_host_threads_rule", "ltr_debug_parallel_threads", "ltr_debug_prep_ahead_rule", "ltr_debug_num_classes", "ltr_debug_class_info", "ltr_debug_classify", "ltr_debug_sort_by_class", "ltr_debug_pair_costs", "ltr_debug_threshold_table", "ltr_debug_calc_seed_base",
     "ltr_read_regions", "ltr_region_set_size", "ltr_region_set_lines_read", "ltr_region_set_order", "ltr_region_set_free", "ltr_region_chrom",
@@ -39,6 +39,7 @@ EXPORTS = [
     "ltr_bam_open", "ltr_bam_close", "ltr_bam_num_refs", "ltr_bam_ref_name", "ltr_bam_ref_len", "ltr_bam_num_read_groups", "ltr_bam_read_group_id",
     "ltr_bam_read_group_sample", "ltr_bam_read_group_library", "ltr_bam_read_group_file", "ltr_bam_set_region", "ltr_bam_next",
     "ltr_bam_aux_int", "ltr_bam_aux_float", "ltr_bam_aux_char", "ltr_bam_aux_string",
+    "ltr_vcf_reader_open", "ltr_vcf_reader_close", "ltr_vcf_read_alleles", "ltr_vcf_index", "ltr_debug_vcf_query", "ltr_debug_tbi_parse",
 ]
 
 
@@ -506,6 +507,90 @@ class VcfWriter:
                 raise LtrError(rc, "ltr_vcf_writer_close")
 
 
+class VcfPanel:
+    """ltr_vcf_reader: a bgzipped, tabix-indexed VCF of TR alleles (--ref-vcf).  alleles(chrom, start, stop) = read_vcf_alleles:
+    (pos, [REF, ALT...]) with pos 0-based, or None when the panel has no record of the region."""
+
+    def __init__(self, path):
+        L = lib()
+        L.ltr_vcf_reader_open.argtypes = [C.c_char_p, C.POINTER(C.c_void_p), C.c_char_p, C.c_int]
+        L.ltr_vcf_reader_close.argtypes, L.ltr_vcf_reader_close.restype = [C.c_void_p], None
+        L.ltr_vcf_read_alleles.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_char_p, C.c_int64,
+                                           C.c_void_p, C.POINTER(C.c_int32)]
+        L.ltr_debug_vcf_query.restype = C.c_int64
+        L.ltr_debug_vcf_query.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_int64, C.c_char_p, C.c_int64]
+        self._h = C.c_void_p()
+        err = C.create_string_buffer(2048)
+        rc = L.ltr_vcf_reader_open(os.fsencode(path), C.byref(self._h), err, len(err))
+        if rc != 0:
+            self._h = None
+            raise LtrError(rc, err.value.decode(errors="replace"))
+        self._cap = 1 << 16
+
+    def alleles(self, chrom, start, stop):
+        L = lib()
+        while True:
+            buf = C.create_string_buffer(self._cap)
+            off = np.zeros(self._cap + 1, dtype=np.int64)
+            pos, n = C.c_int32(-1), C.c_int32(0)
+            rc = L.ltr_vcf_read_alleles(self._h, chrom.encode(), int(start), int(stop), C.byref(pos), buf, self._cap, _p(off), C.byref(n))
+            if rc == 1:
+                raw = buf.raw
+                return pos.value, [raw[off[i]:off[i + 1]].decode() for i in range(n.value)]
+            if rc == 0:
+                return None
+            if self._cap >= 1 << 22:
+                raise LtrError(rc, f"ltr_vcf_read_alleles {chrom}:{start}-{stop}")
+            self._cap <<= 2                                      # (a too small buffer is the same status as a malformed record)
+
+    def query_lines(self, chrom, start, end):
+        """Test hook: the text lines of the records whose interval overlaps [start, end)."""
+        cap = 1 << 20
+        while True:
+            buf = C.create_string_buffer(cap)
+            n = lib().ltr_debug_vcf_query(self._h, chrom.encode(), int(start), int(end), buf, cap)
+            if n >= 0:
+                return buf.raw[:n].decode().splitlines()
+            if cap >= 1 << 28:
+                raise LtrError(int(n), "ltr_debug_vcf_query")
+            cap <<= 2
+
+    def close(self):
+        if self._h:
+            lib().ltr_vcf_reader_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def vcf_index(path):
+    """ltr_vcf_index (tabix -p vcf): writes path + ".tbi" for a position-sorted BGZF VCF."""
+    L = lib()
+    L.ltr_vcf_index.argtypes = [C.c_char_p]
+    rc = L.ltr_vcf_index(os.fsencode(path))
+    if rc != 0:
+        raise LtrError(rc, f"ltr_vcf_index {path}")
+
+
+def tbi_parse(tbi_path, max_refs=4096):
+    """Test hook ltr_debug_tbi_parse: dict(format, col_seq, col_beg, col_end, meta, skip, names, bins, chunks) or LtrError."""
+    L = lib()
+    L.ltr_debug_tbi_parse.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_char_p, C.c_int64]
+    header, counts = np.zeros(6, dtype=np.int32), np.zeros(2 * max_refs, dtype=np.int64)
+    names = C.create_string_buffer(1 << 20)
+    n = L.ltr_debug_tbi_parse(os.fsencode(tbi_path), _p(header), _p(counts), max_refs, names, len(names))
+    if n < 0:
+        raise LtrError(n, f"ltr_debug_tbi_parse {tbi_path}")
+    d = dict(zip(("format", "col_seq", "col_beg", "col_end", "meta", "skip"), (int(x) for x in header)))
+    d["names"] = [x.decode() for x in names.raw.split(b"\0")[:n]]
+    d["bins"], d["chunks"] = [int(x) for x in counts[0:2 * min(n, max_refs):2]], [int(x) for x in counts[1:2 * min(n, max_refs):2]]
+    return d
+
+
 class BamRecord(C.Structure):
     _fields_ = [("name", C.c_char_p), ("file_index", C.c_int32), ("ref_id", C.c_int32), ("pos", C.c_int32), ("end_pos", C.c_int32),
                 ("mapq", C.c_int32), ("flag", C.c_int32), ("mate_ref_id", C.c_int32), ("mate_pos", C.c_int32), ("tlen", C.c_int32),
@@ -862,6 +947,31 @@ def vcf_record(packed_vcf_locus, options=None):
     return buf.raw[:n].decode(), pos.value
 
 
+def _hap_result(h):
+    """An ltr_hap_result as dict(blocks=[...] or None, failure, unplaced_reads, samples_needing_clustering); frees it."""
+    L = lib()
+    L.ltr_hap_result_blocks.argtypes, L.ltr_hap_result_blocks.restype = [C.c_void_p], C.POINTER(_abi.HaplotypeBlocks)
+    L.ltr_hap_result_failure.argtypes, L.ltr_hap_result_failure.restype = [C.c_void_p], C.c_char_p
+    L.ltr_hap_result_unplaced_reads.argtypes = [C.c_void_p]
+    L.ltr_hap_result_samples_needing_clustering.argtypes = [C.c_void_p]
+    L.ltr_hap_result_free.argtypes, L.ltr_hap_result_free.restype = [C.c_void_p], None
+    out = dict(failure=L.ltr_hap_result_failure(h).decode(), unplaced_reads=L.ltr_hap_result_unplaced_reads(h),
+               samples_needing_clustering=L.ltr_hap_result_samples_needing_clustering(h), blocks=None)
+    bp = L.ltr_hap_result_blocks(h)
+    if bp:
+        b = bp.contents
+        blocks, k = [], 0
+        for i in range(b.n_blocks):
+            al = []
+            for _ in range(b.n_alleles[i]):
+                al.append(bytes(b.allele_bytes[b.allele_off[k]:b.allele_off[k + 1]]))
+                k += 1
+            blocks.append(dict(start=b.block_start[i], end=b.block_end[i], is_repeat=bool(b.is_repeat[i]), period=b.period[i], alleles=al))
+        out["blocks"] = blocks
+    L.ltr_hap_result_free(h)
+    return out
+
+
 # ---- raw reads -> prepared reads -> candidate haplotypes (host) -----------------------------------
 class ReadSet:
     """ltr_read_set: GenotyperBamProcessor::left_align_reads for one locus.  raw: list of dict(pos, end_pos, bases,
@@ -935,26 +1045,23 @@ class ReadSet:
                                    chrom_seq_start, len(self.chrom), chrom_len, indel_flank_len, C.byref(h))
         if rc != 0:
             raise LtrError(rc, "ltr_build_haplotype")
-        L.ltr_hap_result_blocks.argtypes, L.ltr_hap_result_blocks.restype = [C.c_void_p], C.POINTER(_abi.HaplotypeBlocks)
-        L.ltr_hap_result_failure.argtypes, L.ltr_hap_result_failure.restype = [C.c_void_p], C.c_char_p
-        L.ltr_hap_result_unplaced_reads.argtypes = [C.c_void_p]
-        L.ltr_hap_result_samples_needing_clustering.argtypes = [C.c_void_p]
-        L.ltr_hap_result_free.argtypes, L.ltr_hap_result_free.restype = [C.c_void_p], None
-        out = dict(failure=L.ltr_hap_result_failure(h).decode(), unplaced_reads=L.ltr_hap_result_unplaced_reads(h),
-                   samples_needing_clustering=L.ltr_hap_result_samples_needing_clustering(h), blocks=None)
-        bp = L.ltr_hap_result_blocks(h)
-        if bp:
-            b = bp.contents
-            blocks, k = [], 0
-            for i in range(b.n_blocks):
-                al = []
-                for _ in range(b.n_alleles[i]):
-                    al.append(bytes(b.allele_bytes[b.allele_off[k]:b.allele_off[k + 1]]))
-                    k += 1
-                blocks.append(dict(start=b.block_start[i], end=b.block_end[i], is_repeat=bool(b.is_repeat[i]), period=b.period[i], alleles=al))
-            out["blocks"] = blocks
-        L.ltr_hap_result_free(h)
-        return out
+        return _hap_result(h)
+
+    def build_vcf_haplotype(self, pos, alleles, period, chrom_seq_start, chrom_len, ctx=None):
+        """ltr_build_vcf_haplotype (add_vcf_haplotype_block + fuse_haplotype_blocks) for panel alleles (REF first, as
+        VcfPanel.alleles gives them) at 0-based pos -> the dict of build_haplotype."""
+        L = lib()
+        L.ltr_build_vcf_haplotype.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                              C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]
+        raw = [a.encode() if isinstance(a, str) else bytes(a) for a in alleles]
+        off = np.zeros(len(raw) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(a) for a in raw]) if raw else []
+        h = C.c_void_p()
+        rc = L.ltr_build_vcf_haplotype(None if ctx is None else ctx._h, self._h, int(pos), b"".join(raw), _p(off), len(raw), int(period),
+                                       _p(self.chrom), chrom_seq_start, len(self.chrom), chrom_len, C.byref(h))
+        if rc != 0:
+            raise LtrError(rc, "ltr_build_vcf_haplotype")
+        return _hap_result(h)
 
     def close(self):
         if self._h:

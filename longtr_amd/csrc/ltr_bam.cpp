@@ -1,5 +1,6 @@
 // ltr_bam.cpp -- indexed BAM input without htslib: BGZF blocks through zlib, the BAM
-// record layout and the BAI binning index as the SAM specification publishes them (sections 4.1, 4.2, 5.1.1-5.2).
+// record layout and the BAI binning index as the SAM specification publishes them (sections 4.1, 4.2, 5.1.1-5.2);
+// the BGZF reader and the binning scheme are shared with the tabix-indexed VCF reader (ltr_bgzf.h).
 //
 // Replaces, for position-sorted *.bam files with a *.bam.bai (or *.bai) next to them:
 //   BamHeader (reference names / lengths, @RG ID / SM / LB)            reference src/bam_io.h:360-420, src/bam_io.cpp:43-70
@@ -29,9 +30,12 @@
 #include <sys/stat.h>
 #include <zlib.h>
 
+#include "ltr_bgzf.h"
 #include "ltr_internal.h"
 
 namespace {
+
+namespace bgzf = ltr::bgzf;
 
 void put_error(char* err, int cap, const std::string& msg) {
   if (!err || cap <= 0) return;
@@ -40,78 +44,12 @@ void put_error(char* err, int cap, const std::string& msg) {
   err[n] = 0;
 }
 
-uint32_t le32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
-uint64_t le64(const uint8_t* p) { return (uint64_t)le32(p) | ((uint64_t)le32(p + 4) << 32); }
-uint16_t le16(const uint8_t* p) { return (uint16_t)(p[0] | (p[1] << 8)); }
+using bgzf::le16;
+using bgzf::le32;
+using bgzf::le64;
+using bgzf::Chunk;
+using Bgzf = bgzf::Reader;
 
-// ---- BGZF reader: one inflated block at a time, addressed by virtual offsets (coffset << 16 | uoffset) ----
-struct Bgzf {
-  FILE* f = nullptr;
-  int64_t block_addr = -1, next_addr = 0;         // file offset of the block in `data` / of the one after it
-  std::vector<uint8_t> data;                      // inflated bytes of the current block
-  size_t at = 0;
-  bool bad = false;
-  ~Bgzf() { if (f) std::fclose(f); }
-  bool load(int64_t addr) {                       // false: end of file or a damaged block (bad)
-    uint8_t head[18];
-    if (fseeko(f, (off_t)addr, SEEK_SET) != 0) { bad = true; return false; }
-    const size_t got = std::fread(head, 1, 18, f);
-    if (got == 0) return false;
-    if (got != 18 || head[0] != 0x1f || head[1] != 0x8b || head[2] != 8 || !(head[3] & 4)) { bad = true; return false; }
-    // the extra field holds the BC subfield (possibly after others)
-    const int xlen = le16(head + 10);
-    std::vector<uint8_t> extra((size_t)xlen);
-    std::memcpy(extra.data(), head + 12, std::min<size_t>(6, (size_t)xlen));
-    if (xlen > 6 && std::fread(extra.data() + 6, 1, (size_t)xlen - 6, f) != (size_t)xlen - 6) { bad = true; return false; }
-    int bsize = -1;
-    for (int k = 0; k + 4 <= xlen;) {
-      const int slen = le16(extra.data() + k + 2);
-      if (extra[(size_t)k] == 'B' && extra[(size_t)k + 1] == 'C' && slen == 2 && k + 6 <= xlen) bsize = le16(extra.data() + k + 4) + 1;
-      k += 4 + slen;
-    }
-    if (bsize < 12 + xlen + 8) { bad = true; return false; }
-    const size_t clen = (size_t)bsize - 12 - (size_t)xlen - 8;
-    std::vector<uint8_t> comp(clen + 8);
-    if (std::fread(comp.data(), 1, clen + 8, f) != clen + 8) { bad = true; return false; }
-    const uint32_t isize = le32(comp.data() + clen + 4);
-    if (isize > 65536) { bad = true; return false; }
-    // (inflated into a buffer of its own and committed only once the block is whole: a damaged block never replaces --
-    // or half-overwrites -- the bytes block_addr stands for)
-    std::vector<uint8_t> fresh(isize);
-    if (isize) {
-      z_stream zs; std::memset(&zs, 0, sizeof(zs));
-      if (inflateInit2(&zs, -15) != Z_OK) { bad = true; return false; }
-      zs.next_in = comp.data(); zs.avail_in = (uInt)clen; zs.next_out = fresh.data(); zs.avail_out = isize;
-      const int rc = inflate(&zs, Z_FINISH);
-      inflateEnd(&zs);
-      if (rc != Z_STREAM_END || zs.total_out != isize || (uint32_t)crc32(crc32(0L, Z_NULL, 0), fresh.data(), isize) != le32(comp.data() + clen)) { bad = true; return false; }
-    }
-    data.swap(fresh);
-    block_addr = addr; next_addr = addr + bsize; at = 0;
-    return true;
-  }
-  bool seek(uint64_t voff) {
-    const int64_t addr = (int64_t)(voff >> 16);
-    if (addr != block_addr && !load(addr)) return false;
-    at = (size_t)(voff & 0xffff);
-    return at <= data.size();
-  }
-  uint64_t tell() const { return at < data.size() || block_addr < 0 ? (((uint64_t)block_addr) << 16) | at : ((uint64_t)next_addr) << 16; }
-  bool read(void* dst, size_t n) {                // false: fewer than n bytes left (end of file when !bad and nothing was read)
-    uint8_t* out = (uint8_t*)dst;
-    while (n) {
-      if (block_addr < 0 || at >= data.size()) {
-        do { if (!load(block_addr < 0 ? 0 : next_addr)) return false; } while (data.empty());    // (empty blocks: the end-of-file marker)
-      }
-      const size_t k = std::min(n, data.size() - at);
-      std::memcpy(out, data.data() + at, k);
-      out += k; at += k; n -= k;
-    }
-    return true;
-  }
-};
-
-struct Chunk { uint64_t beg, end; };
 struct RefIndex { std::map<uint32_t, std::vector<Chunk>> bins; std::vector<uint64_t> linear; };
 
 struct ReadGroup { std::string id, sample, library; };
@@ -182,17 +120,6 @@ int read_record(Bgzf& z, Record& r) {
   return parse_record(r) ? 1 : LTR_ERR_INVALID;
 }
 
-// reg2bins of the SAM specification (5.3): the bins a region [beg, end) can overlap
-void reg2bins(int64_t beg, int64_t end, std::vector<uint32_t>& bins) {
-  --end;
-  bins.push_back(0);
-  for (int64_t k = 1 + (beg >> 26); k <= 1 + (end >> 26); ++k) bins.push_back((uint32_t)k);
-  for (int64_t k = 9 + (beg >> 23); k <= 9 + (end >> 23); ++k) bins.push_back((uint32_t)k);
-  for (int64_t k = 73 + (beg >> 20); k <= 73 + (end >> 20); ++k) bins.push_back((uint32_t)k);
-  for (int64_t k = 585 + (beg >> 17); k <= 585 + (end >> 17); ++k) bins.push_back((uint32_t)k);
-  for (int64_t k = 4681 + (beg >> 14); k <= 4681 + (end >> 14); ++k) bins.push_back((uint32_t)k);
-}
-
 bool load_index(Reader& R, std::string* err) {
   FILE* f = std::fopen((R.path + ".bai").c_str(), "rb");
   if (!f && R.path.size() > 4) f = std::fopen((R.path.substr(0, R.path.size() - 4) + ".bai").c_str(), "rb");
@@ -216,7 +143,7 @@ bool load_index(Reader& R, std::string* err) {
       if (!need((size_t)n_chunk * 16)) return false;
       std::vector<Chunk> ch((size_t)n_chunk);
       for (uint32_t c = 0; c < n_chunk; ++c, at += 16) ch[c] = {le64(b.data() + at), le64(b.data() + at + 8)};
-      if (bin != 37450) R.index[r].bins[bin] = std::move(ch);                 // (37450: the metadata pseudo-bin)
+      if (bin != bgzf::kMetaBin) R.index[r].bins[bin] = std::move(ch);                 // (37450: the metadata pseudo-bin)
     }
     if (!need(4)) return false;
     const uint32_t n_intv = le32(b.data() + at); at += 4;
@@ -284,22 +211,7 @@ bool set_region(Reader& R, const std::string& chrom, int32_t start, int32_t end)
   R.done = false;
   if ((size_t)R.tid >= R.index.size() || R.end <= R.beg) { R.done = true; return true; }
   const RefIndex& ix = R.index[(size_t)R.tid];
-  std::vector<uint32_t> bins;
-  reg2bins(R.beg, R.end, bins);
-  uint64_t min_off = 0;
-  if (!ix.linear.empty()) min_off = ix.linear[std::min<size_t>((size_t)(R.beg >> 14), ix.linear.size() - 1)];
-  for (uint32_t bn : bins) {
-    auto b = ix.bins.find(bn);
-    if (b == ix.bins.end()) continue;
-    for (const Chunk& c : b->second) if (c.end > min_off) R.todo.push_back(c);
-  }
-  std::sort(R.todo.begin(), R.todo.end(), [](const Chunk& a, const Chunk& b) { return a.beg < b.beg; });
-  std::vector<Chunk> merged;
-  for (const Chunk& c : R.todo) {
-    if (!merged.empty() && c.beg <= merged.back().end) merged.back().end = std::max(merged.back().end, c.end);
-    else merged.push_back(c);
-  }
-  R.todo.swap(merged);
+  R.todo = bgzf::query_chunks(ix.bins, ix.linear, R.beg, R.end);
   if (R.todo.empty()) R.done = true;
   return true;
 }

@@ -32,6 +32,7 @@
 #include <unistd.h>
 #include <zlib.h>
 
+#include "ltr_bgzf.h"
 #include "ltr_internal.h"
 
 namespace {
@@ -129,30 +130,6 @@ int add_fasta(ltr_fasta* fa, const std::string& path, std::string* err) {
   return LTR_OK;
 }
 
-// ---- BGZF ------------------------------------------------------------------------------------------------
-constexpr size_t kBgzfBlock = 0xff00;                           // uncompressed bytes per block (htslib's BGZF_BLOCK_SIZE)
-const uint8_t kBgzfEof[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-
-bool bgzf_write_block(FILE* f, const uint8_t* data, size_t n) {
-  uint8_t out[0x10000];
-  z_stream zs; std::memset(&zs, 0, sizeof(zs));
-  if (deflateInit2(&zs, Z_DEFAULT_COMPRESSION, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) return false;
-  zs.next_in = const_cast<uint8_t*>(data); zs.avail_in = (uInt)n;
-  zs.next_out = out + 18; zs.avail_out = sizeof(out) - 18 - 8;
-  const int rc = deflate(&zs, Z_FINISH);
-  const size_t clen = zs.total_out;
-  deflateEnd(&zs);
-  if (rc != Z_STREAM_END) return false;                         // (0xff00 bytes always fit: deflate's worst case adds 5 bytes per 16 KB)
-  const size_t total = 18 + clen + 8;
-  const uint8_t head[18] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0,
-                            (uint8_t)((total - 1) & 0xff), (uint8_t)((total - 1) >> 8)};
-  std::memcpy(out, head, 18);
-  const uint32_t crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), data, (uInt)n);
-  uint8_t* tail = out + 18 + clen;
-  for (int k = 0; k < 4; ++k) { tail[k] = (uint8_t)(crc >> (8 * k)); tail[4 + k] = (uint8_t)((uint32_t)n >> (8 * k)); }
-  return std::fwrite(out, 1, total, f) == total;
-}
-
 struct Record { int32_t pos; std::string text; };
 
 }  // namespace
@@ -168,7 +145,7 @@ struct ltr_vcf_writer {
     if (!bgzf) { if (std::fwrite(s.data(), 1, s.size(), f) != s.size()) failed = true; return; }
     buf.insert(buf.end(), s.begin(), s.end());
     size_t done = 0;
-    while (buf.size() - done >= kBgzfBlock) { if (!bgzf_write_block(f, buf.data() + done, kBgzfBlock)) failed = true; done += kBgzfBlock; }
+    while (buf.size() - done >= ltr::bgzf::kBlock) { if (!ltr::bgzf::write_block(f, buf.data() + done, ltr::bgzf::kBlock)) failed = true; done += ltr::bgzf::kBlock; }
     if (done) buf.erase(buf.begin(), buf.begin() + (long)done);
   }
   void write_all() {                                            // write_all_records, vcf_writer.h:38-45
@@ -358,8 +335,8 @@ int ltr_vcf_writer_close(ltr_vcf_writer* w) {                              // cl
     w->write_all();
     if (w->bgzf) {
       size_t done = 0;
-      while (done < w->buf.size()) { const size_t n = std::min(kBgzfBlock, w->buf.size() - done); if (!bgzf_write_block(w->f, w->buf.data() + done, n)) w->failed = true; done += n; }
-      if (std::fwrite(kBgzfEof, 1, sizeof(kBgzfEof), w->f) != sizeof(kBgzfEof)) w->failed = true;
+      while (done < w->buf.size()) { const size_t n = std::min(ltr::bgzf::kBlock, w->buf.size() - done); if (!ltr::bgzf::write_block(w->f, w->buf.data() + done, n)) w->failed = true; done += n; }
+      if (std::fwrite(ltr::bgzf::kEof, 1, sizeof(ltr::bgzf::kEof), w->f) != sizeof(ltr::bgzf::kEof)) w->failed = true;
     }
     if (std::fclose(w->f) != 0) w->failed = true;
     if (w->failed) rc = LTR_ERR_INVALID;

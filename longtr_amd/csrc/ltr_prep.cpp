@@ -10,6 +10,7 @@
 //   HaplotypeGenerator::add_haplotype_block     :530-578
 //   HaplotypeGenerator::fuse_haplotype_blocks   :580-607
 //   SeqStutterGenotyper::build_haplotype        src/seq_stutter_genotyper.cpp:416-482
+//   HaplotypeGenerator::add_vcf_haplotype_block :497-525 (--ref-vcf: ltr_build_vcf_haplotype)
 // NOT here: the partial-order-alignment clustering branch of gen_candidate_seqs (:376-472: spoa, an
 // un-vendored dependency, with std::random_device subsampling) -- ltr_build_haplotype reports how many reads
 // the reference would have handed to it.
@@ -390,6 +391,58 @@ int ltr_build_haplotype(ltr_ctx* ctx, const ltr_read_set* rs, int32_t n_samples,
     for (const std::string& s : seqs) put(s);
     put(rflank);
     if (res->bytes.empty()) res->bytes.push_back(0);
+    res->inexact.assign(seqs.size(), 0);
+    res->view.n_blocks = 3; res->view.block_start = res->bstart.data(); res->view.block_end = res->bend.data();
+    res->view.is_repeat = res->is_rep.data(); res->view.period = res->period.data(); res->view.n_alleles = res->nall.data();
+    res->view.allele_bytes = res->bytes.data(); res->view.allele_off = res->off.data();
+    *out = owner.release();
+    return LTR_OK;
+  } catch (const std::bad_alloc&) { return LTR_ERR_NOMEM; } catch (...) { return LTR_ERR_INVALID; }
+}
+
+// SeqStutterGenotyper::build_haplotype (:438-452) with a --ref-vcf panel: add_vcf_haplotype_block
+// (HaplotypeGenerator.cpp:497-525) + fuse_haplotype_blocks (:580-607) -> [reference flank][panel alleles][reference flank].
+int ltr_build_vcf_haplotype(ltr_ctx* ctx, const ltr_read_set* rs, int32_t pos, const char* alleles, const int64_t* allele_off,
+                            int32_t n_alleles, int32_t period, const uint8_t* chrom_seq, int64_t chrom_seq_start,
+                            int64_t chrom_seq_len, int64_t chrom_len, ltr_hap_result** out) {
+  if (!rs || !alleles || !allele_off || n_alleles < 1 || !chrom_seq || !out || period < 1 || pos < 0) return LTR_ERR_INVALID;
+  *out = nullptr;
+  ltr::TimedCall timed(ctx, ltr::kTimerHapBuild);
+  try {
+    const Chrom chrom{chrom_seq, chrom_seq_start, chrom_seq_len};
+    const int kRefFlank = 35;                                  // REF_FLANK_LEN, HaplotypeGenerator.h
+    std::unique_ptr<ltr_hap_result> owner(new ltr_hap_result());
+    ltr_hap_result* res = owner.get();
+    auto fail = [&](const std::string& msg) { res->failure = msg; std::memset(&res->view, 0, sizeof(res->view)); *out = owner.release(); return LTR_OK; };
+    std::vector<std::string> seqs((size_t)n_alleles);
+    for (int32_t i = 0; i < n_alleles; ++i) {
+      if (allele_off[i] < 0 || allele_off[i + 1] < allele_off[i]) return LTR_ERR_INVALID;
+      std::string s(alleles + allele_off[i], (size_t)(allele_off[i + 1] - allele_off[i]));
+      // (documented deviations: the reference would take symbolic alleles as literal bases.  "<DEL>" as an ALT is what
+      // write_vcf_record writes for a block allele with no bases (get_alleles :700-712) and is read back as that allele.)
+      if (i > 0 && s == "<DEL>") { seqs[(size_t)i].clear(); continue; }
+      if (s.empty() || s.find_first_of("<>*[]") != std::string::npos) return fail("Symbolic allele " + s + " in the reference VCF: panel alleles must be sequences");
+      for (char& c : s) c = upper(c);
+      seqs[(size_t)i] = s;
+    }
+    int32_t min_aln_start = INT_MAX, max_aln_stop = INT_MIN;    // build_haplotype :421-426 over ALL reads
+    for (const PreparedRead& p : rs->reads) { min_aln_start = std::min(min_aln_start, p.start); max_aln_stop = std::max(max_aln_stop, p.stop); }
+    // add_vcf_haplotype_block, :497-525
+    const int64_t rstart = pos, rend = (int64_t)pos + (int64_t)seqs[0].size();
+    if (rstart < kRefFlank || rend + kRefFlank >= chrom_len) return fail("Haplotype blocks are too near to the chromosome ends");
+    // (documented deviation: the reference asserts here, :504)
+    if (chrom.sub_upper(rstart, rend - rstart) != seqs[0]) return fail("The reference VCF's REF allele does not match the reference sequence");
+    // fuse_haplotype_blocks, :580-607
+    const int32_t min_start = (int32_t)std::min<int64_t>(rstart - 10, std::max<int64_t>(rstart - kRefFlank, min_aln_start));
+    const int32_t max_stop = (int32_t)std::max<int64_t>(rend + 10, std::min<int64_t>(rend + kRefFlank, max_aln_stop));
+    const std::string lflank = chrom.sub_upper(min_start, rstart - min_start), rflank = chrom.sub_upper(rend, max_stop - rend);
+    res->bstart = {min_start, (int32_t)rstart, (int32_t)rend}; res->bend = {(int32_t)rstart, (int32_t)rend, max_stop};
+    res->is_rep = {0, 1, 0}; res->period = {0, period, 0}; res->nall = {1, n_alleles, 1};
+    res->off.push_back(0);
+    auto put = [&](const std::string& s) { res->bytes.insert(res->bytes.end(), s.begin(), s.end()); res->off.push_back((int64_t)res->bytes.size()); };
+    put(lflank);
+    for (const std::string& s : seqs) put(s);
+    put(rflank);
     res->inexact.assign(seqs.size(), 0);
     res->view.n_blocks = 3; res->view.block_start = res->bstart.data(); res->view.block_end = res->bend.data();
     res->view.is_repeat = res->is_rep.data(); res->view.period = res->period.data(); res->view.n_alleles = res->nall.data();
