@@ -15,7 +15,8 @@ from . import _abi
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("LTR_GPU_LIB") or os.path.join(CSRC, "libltr_gpu.so")   # override: A/B builds only
-SOURCES = ["ltr_gpu.hip", "ltr_short.hip", "ltr_nw.hip", "ltr_host.cpp", "ltr_genotype.cpp", "ltr_vcf.cpp", "ltr_prep.cpp", "ltr_io.cpp", "ltr_bam.cpp", "ltr_vcf_in.cpp"]
+KERNEL_TUS = ["ltr_k_one.hip", "ltr_k_pack.hip", "ltr_k_plan.hip", "ltr_k_wg.hip", "ltr_k_wgt.hip", "ltr_k_exact.hip", "ltr_plan.cpp"]      # one family of DP kernels each
+SOURCES = ["ltr_ctx.hip", "ltr_plan_build.hip", "ltr_plan_run.hip", "ltr_posterior.hip"] + KERNEL_TUS + ["ltr_short.hip", "ltr_nw.hip", "ltr_host.cpp", "ltr_genotype.cpp", "ltr_vcf.cpp", "ltr_prep.cpp", "ltr_io.cpp", "ltr_bam.cpp", "ltr_vcf_in.cpp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-honor-nans", "-std=c++17", "-fPIC", "-shared", "-pthread", "-Wall"]
 LINK_LIBS = ["-lz"]                                         # BGZF blocks (ltr_bgzf.h: BAM, VCF writer, tabix-indexed VCF input)
 
@@ -52,8 +53,6 @@ class LtrError(RuntimeError):
         self.code = code
 
 
-KERNEL_TUS = ["ltr_k_one.hip", "ltr_k_pack.hip", "ltr_k_plan.hip", "ltr_k_wg.hip", "ltr_k_wgt.hip", "ltr_k_exact.hip", "ltr_plan.cpp"]      # one family of DP kernels each
-SOURCES = ["ltr_gpu.hip"] + KERNEL_TUS + SOURCES[1:]
 OBJ_DIR = os.path.join(CSRC, "build")
 
 
@@ -574,6 +573,43 @@ def vcf_index(path):
     rc = L.ltr_vcf_index(os.fsencode(path))
     if rc != 0:
         raise LtrError(rc, f"ltr_vcf_index {path}")
+
+
+def debug_describe_batch(batch, params=None, mode=-1, n_cu=256):
+    """Test hook ltr_debug_describe_batch (csrc/ltr_plan.h): the host half of ltr_plan_create on a _abi.PackedBatch, no GPU.  dict(n_pairs,
+    ll_size, max_len, cells, input_bytes, class_first, and per SORTED pair n, m, out_idx, key) or LtrError with the library's text."""
+    L = lib()
+    L.ltr_debug_describe_batch.argtypes = [C.POINTER(_abi.AlignParams), C.c_int, C.c_int, C.POINTER(_abi.LocusBatch), C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
+    L.ltr_debug_num_classes.restype = C.c_int
+    prm = params or _abi.default_params()
+    cap = int(np.sum(np.diff(batch.locus_read_off) * np.diff(batch.locus_hap_off))) if batch.n_loci > 0 else 0
+    cap = max(cap, 1)
+    i64, f64 = np.zeros(3, dtype=np.int64), np.zeros(2, dtype=np.float64)
+    first = np.zeros(L.ltr_debug_num_classes() + 1, dtype=np.int32)
+    n, m, key = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int16)
+    out_idx = np.zeros(cap, dtype=np.int64)
+    err = C.create_string_buffer(512)
+    rc = L.ltr_debug_describe_batch(C.byref(prm), int(mode), int(n_cu), C.byref(batch.struct), _p(i64), _p(f64), _p(first), cap, _p(n), _p(m), _p(out_idx), _p(key), err, len(err))
+    if rc != 0:
+        raise LtrError(rc, err.value.decode())
+    k = int(i64[0])
+    return dict(n_pairs=k, ll_size=int(i64[1]), max_len=int(i64[2]), cells=float(f64[0]), input_bytes=float(f64[1]), class_first=first,
+                n=n[:k], m=m[:k], out_idx=out_idx[:k], key=key[:k])
+
+
+def debug_threshold_groups(class_first, merge=True, keep_waves=False):
+    """Test hook ltr_debug_threshold_groups (ltrp::threshold_groups): per class (waves, strip width, pairs of the launch it leads)."""
+    L = lib()
+    L.ltr_debug_threshold_groups.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    first = np.ascontiguousarray(class_first, dtype=np.int32)
+    nk = L.ltr_debug_num_classes()
+    assert first.size == nk + 1
+    nw, w, npairs = (np.zeros(nk, dtype=np.int32) for _ in range(3))
+    rc = L.ltr_debug_threshold_groups(_p(first), int(bool(merge)), int(bool(keep_waves)), _p(nw), _p(w), _p(npairs))
+    if rc != 0:
+        raise LtrError(rc, "ltr_debug_threshold_groups")
+    return nw, w, npairs
 
 
 def tbi_parse(tbi_path, max_refs=4096):

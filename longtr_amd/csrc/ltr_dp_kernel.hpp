@@ -1,4 +1,4 @@
-// ltr_dp_kernel.hpp -- device side of the read-vs-haplotype DP (included by ltr_gpu.hip only).
+// ltr_dp_kernel.hpp -- device side of the read-vs-haplotype DP (included by the kernel translation units, ltr_k_*.hip).
 //
 // Replaces HapAligner::align_seq_to_hap (reference src/SeqAlignment/HapAligner.cpp:236-343).
 //

@@ -1,4 +1,4 @@
-// ltr_dp_types.h -- what the host side (ltr_gpu.hip) and the kernel translation units (ltr_k_*.hip) share:
+// ltr_dp_types.h -- what the host side (ltr_ctx.h and its four units) and the kernel translation units (ltr_k_*.hip) share:
 // pair descriptors, kernel arguments, launch-class constants.  No device code.
 #ifndef LTR_DP_TYPES_H_
 #define LTR_DP_TYPES_H_

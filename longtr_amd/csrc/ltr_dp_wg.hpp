@@ -1,4 +1,4 @@
-// ltr_dp_wg.hpp -- ONE pair per WORKGROUP of NW wavefronts (included by ltr_gpu.hip after
+// ltr_dp_wg.hpp -- ONE pair per WORKGROUP of NW wavefronts (included by ltr_k_*.hip after
 // ltr_dp_kernel.hpp).  Replaces HapAligner::align_seq_to_hap (reference
 // src/SeqAlignment/HapAligner.cpp:236-343) for the pairs the one-wave kernels serve badly:
 //

@@ -1,4 +1,4 @@
-// ltr_internal.h -- shared between the HIP side (ltr_gpu.hip) and the host mirror (ltr_host.cpp).
+// ltr_internal.h -- shared between the HIP side (ltr_ctx.hip and the units around it, ltr_short.hip, ltr_nw.hip) and the host mirror (ltr_host.cpp).
 #ifndef LTR_INTERNAL_H_
 #define LTR_INTERNAL_H_
 
@@ -214,6 +214,11 @@ struct TimedCall {
     if (outer) add_time(ctx, which, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
   }
 };
+
+// ltr_ctx_set_debug(ctx, "trace", 1) on any context: phase prints to stderr (the flag and the clock live in ltr_ctx.hip)
+extern std::atomic<int> g_trace __attribute__((visibility("hidden")));
+double dbg_ms() __attribute__((visibility("hidden")));
+#define LTR_DBG(...) do { if (ltr::g_trace.load(std::memory_order_relaxed)) { std::fprintf(stderr, "[ltr %10.2f ms] ", ltr::dbg_ms()); std::fprintf(stderr, __VA_ARGS__); std::fprintf(stderr, "\n"); std::fflush(stderr); } } while (0)
 
 // Measurement switches of a context (ltr_ctx_set_debug): A/B runs of tests/manual/*.py and profiles/collect.sh.
 // 0 / unset = the library's own rule.  Scheduling only: results never depend on them.

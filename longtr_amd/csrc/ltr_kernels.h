@@ -1,7 +1,7 @@
 // ltr_kernels.h -- host-callable entry points of the kernel translation units (ltr_k_*.hip).
 // Every family of DP kernels is compiled in a TU of its own (the template instances of one family take
 // tens of seconds of hipcc each; side by side they build in the time of the slowest) and is reached from
-// ltr_gpu.hip through these launchers.  `occ_*` = resident workgroups per CU
+// ltr_plan_build.hip (occupancy) and ltr_plan_run.hip (launches) through these launchers.  `occ_*` = resident workgroups per CU
 // (hipOccupancyMaxActiveBlocksPerMultiprocessor) of the family's kernel with strip width W.
 #ifndef LTR_KERNELS_H_
 #define LTR_KERNELS_H_

@@ -1,14 +1,67 @@
 // ltr_plan.h -- host-side planning of a batch (no HIP in here): the table of launch classes, the rule that
 // gives every (read, haplotype) pair its class and launch-order key, and the sort that lays the pairs out
-// class by class, longest first.  ltr_gpu.hip's ltr_plan_create strings these units together with the
-// uploads; tests/test_plan_units.py exercises them on the CPU through the ltr_debug_* entry points.
+// class by class, longest first, and describe_batch, the host half of ltr_plan_create that strings them together
+// (ltr_plan_build.hip adds the uploads); tests/test_plan_units.py exercises them on the CPU through the ltr_debug_* entry points.
 #ifndef LTR_PLAN_H_
 #define LTR_PLAN_H_
 
+#include <algorithm>
 #include <cstdint>
+#include <cstdlib>
+#include <new>
+#include <string>
 #include <vector>
 
+#include "../../include/ltr_gpu.h"
 #include "ltr_dp_types.h"
+
+namespace ltr { struct DebugKnobs; }
+namespace ltrp {
+// page-locked host memory for RawBuf (hipHostMalloc / hipHostFree behind them: ltr_ctx.hip); nullptr = none to be had
+void* pinned_alloc(size_t bytes) __attribute__((visibility("hidden")));
+void pinned_free(void* p) __attribute__((visibility("hidden")));
+}
+
+// Grow-only host array of trivially copyable elements that keeps its storage between uses and never
+// initialises it: the per-plan work arrays (tens of MB: descriptors, costs, sort order) would otherwise be
+// mapped, zero-filled page by page and unmapped again for every plan.
+template <class T>
+struct RawBuf {
+  T* p = nullptr; size_t n = 0, cap = 0;
+  // pinned: page-locked host memory (hipHostMalloc) -- for arrays the library uploads itself: a copy from pinned memory goes
+  // over the DMA engines; from pageable memory it is staged by a copy KERNEL that waits for wave slots behind the persistent
+  // DP launches of the previous chunk (measured on MI355X, ltr_calc_hap_aln_probs on the catalogue: the uploads of chunks
+  // 1 and 2 took 1.1 - 1.6 ms against 0.3 - 0.4 ms for chunk 0, which finds the GPU idle).  Falls back to malloc.
+  bool pinned = false, p_is_pinned = false;
+  RawBuf() = default;
+  RawBuf(const RawBuf&) = delete;
+  RawBuf& operator=(const RawBuf&) = delete;
+  ~RawBuf() __attribute__((visibility("hidden"))) { release(); }
+  void release() { if (p) { if (p_is_pinned) ltrp::pinned_free(p); else std::free(p); } p = nullptr; cap = 0; n = 0; }
+  // NOTE: the contents are UNDEFINED after a growth (resize is not std::vector's: every user rewrites the whole buffer).
+  void resize(size_t m) {
+    if (m > cap) {
+      const size_t c = std::max(m + m / 4, (size_t)1024);
+      // (the contents are never kept across a growth: the old block goes first, so that a context never holds both -- hundreds of
+      // MB of pinned memory each on a 30 000-locus call; hipHostMallocPortable: usable from whichever device is current)
+      release();
+      T* q = nullptr;
+      bool q_pinned = false;
+      if (pinned) { q = (T*)ltrp::pinned_alloc(c * sizeof(T)); q_pinned = (q != nullptr); }
+      if (!q) q = (T*)std::malloc(c * sizeof(T));
+      if (!q) throw std::bad_alloc();
+      p = q; cap = c; p_is_pinned = q_pinned;
+    }
+    n = m;
+  }
+  size_t size() const { return n; }
+  bool empty() const { return n == 0; }
+  T* data() { return p; }
+  T* begin() { return p; }
+  T* end() { return p + n; }
+  T& operator[](size_t i) { return p[i]; }
+  const T& operator[](size_t i) const { return p[i]; }
+};
 
 namespace ltrp {
 
@@ -127,6 +180,48 @@ PairClass classify_pair(const Rules& R, int64_t n, int64_t m, int64_t hap_full_l
 void sort_by_class(const int16_t* bin, const int16_t* key, int64_t n_pairs, int fold_rounds, int n_cu, int32_t* order,
                    int* bin_first /* [kNumKernels + 1] */, int* counts /* [kNumKernels] */, int multi_launch = 0);
 
+// ---- the host half of ltr_plan_create ------------------------------------------------------------------------------------
+// The context's work arrays a description is built in (a view: the context keeps the storage from plan to plan).
+struct BatchScratch {
+  RawBuf<PairDesc>& pairs; RawBuf<PairDesc>& sorted; RawBuf<int16_t>& key; RawBuf<int16_t>& bin; RawBuf<int32_t>& order;
+  RawBuf<uint8_t>& read_acgt; RawBuf<uint8_t>& hap_acgt;
+};
+// What describe_batch decides about a batch; a plan (struct ltr_plan, ltr_ctx.h) starts out as one of these.
+struct __attribute__((visibility("hidden"))) BatchPlan {
+  int64_t n_pairs = 0, ll_size = 0;
+  double cells = 0.0, input_bytes = 0.0;
+  int32_t max_len = 0;
+  int bin_first[kNumKernels + 1] = {0};    // classes kNumFast + c: pairs that start out in exact list c (non-ACGT pairs; mode 4: all)
+  int counts[kNumKernels] = {0};           // pairs per class after folding
+  int x_seed[kNumExact] = {0};          // pairs pre-seeded into every exact list (sorted array ranges bin_first[kNumFast + c] ..)
+  int64_t xcand[kNumExact] = {0};          // pairs that could end up in each exact kernel's list
+  int64_t xstart[kNumExact] = {0};         // (plan kernel: the pairs that start out in a list, counted apart -- the plan kernel scores them itself)
+  std::vector<int32_t> seed;            // host: read length - 1 (or -1 when the read is masked out)
+  std::vector<int32_t> locus_P, locus_H;   // per locus: pools, haplotypes
+  std::vector<int64_t> locus_ll_off;       // per locus: offset of its [P x H] block
+  bool sym_at_create = true;            // indel model was symmetric when the pairs were binned
+  bool xlut = false;                    // LUT / penalty-table exact kernels usable (symmetric model, k600 <= kPenKMax)
+  bool uses_wg = false;                 // some pairs sit in workgroup-kernel classes (symmetric models only)
+  bool use_plan = false;                // the plan kernel (ltr_dp_plan.hpp) scores the one-wave and packed classes
+  bool use_multi = false;               // ... or the multi-width launches do
+};
+// Validates the batch, gives every pair its descriptor, class and key, sorts them (w.sorted, w.order, w.key stay valid for the
+// caller) and fills *d.  mode: ltr_ctx_set_pair_packing.  LTR_OK, or LTR_ERR_INVALID with the reason in *err.
+int describe_batch(const ltr_locus_batch* b, const ModelConsts& mc, int indel_flank_len, int mode, int n_cu, const ltr::DebugKnobs& dbg,
+                   const BatchScratch& w, BatchPlan* d, std::string* err) __attribute__((visibility("hidden")));
+
+// ---- pure pieces of ltr_plan_execute --------------------------------------------------------------------------------------
+// Threshold first pass of the workgroup classes: which kernel scores a class (nw waves, strips of w columns; nw 0 = not a
+// workgroup class with pairs) and how many pairs the launch it leads takes (np 0: led by a class before it).
+// strip width of the threshold kernel that takes strips of W columns: W rounded up to even (the launchers of ltr_k_wgt.hip round
+// whatever they are given the same way, ltrk::wgt_width: a width from here is a fixed point of theirs)
+inline int threshold_strip_width(int W) { return W + (W & 1); }
+struct ThresholdGroups { int nw[kNumFast] = {0}, w[kNumFast] = {0}, np[kNumFast] = {0}; };
+// merge: neighbouring narrow eight-wave classes share a launch (not under per-launch timing); keep_waves: ltr_ctx_set_debug "wgt_keep_waves"
+ThresholdGroups threshold_groups(const int* bin_first, bool merge, bool keep_waves) __attribute__((visibility("hidden")));
+// The ranges of the packed launch of strip width W, widest segments first (their groups last longest): five entries each.
+void pack_ranges(const int* bin_first, int W, int32_t* shift, int32_t* first, int32_t* end, int32_t* grp_end) __attribute__((visibility("hidden")));
+
 // The exact kernels' row test (ltr_dp_kernel.hpp, column_block): the reference aborts a pair when a row's maximum of
 // fl(best + pen(k)), pen(k) = (double)((float)|k| * c), is below -600 (HapAligner.cpp:297-306).  x -> fl(x + p) is monotone, so
 // "some cell reaches -600" is "some cell has best >= thr(k)" with thr(k) the SMALLEST double that does.  Entry k + kPenHalf of
@@ -134,5 +229,17 @@ void sort_by_class(const int16_t* bin, const int16_t* key, int64_t n_pairs, int 
 void build_threshold_table(float c, double* out);
 
 }  // namespace ltrp
+
+// Test hooks of the two units above (tests/test_plan_units.py; the other ltr_debug_* hooks are declared in include/ltr_gpu.h).
+// ltr_debug_describe_batch: ltrp::describe_batch on arrays of its own; out_i64[0..2] = pairs, LL size, longest sequence,
+// out_f64[0..1] = cells, input bytes, class_first[ltr_debug_num_classes() + 1], per sorted pair its descriptor fields
+// (n, m, out_idx) and key; the reason of an LTR_ERR_INVALID goes to err[err_cap].
+// ltr_debug_threshold_groups: ltrp::threshold_groups; nw / w / np hold ltr_debug_num_classes() entries each.
+extern "C" {
+int ltr_debug_describe_batch(const ltr_align_params* p, int mode, int n_cu, const ltr_locus_batch* b, int64_t* out_i64, double* out_f64,
+                             int32_t* class_first, int64_t pair_cap, int32_t* pair_n, int32_t* pair_m, int64_t* pair_out_idx, int16_t* pair_key,
+                             char* err, int err_cap);
+int ltr_debug_threshold_groups(const int32_t* class_first, int merge, int keep_waves, int32_t* nw, int32_t* w, int32_t* np);
+}
 
 #endif

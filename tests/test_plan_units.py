@@ -226,3 +226,132 @@ def test_risky_pairs_go_straight_to_the_exact_body_per_gap_direction():
     assert fam(700 - 573, 700, params=asym) != 3 and fam(700 - 574, 700, params=asym) == 3
     # not in the explicit modes (mode 0: every pair keeps its certificate class)
     assert fam(700, 100, mode=0) != 3
+
+
+# ---- the host half of ltr_plan_create (ltrp::describe_batch) and the pure pieces of ltr_plan_execute, without a GPU ----
+
+def _random_batch(rng, n_loci=40):
+    loci = []
+    for _ in range(n_loci):
+        tr = int(rng.integers(20, 900))
+        haps = [bytes(rng.choice(list(b"ACGT"), size=tr + 70 + int(rng.integers(-15, 15))).astype(np.uint8)) for _ in range(int(rng.integers(1, 6)))]
+        reads = [bytes(rng.choice(list(b"ACGT"), size=max(2, tr + int(rng.integers(-30, 30)))).astype(np.uint8)) for _ in range(int(rng.integers(1, 12)))]
+        if rng.random() < 0.2:
+            reads[0] = reads[0][:1] + b"N" + reads[0][2:]                # a pair outside ACGT: starts out in an exact list
+        if rng.random() < 0.2:
+            haps.append(b"ACGT" * 10)                                    # 40 <= 60 bases: the constant-score shortcut
+        if rng.random() < 0.1:
+            reads.append(bytes(rng.choice(list(b"ACGT"), size=tr + 700).astype(np.uint8)))      # more than 600 longer than any window: the other shortcut
+        loci.append((reads, haps))
+    return _abi.PackedBatch(loci)
+
+
+def test_describe_batch_rejects_invalid_batches_with_the_library_text():
+    """Every LTR_ERR_INVALID exit of the host half, each with the text ltr_plan_create reports."""
+    good = lambda: _abi.PackedBatch([([b"ACGT" * 30, b"ACGTT" * 20], [b"ACGT" * 40, b"AC" * 70])])
+
+    def fails(batch, text, params=None):
+        with pytest.raises(_lib.LtrError) as e:
+            _lib.debug_describe_batch(batch, params=params)
+        assert e.value.code == _abi.LTR_ERR_INVALID and text in str(e.value), str(e.value)
+
+    b = good(); b.struct.n_reads = -1
+    fails(b, "negative counts")
+    b = good(); b.struct.read_off = None
+    fails(b, "null offset array")
+    b = good(); b.locus_read_off[1] = 3
+    fails(b, "locus offsets out of range")
+    b = good(); b.read_off[1], b.read_off[2] = b.read_off[2], b.read_off[1] - 1
+    fails(b, "read offsets not ascending")
+    b = good(); b.hap_off[1] = b.hap_off[2] + 1
+    fails(b, "haplotype offsets not ascending")
+    b = good(); b.read_off[1] = b.read_off[0]
+    fails(b, "empty or oversized read")
+    fails(_abi.PackedBatch([([b"ACGT" * 30], [b"A" * ((1 << 20) + 1)])]), "bad haplotype length")       # (real bytes: the ACGT scan reads them first)
+    p = _abi.default_params(); p.indel_flank_len = 0
+    fails(_abi.PackedBatch([([b"ACGT" * 30], [b"AC" * 35])]), "haplotype window is empty", params=p)      # 70 bases less 2 x 35 of flank: nothing left
+    assert _lib.debug_describe_batch(good())["n_pairs"] == 4
+
+
+def test_describe_batch_sorts_every_pair_into_its_class():
+    rng = np.random.default_rng(5)
+    for mode in (-1, 0, 1):
+        batch = _random_batch(rng)
+        d = _lib.debug_describe_batch(batch, mode=mode, n_cu=N_CU)
+        first = d["class_first"]
+        assert d["n_pairs"] == batch.ll_size == d["ll_size"] and first[0] == 0 and first[NK] == d["n_pairs"] and (np.diff(first) >= 0).all()
+        assert sorted(d["out_idx"].tolist()) == list(range(batch.ll_size))
+        prm = _abi.default_params()
+        for k in range(NK):
+            seg = slice(first[k], first[k + 1])
+            assert (np.diff(d["key"][seg].astype(np.int32)) <= 0).all()                      # keys descend inside a class
+            if k < NK - 6:
+                ck = class_info(k)
+                for n, m in zip(d["n"][seg], d["m"][seg]):
+                    k0 = classify(int(n), int(m), mode=mode, pairs=d["n_pairs"])[0]
+                    if mode != -1:
+                        assert k0 == k
+                    else:                                                                    # automatic mode folds an under-filled class into a wider one of its family
+                        c0 = class_info(k0)
+                        assert (c0["family"], c0["waves"], c0["lanes"]) == (ck["family"], ck["waves"], ck["lanes"]) and c0["W"] <= ck["W"], (k0, k)
+            if k < NK - 6 and class_info(k)["family"] == 1:
+                ci = class_info(k)
+                assert ((d["m"][seg] - 1) <= ci["lanes"] * ci["W"]).all()                   # every pair fits the class it was sorted into
+        # cells: sum of n * m over the pairs that are not shortcuts, pair by pair inside a locus, locus by locus
+        # (a shortcut by the reference's own rule, HapAligner.cpp:241-252: haplotype of at most 60 bases, or lengths more than 600 apart)
+        by_out = np.argsort(d["out_idx"], kind="stable")
+        locus_of = np.searchsorted(batch.ll_off, d["out_idx"][by_out], side="right") - 1
+        hap_len = np.diff(batch.hap_off)
+        cells, longest = 0.0, 1
+        for l in range(batch.n_loci):
+            acc = 0.0
+            H = int(batch.locus_hap_off[l + 1] - batch.locus_hap_off[l])
+            for i in by_out[locus_of == l]:
+                hl = int(hap_len[batch.locus_hap_off[l] + (d["out_idx"][i] - batch.ll_off[l]) % H])
+                shortcut = hl <= 60 or abs(int(d["n"][i]) - int(d["m"][i])) > 600
+                assert (d["key"][i] == 0) == shortcut and (shortcut or d["n"][i] == hl - 60)   # (window: the haplotype less 2 x 30 of flank)
+                if not shortcut:
+                    acc += float(d["n"][i]) * float(d["m"][i])
+                    longest = max(longest, int(d["n"][i]), int(d["m"][i]))
+            cells += acc
+        assert d["cells"] == cells and d["max_len"] == longest                          # (shortcut pairs are never laid out: they do not size the tables)
+        assert d["input_bytes"] == float(batch.read_off[-1] + batch.hap_off[-1] + 8 * batch.ll_size)
+
+
+def test_threshold_groups_merge_neighbouring_narrow_eight_wave_classes():
+    wg = [k for k in range(NK) if L.ltr_kernel_family(k) == 2 and class_info(k)["waves"] in (4, 8)]
+    rng = np.random.default_rng(9)
+    for _ in range(50):
+        counts = np.zeros(NK, dtype=np.int64)
+        for k in rng.choice(wg, size=int(rng.integers(1, 8)), replace=False):
+            counts[k] = int(rng.integers(1, 500))
+        counts[int(rng.integers(0, 20))] = 1000                                               # (classes of other families are left alone)
+        first = np.zeros(NK + 1, dtype=np.int32); first[1:] = np.cumsum(counts)
+        for merge in (True, False):
+            nw, w, npairs = _lib.debug_threshold_groups(first, merge=merge)
+            assert npairs.sum() == counts[wg].sum() and (nw[counts == 0] == 0).all() and (nw[[k for k in range(NK) if k not in wg]] == 0).all()
+            lead = -1
+            for k in wg:
+                if counts[k] == 0:
+                    continue
+                assert nw[k] in (4, 8) and w[k] % 2 == 0
+                if npairs[k] == 0:                                                            # led by another class: its pairs follow the leader's without a gap
+                    assert merge and lead >= 0 and nw[k] == 8 and w[k] <= 10 and w[lead] >= w[k]
+                    assert all(counts[j] == 0 or (nw[j] == 8 and w[j] <= 10) for j in range(lead, k))
+                else:
+                    assert npairs[k] >= counts[k]
+                    lead = k
+                    run_end = k
+                    while sum(counts[k:run_end + 1]) < npairs[k]:
+                        run_end += 1
+                    assert sum(counts[k:run_end + 1]) == npairs[k]                           # a leader's launch = a contiguous range of the sorted pairs
+            if not merge:
+                assert (npairs[wg] == counts[wg]).all()
+        # "wgt_keep_waves": every class keeps its waves and its own launch, whatever `merge` says
+        for merge in (True, False):
+            nw, w, npairs = _lib.debug_threshold_groups(first, merge=merge, keep_waves=True)
+            assert (npairs[wg] == counts[wg]).all()
+            for k in wg:
+                if counts[k]:
+                    ci = class_info(k)
+                    assert nw[k] == ci["waves"] and w[k] == ci["W"] + (ci["W"] & 1)
