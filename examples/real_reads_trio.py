@@ -12,9 +12,12 @@
   read x haplotype   -> ltr_calc_hap_aln_probs      (GPU; every locus in one call)
   phasing priors     -> ltr_phasing_priors          (the HP tags, process_phased_reads' rule: --phased-bam)
   posteriors, GT     -> ltr_posteriors
+                        or, with --prune-alleles, ltr_plan_create / _execute + ltr_plan_genotype: every locus in one resident
+                        plan, posteriors -> uncalled alleles removed -> posteriors over the surviving haplotypes
+                        (SeqStutterGenotyper::genotype, seq_stutter_genotyper.cpp:632-645)
   VCF                -> ltr_vcf_header, ltr_vcf_record, ltr_vcf_writer_*
 
-    python examples/real_reads_trio.py [out.vcf.gz] [--ref-vcf panel.vcf.gz]
+    python examples/real_reads_trio.py [out.vcf.gz] [--ref-vcf panel.vcf.gz] [--prune-alleles]
 
 run(...) returns the per-locus results (used by tests/test_gpu_real_reads.py, which also bit-compares the
 LL matrices with the CPU oracle and checks the trio for Mendelian consistency)."""
@@ -76,10 +79,41 @@ def phasing_priors(sample, hp):
     return p1, p2
 
 
-def run(ctx, vcf_path=None, max_loci=None, tmp_dir="/tmp", ref_vcf=None):
+def plan_genotype(ctx, todo):
+    """Every locus in ONE resident plan (pools trimmed like HapAligner::process_reads) and one ltr_plan_genotype call: per locus
+    the dict of Plan.genotype (final blocks, posteriors, best pairs, per-read scores in the final columns)."""
+    flat, lro, pool_index, p1s, p2s, labs = [], [0], [], [], [], []
+    for l in todo:
+        alns, rb = l["alns"], l["blocks"][1]
+        n, idx = _lib.pool_reads([a["seq"] for a in alns])
+        first = {}
+        for i, q in enumerate(idx):
+            first.setdefault(int(q), i)
+        pools = []
+        for q in range(n):                                          # the pool's first read stands for it (ReadPooler)
+            a = alns[first[q]]
+            rc, lt, rt = _lib.trim_alignment(a, rb["start"], rb["end"], ctx.params.indel_flank_len)
+            assert rc == 0
+            t = a["seq"][lt:len(a["seq"]) - rt]
+            pools.append(t if t else l["blocks"][0]["alleles"][0][-5:] + l["blocks"][2]["alleles"][0][:5])     # HapAligner.cpp:820-823
+        flat.append((pools, _lib.haplotype_seqs(l["blocks"])))
+        p1, p2 = phasing_priors(l["sample"], l["hp"])
+        pool_index += list(idx); p1s += list(p1); p2s += list(p2); labs += list(l["sample"])
+        lro.append(lro[-1] + len(alns))
+    plan = ctx.plan(_abi.PackedBatch(flat))
+    plan.execute()
+    out = plan.genotype([l["blocks"] for l in todo], lro, pool_index, p1s, p2s, labs, [len(SAMPLES)] * len(todo), prune=True)
+    plan.close()
+    return out
+
+
+def run(ctx, vcf_path=None, max_loci=None, tmp_dir="/tmp", ref_vcf=None, prune=False):
     """ref_vcf: a bgzipped, tabix-indexed VCF whose records give the candidate alleles (--ref-vcf: read_vcf_alleles,
-    add_vcf_haplotype_block); a locus without a record gets the status "no panel record".  No allele is pruned in
-    either mode."""
+    add_vcf_haplotype_block); a locus without a record gets the status "no panel record".
+    prune: discovery mode as the reference runs it (seq_stutter_genotyper.cpp:636-645) -- alleles no sample carries in its best
+    haplotype pair are removed once and the posteriors recomputed over the surviving haplotypes (ltr_plan_genotype), so the
+    record lists only called ALT alleles and Q is normalised over the diplotypes LongTR keeps.  With ref_vcf nothing is
+    pruned, as in the reference (:636).  Default off: every candidate allele stays in the record."""
     bed = os.path.join(tmp_dir, f"ltr_regions_{os.getpid()}.bed")
     convert_bed(os.path.join(DATA, "test_regions_hg38.bed"), bed)
     regions, _ = _lib.read_regions(bed, order=True)
@@ -122,17 +156,24 @@ def run(ctx, vcf_path=None, max_loci=None, tmp_dir="/tmp", ref_vcf=None):
     if panel is not None:
         panel.close()
     todo = [l for l in loci if l["status"] == "ok"]
-    res = ctx.calc_hap_aln_probs([(l["blocks"], l["alns"], None) for l in todo])              # one GPU pass for every locus
+    # one GPU pass for every locus: ltr_calc_hap_aln_probs, or -- pruning -- a resident plan and ltr_plan_genotype on it
+    final = plan_genotype(ctx, todo) if prune and panel is None and todo else None
+    res = ctx.calc_hap_aln_probs([(l["blocks"], l["alns"], None) for l in todo]) if final is None else [(g["read_ll"], None) for g in final]
     writer = _lib.VcfWriter(vcf_path) if vcf_path else None
     if writer:
         # Genotyper::get_vcf_header: field definitions a downstream tool can type the records with (no FASTA here: the
         # reference windows are rebuilt from the reads, so there are no ##contig lines)
         writer.header(_lib.vcf_header("(no hg38 FASTA bundled: windows rebuilt from the reads' = runs)", "examples/real_reads_trio.py", None, SAMPLES))
-    for l, (ll, seeds) in zip(todo, res):
+    for k, (l, (ll, seeds)) in enumerate(zip(todo, res)):
         R, H = ll.shape
         log_p1, log_p2 = phasing_priors(l["sample"], l["hp"])
         lab = np.asarray(l["sample"], dtype=np.int32)
-        post = ctx.posteriors(ll, log_p1, log_p2, lab, len(SAMPLES))
+        if final is None:
+            post = ctx.posteriors(ll, log_p1, log_p2, lab, len(SAMPLES))
+        else:                                                       # the pruned state: blocks, posteriors and scores of the surviving haplotypes
+            g = final[k]
+            post = dict(post=g["post"], sample_total_ll=g["sample_total_ll"], gts=g["gts"], clamped_ll=g["read_ll"])
+            l.update(candidate_blocks=l["blocks"], blocks=g["blocks"], removed=g["removed"])
         alleles = l["blocks"][1]["alleles"]
         l.update(ll=ll, seeds=seeds, gts=post["gts"], allele_lens=[len(a) for a in alleles], log_p1=log_p1,
                  gt_lens=[tuple(sorted(len(alleles[int(g)]) for g in gt)) for gt in post["gts"]])
@@ -144,7 +185,7 @@ def run(ctx, vcf_path=None, max_loci=None, tmp_dir="/tmp", ref_vcf=None):
                                           sample_label=lab, alns=l["alns"], log_sample_posteriors=post["post"], sample_total_ll=post["sample_total_ll"],
                                           best_haplotypes=post["gts"], n_p1s=l["n_p1s"], n_p2s=l["n_p2s"], sample_names=SAMPLES))
             line, pos = _lib.vcf_record(pv)
-            l["vcf_line"] = line
+            l["vcf_line"], l["vcf_locus"] = line, pv
             writer.add_record(reg["chrom"], pos, line)
     if writer:
         writer.close()
@@ -156,9 +197,10 @@ def main():
     ap = argparse.ArgumentParser(description="The chain on the bundled trio reads.")
     ap.add_argument("out", nargs="?", default=None, help="VCF to write (BGZF for *.gz)")
     ap.add_argument("--ref-vcf", default=None, metavar="PATH", help="bgzipped, tabix-indexed VCF of candidate alleles (LongTR's --ref-vcf)")
+    ap.add_argument("--prune-alleles", action="store_true", help="remove the alleles no sample is called with and genotype again (the reference's discovery mode)")
     args = ap.parse_args()
     ctx = _lib.Context(0)
-    loci = run(ctx, args.out, ref_vcf=args.ref_vcf)
+    loci = run(ctx, args.out, ref_vcf=args.ref_vcf, prune=args.prune_alleles)
     for l in loci:
         if l["status"] != "ok":
             print(f"{l['region']['name']:>16} {l['region']['chrom']}:{l['region']['start']}-{l['region']['stop']}  skipped: {l['status']}")

@@ -556,6 +556,65 @@ int32_t ltr_unused_alleles(int32_t n_samples, const int32_t* best_haplotypes, co
 int ltr_remap_haplotypes(const ltr_haplotype_blocks* old_hap, const ltr_haplotype_blocks* new_hap,
                          int32_t* allele_mapping, uint8_t* realign_to_hap);
 int ltr_remap_aln_probs(const double* old_ll, int32_t n_reads, int32_t h_old, const int32_t* allele_mapping, int32_t h_new, double* new_ll);
+/* HapBlock::remove_alleles (HapBlock.h:151-160, RepeatBlock.h:60-69) for `block` of a block list, the other blocks copied:
+ * the rebuilt list remove_alleles (:411-414, :332-335) makes from the indices ltr_unused_alleles returned.  Allele 0 is never
+ * removed (the assert of HapBlock.h:153): LTR_ERR_INVALID, as for an index outside the block.  Free with ltr_hap_result_free. */
+int ltr_prune_hap_blocks(const ltr_haplotype_blocks* old_hap, int32_t block, const int32_t* unused, int32_t n_unused, ltr_hap_result** out);
+
+/* ---- consumer, whole chain: posteriors -> prune uncalled alleles -> posteriors again, every locus of a plan (GPU) ---- */
+/*
+ * SeqStutterGenotyper::genotype after the alignment (seq_stutter_genotyper.cpp:632-645) for EVERY locus of an executed plan:
+ *   1. calc_log_sample_posteriors + get_optimal_haplotypes (:635, genotyper.cpp:21-100), as ltr_plan_posteriors, bit for bit;
+ *   2. prune != 0 (discovery mode, :636-645): get_unused_alleles(false, true) (:250-308) per locus -- aligned_read[s] from the
+ *      plan's seed positions through pool_index (:262-266); blocks with one option skipped (:274); allele 0 never removed
+ *      (:298); sample_filtered[s] != 0 <=> call_sample_[s] not empty (:289);
+ *   3. remove_alleles -> add_and_remove_alleles (:317-409) for the loci where something is unused (:641): the new block list
+ *      (HapBlock::remove_alleles), its haplotypes in Haplotype::next() order of the NEW list, matched to the old ones by
+ *      sequence like ltr_remap_haplotypes (:322-360), the surviving columns of log_aln_probs_ (:364-377; a new haplotype
+ *      without an old one reads -100000, :367);
+ *   4. calc_log_sample_posteriors over the smaller set (:405-408): priors of the new H (genotyper.cpp:21-33), bit-identical
+ *      to ltr_posteriors on the re-mapped matrix.
+ * Pruning happens ONCE, not to a fixed point (:640-645); a locus with nothing unused keeps its first posteriors (:641);
+ * prune == 0 is the --ref-vcf mode (:636): the first posteriors are final.  The posterior arithmetic and the column gather
+ * run on the device (ltr_plan_genotype.hip); the host sees the first pass's best pairs only.
+ * The plan must have been executed.  An error (LTR_ERR_INVALID + ltr_last_error) launches nothing and leaves *out NULL.
+ */
+typedef struct ltr_genotype_batch {
+  const ltr_posterior_batch*         pb;      /* reads -> pool rows, priors, sample labels, S_l, haploid: as ltr_plan_posteriors */
+  const ltr_haplotype_blocks* const* haps;    /* [n_loci] block list of each locus; its number of combinations must equal the plan's H_l.
+                                                 prune == 0: not read at all (may be NULL; ltr_genotype_result_blocks hands back what was given) */
+  const uint8_t*                     sample_filtered;   /* optional [sum_l S_l], loci then samples in order */
+  int32_t                            prune;   /* 1 = discovery mode (:636-645); 0 = first posteriors are final */
+  int32_t                            want_read_ll;      /* != 0: also gather the per-read matrices (ltr_genotype_result_read_ll) */
+} ltr_genotype_batch;
+typedef struct ltr_genotype_result ltr_genotype_result;      /* owned by the library */
+int  ltr_plan_genotype(ltr_plan* plan, const ltr_genotype_batch* gb, ltr_genotype_result** out);
+void ltr_genotype_result_free(ltr_genotype_result* r);
+/* Per locus l (NULL / a negative status for a bad index); pointers stay valid until ltr_genotype_result_free.  H = the plan's
+ * number of haplotypes of the locus, H' = after pruning, S = its samples, R = its reads.
+ *   n_haps          H'
+ *   new_to_old      [H'] column of the plan's LL matrix each final haplotype reads (-1: none, see 3.)
+ *   allele_mapping  [H]  old haplotype -> new index or -1, the array of :349-359
+ *   removed         indices of the removed alleles of `block` through *alleles (NULL when none); returns their number
+ *   num_aff_blocks, num_aff_alleles   the counters of get_unused_alleles (:253-306)
+ *   blocks          the block list the final haplotypes enumerate: the pruned copy, or -- for a locus that lost no allele --
+ *                   the caller's own gb->haps[l] (not copied: valid as long as the caller keeps it; the ONLY accessor that
+ *                   hands out or reads caller memory after the call has returned); ready for ltr_vcf_record
+ *   log_sample_posteriors [S x H' x H'], sample_total_ll [S], gts [S x 2] in the NEW indices
+ *   read_ll         [R x H'] log_aln_probs_ per READ (not per pool), clamped at -600 as genotyper.cpp:57-58 leaves it: what
+ *                   ltr_vcf_locus.log_aln_probs wants (NULL unless want_read_ll) */
+int64_t        ltr_genotype_result_n_loci(const ltr_genotype_result* r);
+int32_t        ltr_genotype_result_n_haps(const ltr_genotype_result* r, int64_t l);
+const int32_t* ltr_genotype_result_new_to_old(const ltr_genotype_result* r, int64_t l);
+const int32_t* ltr_genotype_result_allele_mapping(const ltr_genotype_result* r, int64_t l);
+int32_t        ltr_genotype_result_removed(const ltr_genotype_result* r, int64_t l, int32_t block, const int32_t** alleles);
+int32_t        ltr_genotype_result_num_aff_blocks(const ltr_genotype_result* r, int64_t l);
+int32_t        ltr_genotype_result_num_aff_alleles(const ltr_genotype_result* r, int64_t l);
+const ltr_haplotype_blocks* ltr_genotype_result_blocks(const ltr_genotype_result* r, int64_t l);
+const double*  ltr_genotype_result_log_sample_posteriors(const ltr_genotype_result* r, int64_t l);
+const double*  ltr_genotype_result_sample_total_ll(const ltr_genotype_result* r, int64_t l);
+const int32_t* ltr_genotype_result_gts(const ltr_genotype_result* r, int64_t l);
+const double*  ltr_genotype_result_read_ll(const ltr_genotype_result* r, int64_t l);
 
 /* Genotyper's output switches (genotyper.cpp:339-346; CLI --output-gls etc., hipstr_main.cpp:178-183). */
 typedef struct ltr_vcf_options {
@@ -723,7 +782,7 @@ const char* ltr_bam_aux_string(const ltr_bam_record* rec, const char tag[2]);   
  *                 haplotype construction -- ltr_build_haplotype, ltr_haplotype_align_to_ref
  *   hap_aln_s     total_hap_aln_time_ (:515,:561-562): everything inside ltr_process_reads, ltr_align_batch
  *                 and ltr_calc_hap_aln_probs (host preparation, upload, kernels, download, scatter)
- *   posterior_s   total_posterior_time_ (genotyper.cpp:46,:80-81): ltr_posteriors, ltr_plan_posteriors
+ *   posterior_s   total_posterior_time_ (genotyper.cpp:46,:80-81): ltr_posteriors, ltr_plan_posteriors, ltr_plan_genotype
  *   dp_kernel_ms  device time of the DP kernels inside hap_aln_s (HIP events around every execute)
  *   nw_kernel_ms  device time of the Needleman-Wunsch kernels inside hap_build_s (HIP events, first launch to last)
  *   short_kernel_ms  device time of the seeded stutter path's kernels inside hap_aln_s (same)

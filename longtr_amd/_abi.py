@@ -150,6 +150,30 @@ class HaplotypeBlocks(C.Structure):
     ]
 
 
+class GenotypeBatch(C.Structure):
+    """struct ltr_genotype_batch."""
+
+    _fields_ = [
+        ("pb", C.POINTER(PosteriorBatch)),
+        ("haps", C.POINTER(C.POINTER(HaplotypeBlocks))),
+        ("sample_filtered", C.POINTER(C.c_uint8)),
+        ("prune", C.c_int32),
+        ("want_read_ll", C.c_int32),
+    ]
+
+
+def blocks_from_struct(b):
+    """A struct ltr_haplotype_blocks as the list of dicts PackedHaplotype takes."""
+    blocks, k = [], 0
+    for i in range(b.n_blocks):
+        al = []
+        for _ in range(b.n_alleles[i]):
+            al.append(bytes(b.allele_bytes[b.allele_off[k]:b.allele_off[k + 1]]))
+            k += 1
+        blocks.append(dict(start=b.block_start[i], end=b.block_end[i], is_repeat=bool(b.is_repeat[i]), period=b.period[i], alleles=al))
+    return blocks
+
+
 class Alignment(C.Structure):
     """struct ltr_alignment (reference: class Alignment, AlignmentData.h:28-140)."""
 

@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("LTR_GPU_LIB") or os.path.join(CSRC, "libltr_gpu.so")   # override: A/B builds only
 KERNEL_TUS = ["ltr_k_one.hip", "ltr_k_pack.hip", "ltr_k_plan.hip", "ltr_k_wg.hip", "ltr_k_wgt.hip", "ltr_k_exact.hip", "ltr_plan.cpp"]      # one family of DP kernels each
-SOURCES = ["ltr_ctx.hip", "ltr_plan_build.hip", "ltr_plan_run.hip", "ltr_posterior.hip"] + KERNEL_TUS + ["ltr_short.hip", "ltr_nw.hip", "ltr_host.cpp", "ltr_genotype.cpp", "ltr_vcf.cpp", "ltr_prep.cpp", "ltr_io.cpp", "ltr_bam.cpp", "ltr_vcf_in.cpp"]
+SOURCES = ["ltr_ctx.hip", "ltr_plan_build.hip", "ltr_plan_run.hip", "ltr_posterior.hip", "ltr_plan_genotype.hip"] + KERNEL_TUS + ["ltr_short.hip", "ltr_nw.hip", "ltr_host.cpp", "ltr_genotype.cpp", "ltr_vcf.cpp", "ltr_prep.cpp", "ltr_io.cpp", "ltr_bam.cpp", "ltr_vcf_in.cpp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-honor-nans", "-std=c++17", "-fPIC", "-shared", "-pthread", "-Wall"]
 LINK_LIBS = ["-lz"]                                         # BGZF blocks (ltr_bgzf.h: BAM, VCF writer, tabix-indexed VCF input)
 
@@ -41,6 +41,10 @@ EXPORTS = [
     "ltr_bam_read_group_sample", "ltr_bam_read_group_library", "ltr_bam_read_group_file", "ltr_bam_set_region", "ltr_bam_next",
     "ltr_bam_aux_int", "ltr_bam_aux_float", "ltr_bam_aux_char", "ltr_bam_aux_string",
     "ltr_vcf_reader_open", "ltr_vcf_reader_close", "ltr_vcf_read_alleles", "ltr_vcf_index", "ltr_debug_vcf_query", "ltr_debug_tbi_parse",
+    "ltr_prune_hap_blocks", "ltr_plan_genotype", "ltr_genotype_result_free", "ltr_genotype_result_n_loci", "ltr_genotype_result_n_haps",
+    "ltr_genotype_result_new_to_old", "ltr_genotype_result_allele_mapping", "ltr_genotype_result_removed", "ltr_genotype_result_num_aff_blocks",
+    "ltr_genotype_result_num_aff_alleles", "ltr_genotype_result_blocks", "ltr_genotype_result_log_sample_posteriors",
+    "ltr_genotype_result_sample_total_ll", "ltr_genotype_result_gts", "ltr_genotype_result_read_ll",
 ]
 
 
@@ -769,6 +773,82 @@ class Plan:
         self.ctx._check(lib().ltr_plan_posteriors(self._h, C.byref(pb), _p(post), _p(stl), _p(gts)))
         return post[:off[-1]], off, stl[:len(sizes)], gts[:2 * len(sizes)].reshape(-1, 2)
 
+    def _posterior_batch(self, locus_read_off, pool_index, log_p1, log_p2, sample_label, n_samples, haploid):
+        keep = [np.ascontiguousarray(locus_read_off, dtype=np.int64), np.ascontiguousarray(pool_index, dtype=np.int32),
+                np.ascontiguousarray(log_p1, dtype=np.float64), np.ascontiguousarray(log_p2, dtype=np.float64),
+                np.ascontiguousarray(sample_label, dtype=np.int32), np.ascontiguousarray(n_samples, dtype=np.int32)]
+        pb = _abi.PosteriorBatch()
+        pb.n_loci = len(keep[5])
+        pb.locus_read_off = keep[0].ctypes.data_as(C.POINTER(C.c_int64))
+        pb.n_reads = len(keep[1])
+        pb.pool_index = keep[1].ctypes.data_as(C.POINTER(C.c_int32))
+        pb.log_p1 = keep[2].ctypes.data_as(C.POINTER(C.c_double))
+        pb.log_p2 = keep[3].ctypes.data_as(C.POINTER(C.c_double))
+        pb.sample_label = keep[4].ctypes.data_as(C.POINTER(C.c_int32))
+        pb.n_samples = keep[5].ctypes.data_as(C.POINTER(C.c_int32))
+        pb.haploid = int(haploid)
+        return pb, keep
+
+    def pack_genotype(self, loci_blocks, locus_read_off, pool_index, log_p1, log_p2, sample_label, n_samples, haploid=False,
+                      sample_filtered=None, prune=True, want_read_ll=True):
+        """ctypes image of an ltr_genotype_batch (for repeated genotype_packed calls).  loci_blocks: the block list of every
+        locus; the other arrays as Plan.posteriors takes them; sample_filtered: optional flat [sum S_l] (call_sample_ not empty)."""
+        pb, keep = self._posterior_batch(locus_read_off, pool_index, log_p1, log_p2, sample_label, n_samples, haploid)
+        phs = [_abi.PackedHaplotype(b) for b in loci_blocks]
+        arr = (C.POINTER(_abi.HaplotypeBlocks) * max(len(phs), 1))(*[C.pointer(p.struct) for p in phs])
+        sf = None if sample_filtered is None else np.ascontiguousarray(sample_filtered, dtype=np.uint8)
+        gb = _abi.GenotypeBatch()
+        gb.pb = C.pointer(pb)
+        gb.haps = arr
+        gb.sample_filtered = sf.ctypes.data_as(C.POINTER(C.c_uint8)) if sf is not None else None
+        gb.prune, gb.want_read_ll = int(bool(prune)), int(bool(want_read_ll))
+        return dict(gb=gb, keep=(pb, keep, phs, arr, sf), n_samples=keep[5], locus_read_off=keep[0], loci_blocks=loci_blocks)
+
+    def genotype_packed(self, packed, decode=True):
+        """ltr_plan_genotype on a pack_genotype image.  decode=False: run, free the result, return None (timing)."""
+        L = lib()
+        _bind_genotype(L)
+        h = C.c_void_p()
+        self.ctx._check(L.ltr_plan_genotype(self._h, C.byref(packed["gb"]), C.byref(h)))
+        try:
+            if not decode:
+                return None
+            out, ns, lro = [], packed["n_samples"], packed["locus_read_off"]
+            take = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dtype=dt)
+            for l in range(L.ltr_genotype_result_n_loci(h)):
+                S, R, Hn = int(ns[l]), int(lro[l + 1] - lro[l]), L.ltr_genotype_result_n_haps(h, l)
+                old = packed["loci_blocks"][l]
+                a2n = L.ltr_genotype_result_allele_mapping(h, l)
+                Ho = int(np.prod([len(b["alleles"]) for b in old], dtype=np.int64))
+                removed = []
+                for b in range(len(old)):
+                    ptr = C.POINTER(C.c_int32)()
+                    n = L.ltr_genotype_result_removed(h, l, b, C.byref(ptr))
+                    removed.append([ptr[i] for i in range(n)])
+                pruned = any(removed)
+                rll = L.ltr_genotype_result_read_ll(h, l)
+                out.append(dict(
+                    n_haps=Hn, new_to_old=take(L.ltr_genotype_result_new_to_old(h, l), Hn, np.int32), allele_mapping=take(a2n, Ho, np.int32),
+                    removed=removed, num_aff_blocks=L.ltr_genotype_result_num_aff_blocks(h, l),
+                    num_aff_alleles=L.ltr_genotype_result_num_aff_alleles(h, l),
+                    blocks=_abi.blocks_from_struct(L.ltr_genotype_result_blocks(h, l).contents) if pruned else old,
+                    post=take(L.ltr_genotype_result_log_sample_posteriors(h, l), S * Hn * Hn, np.float64).reshape(S, Hn, Hn),
+                    sample_total_ll=take(L.ltr_genotype_result_sample_total_ll(h, l), S, np.float64),
+                    gts=take(L.ltr_genotype_result_gts(h, l), 2 * S, np.int32).reshape(S, 2),
+                    read_ll=take(rll, R * Hn, np.float64).reshape(R, Hn) if rll else None))
+            return out
+        finally:
+            L.ltr_genotype_result_free(h)
+
+    def genotype(self, loci_blocks, locus_read_off, pool_index, log_p1, log_p2, sample_label, n_samples, haploid=False,
+                 sample_filtered=None, prune=True, want_read_ll=True):
+        """ltr_plan_genotype: SeqStutterGenotyper::genotype after the alignment for every locus of the executed plan --
+        posteriors, uncalled alleles pruned once (prune=True), posteriors again over the surviving haplotypes.  Returns per
+        locus a dict: n_haps, new_to_old, allele_mapping, removed (per block), num_aff_blocks / num_aff_alleles, blocks (the
+        final block list), post [S, H', H'], sample_total_ll [S], gts [S, 2] (new indices), read_ll [R, H'] or None."""
+        return self.genotype_packed(self.pack_genotype(loci_blocks, locus_read_off, pool_index, log_p1, log_p2, sample_label, n_samples,
+                                                       haploid, sample_filtered, prune, want_read_ll))
+
     def set_timing(self, on=True):
         """on: False / True (every launch as it is launched) / 2 (the multi-width one-wave launch class by class)."""
         self.ctx._check(lib().ltr_plan_set_timing(self._h, int(on)))
@@ -981,6 +1061,32 @@ def vcf_record(packed_vcf_locus, options=None):
     if n < 0:
         raise LtrError(int(n), "ltr_vcf_record")
     return buf.raw[:n].decode(), pos.value
+
+
+def _bind_genotype(L):
+    vp, i64, i32 = C.c_void_p, C.c_int64, C.c_int32
+    L.ltr_plan_genotype.argtypes = [vp, C.POINTER(_abi.GenotypeBatch), C.POINTER(vp)]
+    L.ltr_genotype_result_free.argtypes, L.ltr_genotype_result_free.restype = [vp], None
+    L.ltr_genotype_result_n_loci.argtypes, L.ltr_genotype_result_n_loci.restype = [vp], i64
+    for f, rt in (("n_haps", i32), ("num_aff_blocks", i32), ("num_aff_alleles", i32), ("new_to_old", C.POINTER(i32)),
+                  ("allele_mapping", C.POINTER(i32)), ("gts", C.POINTER(i32)), ("blocks", C.POINTER(_abi.HaplotypeBlocks)),
+                  ("log_sample_posteriors", C.POINTER(C.c_double)), ("sample_total_ll", C.POINTER(C.c_double)), ("read_ll", C.POINTER(C.c_double))):
+        fn = getattr(L, "ltr_genotype_result_" + f)
+        fn.argtypes, fn.restype = [vp, i64], rt
+    L.ltr_genotype_result_removed.argtypes, L.ltr_genotype_result_removed.restype = [vp, i64, i32, C.POINTER(C.POINTER(i32))], i32
+
+
+def prune_hap_blocks(blocks, block, unused):
+    """ltr_prune_hap_blocks (HapBlock::remove_alleles for one block of a list): the new list of block dicts."""
+    L = lib()
+    L.ltr_prune_hap_blocks.argtypes = [C.POINTER(_abi.HaplotypeBlocks), C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
+    ph = _abi.PackedHaplotype(blocks)
+    un = np.ascontiguousarray(unused, dtype=np.int32)
+    h = C.c_void_p()
+    rc = L.ltr_prune_hap_blocks(C.byref(ph.struct), int(block), _p(un) if len(un) else None, len(un), C.byref(h))
+    if rc != 0:
+        raise LtrError(rc, "ltr_prune_hap_blocks")
+    return _hap_result(h)["blocks"]
 
 
 def _hap_result(h):

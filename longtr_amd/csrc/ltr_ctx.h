@@ -74,6 +74,7 @@ struct ltr_ctx {
   struct PlanScratch {
     RawBuf<PairDesc> pairs, sorted; RawBuf<int16_t> key, bin; RawBuf<int32_t> order; RawBuf<uint8_t> read_acgt, hap_acgt;
   } scratch;
+  RawBuf<uint8_t> gt_units;             // host work array of ltr_plan_genotype (used under mu): the units of the first pass
   RawBuf<uint8_t> host_bytes[4];         // (two pairs: the chunks of ltr_calc_hap_aln_probs alternate, one is laid out while the other is uploaded)
   void* d_big = nullptr; size_t big_bytes = 0;      // ctx_big_scratch
   hipStream_t stream = nullptr;

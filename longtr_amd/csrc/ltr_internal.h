@@ -281,6 +281,24 @@ int short_batch_run(ltr_ctx* ctx, ShortBatch* b);
 // every combination, combination-major.
 int haplotype_counts(const ltr_haplotype_blocks* hap, std::vector<int32_t>* counts, int64_t* ncombs);
 
+// A block list that owns its arrays (view points into them; not copyable once filled).
+struct OwnedHapBlocks {
+  std::vector<int32_t> bstart, bend, period, nall;
+  std::vector<uint8_t> is_rep, bytes;
+  std::vector<int64_t> off;
+  ltr_haplotype_blocks view = {};
+  OwnedHapBlocks() = default;
+  OwnedHapBlocks(const OwnedHapBlocks&) = delete;
+  OwnedHapBlocks& operator=(const OwnedHapBlocks&) = delete;
+};
+// HapBlock::remove_alleles (HapBlock.h:151-160, RepeatBlock.h:60-69) for every block of a list: removed[b] = allele indices
+// of block b to drop (b beyond removed.size(): none).  Allele 0 or an index outside the block: LTR_ERR_INVALID.  (ltr_vcf.cpp)
+int prune_hap_blocks(const ltr_haplotype_blocks* old, const std::vector<std::vector<int32_t>>& removed, OwnedHapBlocks* out);
+// The haplotype matching of add_and_remove_alleles (seq_stutter_genotyper.cpp:322-360) as ltr_remap_haplotypes does it, on
+// Haplotype::next() tables computed once: allele_mapping [H old] = new index or -1; realign [H new] (may be null).  (ltr_vcf.cpp)
+int remap_haplotypes(const ltr_haplotype_blocks* old_hap, const ltr_haplotype_blocks* new_hap, std::vector<int32_t>* allele_mapping,
+                     std::vector<uint8_t>* realign);
+
 }  // namespace ltr
 
 #endif

@@ -452,6 +452,26 @@ int ltr_build_vcf_haplotype(ltr_ctx* ctx, const ltr_read_set* rs, int32_t pos, c
   } catch (const std::bad_alloc&) { return LTR_ERR_NOMEM; } catch (...) { return LTR_ERR_INVALID; }
 }
 
+// HapBlock::remove_alleles (HapBlock.h:151-160, RepeatBlock.h:60-69) for one block of a list: what remove_alleles
+// (seq_stutter_genotyper.cpp:411-414, :332-335) does with the indices ltr_unused_alleles returned.
+int ltr_prune_hap_blocks(const ltr_haplotype_blocks* old_hap, int32_t block, const int32_t* unused, int32_t n_unused, ltr_hap_result** out) {
+  if (!old_hap || !out || block < 0 || block >= old_hap->n_blocks || n_unused < 0 || (n_unused > 0 && !unused)) return LTR_ERR_INVALID;
+  *out = nullptr;
+  try {
+    std::vector<std::vector<int32_t>> removed((size_t)old_hap->n_blocks);
+    removed[(size_t)block].assign(unused, unused + n_unused);
+    ltr::OwnedHapBlocks pruned;
+    const int rc = ltr::prune_hap_blocks(old_hap, removed, &pruned);
+    if (rc != LTR_OK) return rc;
+    std::unique_ptr<ltr_hap_result> res(new ltr_hap_result());
+    res->bstart.swap(pruned.bstart); res->bend.swap(pruned.bend); res->period.swap(pruned.period); res->nall.swap(pruned.nall);
+    res->is_rep.swap(pruned.is_rep); res->bytes.swap(pruned.bytes); res->off.swap(pruned.off);
+    res->view = pruned.view;                                   // (the swapped vectors keep their storage: the pointers stay good)
+    *out = res.release();
+    return LTR_OK;
+  } catch (const std::bad_alloc&) { return LTR_ERR_NOMEM; } catch (...) { return LTR_ERR_INVALID; }
+}
+
 const ltr_haplotype_blocks* ltr_hap_result_blocks(const ltr_hap_result* r) { return (r && r->failure.empty()) ? &r->view : nullptr; }
 const char* ltr_hap_result_failure(const ltr_hap_result* r) { return r ? r->failure.c_str() : "null"; }
 int32_t ltr_hap_result_unplaced_reads(const ltr_hap_result* r) { return r ? r->unplaced : 0; }

@@ -179,6 +179,80 @@ void reorder(const std::vector<std::string>& alleles, std::vector<int>* old_to_n
 
 }  // namespace
 
+namespace ltr {
+
+// HapBlock::remove_alleles (HapBlock.h:151-160; RepeatBlock.h:60-69 keeps period and coordinates the same way) for a block list
+int prune_hap_blocks(const ltr_haplotype_blocks* old, const std::vector<std::vector<int32_t>>& removed, OwnedHapBlocks* out) {
+  if (!old || !out || old->n_blocks <= 0) return LTR_ERR_INVALID;
+  const int nb = old->n_blocks;
+  out->bstart.assign(old->block_start, old->block_start + nb);
+  out->bend.assign(old->block_end, old->block_end + nb);
+  out->period.assign(old->period, old->period + nb);
+  out->is_rep.assign(old->is_repeat, old->is_repeat + nb);
+  out->nall.assign((size_t)nb, 0);
+  out->bytes.clear();
+  out->off.assign(1, 0);
+  int64_t k = 0;
+  for (int b = 0; b < nb; ++b) {
+    const int n = old->n_alleles[b];
+    if (n <= 0) return LTR_ERR_INVALID;
+    std::vector<uint8_t> bad((size_t)n, 0);
+    if ((size_t)b < removed.size())
+      for (int32_t a : removed[(size_t)b]) {
+        if (a <= 0 || a >= n) return LTR_ERR_INVALID;          // assert(bad_alleles.find(0) == end), HapBlock.h:153
+        bad[(size_t)a] = 1;
+      }
+    for (int a = 0; a < n; ++a, ++k) {
+      if (bad[(size_t)a]) continue;
+      out->bytes.insert(out->bytes.end(), old->allele_bytes + old->allele_off[k], old->allele_bytes + old->allele_off[k + 1]);
+      out->off.push_back((int64_t)out->bytes.size());
+      out->nall[(size_t)b]++;
+    }
+  }
+  if (out->bytes.empty()) out->bytes.push_back(0);              // (allele_bytes stays a valid pointer)
+  out->view.n_blocks = nb;
+  out->view.block_start = out->bstart.data(); out->view.block_end = out->bend.data();
+  out->view.is_repeat = out->is_rep.data(); out->view.period = out->period.data();
+  out->view.n_alleles = out->nall.data(); out->view.allele_bytes = out->bytes.data(); out->view.allele_off = out->off.data();
+  return LTR_OK;
+}
+
+// every haplotype string of a block list in Haplotype::next() order
+static int all_hap_strings(const ltr_haplotype_blocks* hap, std::vector<std::string>* out) {
+  std::vector<int32_t> counts; int64_t H = 0;
+  const int rc = haplotype_counts(hap, &counts, &H);
+  if (rc != LTR_OK) return rc;
+  std::vector<int64_t> first((size_t)hap->n_blocks, 0);
+  for (int b = 1; b < hap->n_blocks; ++b) first[(size_t)b] = first[(size_t)b - 1] + hap->n_alleles[b - 1];
+  out->assign((size_t)H, std::string());
+  for (int64_t h = 0; h < H; ++h)
+    for (int b = 0; b < hap->n_blocks; ++b) {                   // Haplotype::get_seq(), Haplotype.h:99-104
+      const int64_t a = first[(size_t)b] + counts[(size_t)(h * hap->n_blocks + b)];
+      (*out)[(size_t)h].append(reinterpret_cast<const char*>(hap->allele_bytes) + hap->allele_off[a], (size_t)(hap->allele_off[a + 1] - hap->allele_off[a]));
+    }
+  return LTR_OK;
+}
+
+int remap_haplotypes(const ltr_haplotype_blocks* old_hap, const ltr_haplotype_blocks* new_hap, std::vector<int32_t>* allele_mapping,
+                     std::vector<uint8_t>* realign) {
+  std::vector<std::string> so, sn;
+  int rc = all_hap_strings(old_hap, &so);
+  if (rc == LTR_OK) rc = all_hap_strings(new_hap, &sn);
+  if (rc != LTR_OK) return rc;
+  std::map<std::string, int32_t> index;                        // (a repeated sequence keeps its LAST index, :328)
+  for (size_t k = 0; k < so.size(); ++k) index[so[k]] = (int32_t)k;
+  allele_mapping->assign(so.size(), -1);
+  if (realign) realign->assign(sn.size(), 0);
+  for (size_t k = 0; k < sn.size(); ++k) {                     // :351-360
+    auto it = index.find(sn[k]);
+    if (it == index.end()) { if (realign) (*realign)[k] = 1; }
+    else (*allele_mapping)[(size_t)it->second] = (int32_t)k;
+  }
+  return LTR_OK;
+}
+
+}  // namespace ltr
+
 extern "C" {
 
 void ltr_default_vcf_options(ltr_vcf_options* o) {
