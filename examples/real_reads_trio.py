@@ -79,9 +79,11 @@ def phasing_priors(sample, hp):
     return p1, p2
 
 
-def plan_genotype(ctx, todo):
+def plan_genotype(ctx, todo, device_fields=False):
     """Every locus in ONE resident plan (pools trimmed like HapAligner::process_reads) and one ltr_plan_genotype call: per locus
-    the dict of Plan.genotype (final blocks, posteriors, best pairs, per-read scores in the final columns)."""
+    the dict of Plan.genotype (final blocks, posteriors, best pairs, per-read scores in the final columns).
+    device_fields: ltr_plan_genotype_fields instead -- the GenotypeResult itself (the caller closes it); neither the posterior
+    blocks nor the per-read scores leave the device."""
     flat, lro, pool_index, p1s, p2s, labs = [], [0], [], [], [], []
     for l in todo:
         alns, rb = l["alns"], l["blocks"][1]
@@ -102,18 +104,24 @@ def plan_genotype(ctx, todo):
         lro.append(lro[-1] + len(alns))
     plan = ctx.plan(_abi.PackedBatch(flat))
     plan.execute()
+    if device_fields:
+        out = plan.genotype_fields([l["blocks"] for l in todo], lro, pool_index, p1s, p2s, labs, [len(SAMPLES)] * len(todo), prune=True)
+        plan.close()
+        return out
     out = plan.genotype([l["blocks"] for l in todo], lro, pool_index, p1s, p2s, labs, [len(SAMPLES)] * len(todo), prune=True)
     plan.close()
     return out
 
 
-def run(ctx, vcf_path=None, max_loci=None, tmp_dir="/tmp", ref_vcf=None, prune=False):
+def run(ctx, vcf_path=None, max_loci=None, tmp_dir="/tmp", ref_vcf=None, prune=False, device_fields=False):
     """ref_vcf: a bgzipped, tabix-indexed VCF whose records give the candidate alleles (--ref-vcf: read_vcf_alleles,
     add_vcf_haplotype_block); a locus without a record gets the status "no panel record".
     prune: discovery mode as the reference runs it (seq_stutter_genotyper.cpp:636-645) -- alleles no sample carries in its best
     haplotype pair are removed once and the posteriors recomputed over the surviving haplotypes (ltr_plan_genotype), so the
     record lists only called ALT alleles and Q is normalised over the diplotypes LongTR keeps.  With ref_vcf nothing is
-    pruned, as in the reference (:636).  Default off: every candidate allele stays in the record."""
+    pruned, as in the reference (:636).  Default off: every candidate allele stays in the record.
+    device_fields (with prune): the numbers of every record (GT, Q, PQ, GLDIFF, DP, DSNP, PSNP, MALLREADS) are computed on the
+    device by ltr_plan_genotype_fields and all records formatted by one ltr_genotype_result_vcf_records call."""
     bed = os.path.join(tmp_dir, f"ltr_regions_{os.getpid()}.bed")
     convert_bed(os.path.join(DATA, "test_regions_hg38.bed"), bed)
     regions, _ = _lib.read_regions(bed, order=True)
@@ -157,6 +165,10 @@ def run(ctx, vcf_path=None, max_loci=None, tmp_dir="/tmp", ref_vcf=None, prune=F
         panel.close()
     todo = [l for l in loci if l["status"] == "ok"]
     # one GPU pass for every locus: ltr_calc_hap_aln_probs, or -- pruning -- a resident plan and ltr_plan_genotype on it
+    if device_fields and (not prune or panel is not None):
+        raise ValueError("device_fields needs prune=True and no ref_vcf: it is the plan path (ltr_plan_genotype_fields)")
+    if device_fields and todo:
+        return _run_device_fields(ctx, loci, todo, vcf_path)
     final = plan_genotype(ctx, todo) if prune and panel is None and todo else None
     res = ctx.calc_hap_aln_probs([(l["blocks"], l["alns"], None) for l in todo]) if final is None else [(g["read_ll"], None) for g in final]
     writer = _lib.VcfWriter(vcf_path) if vcf_path else None
@@ -192,15 +204,48 @@ def run(ctx, vcf_path=None, max_loci=None, tmp_dir="/tmp", ref_vcf=None, prune=F
     return loci
 
 
+def _run_device_fields(ctx, loci, todo, vcf_path):
+    """The pruned run with the fields of every record from the device and one formatting call for all records."""
+    none = np.zeros(0)
+    with plan_genotype(ctx, todo, device_fields=True) as result:
+        pvs = []
+        for k, l in enumerate(todo):
+            g = result.locus(k)
+            l.update(candidate_blocks=l["blocks"], blocks=g["blocks"], removed=g["removed"])
+            alleles = l["blocks"][1]["alleles"]
+            log_p1, log_p2 = phasing_priors(l["sample"], l["hp"])
+            l.update(ll=None, seeds=None, gts=g["gts"], allele_lens=[len(a) for a in alleles], log_p1=log_p1,
+                     gt_lens=[tuple(sorted(len(alleles[int(x)]) for x in gt)) for gt in g["gts"]])
+            reg = l["region"]
+            pvs.append(_abi.PackedVcfLocus(dict(
+                chrom=reg["chrom"], region_start=reg["start"], region_stop=reg["stop"], name=reg["name"], motif=reg["motif"],
+                period_str=reg["period_str"], chrom_seq=l["ref"], chrom_seq_start=l["ref_start"], blocks=l["blocks"], block=1,
+                inexact_allele=np.zeros(len(alleles), dtype=np.uint8), log_aln_probs=none, log_p1=log_p1, log_p2=log_p2,
+                sample_label=np.asarray(l["sample"], dtype=np.int32), alns=l["alns"], log_sample_posteriors=none, sample_total_ll=none,
+                best_haplotypes=np.zeros(0, dtype=np.int32), n_p1s=l["n_p1s"], n_p2s=l["n_p2s"], sample_names=SAMPLES)))
+        lines, pos = result.vcf_records(pvs)
+    writer = _lib.VcfWriter(vcf_path) if vcf_path else None
+    if writer:
+        writer.header(_lib.vcf_header("(no hg38 FASTA bundled: windows rebuilt from the reads' = runs)", "examples/real_reads_trio.py", None, SAMPLES))
+    for l, pv, line, p in zip(todo, pvs, lines, pos):
+        l["vcf_line"], l["vcf_locus"] = line, pv
+        if writer:
+            writer.add_record(l["region"]["chrom"], int(p), line)
+    if writer:
+        writer.close()
+    return loci
+
+
 def main():
     import argparse
     ap = argparse.ArgumentParser(description="The chain on the bundled trio reads.")
     ap.add_argument("out", nargs="?", default=None, help="VCF to write (BGZF for *.gz)")
     ap.add_argument("--ref-vcf", default=None, metavar="PATH", help="bgzipped, tabix-indexed VCF of candidate alleles (LongTR's --ref-vcf)")
     ap.add_argument("--prune-alleles", action="store_true", help="remove the alleles no sample is called with and genotype again (the reference's discovery mode)")
+    ap.add_argument("--device-fields", action="store_true", help="needs --prune-alleles, not with --ref-vcf: the records' numbers from the device, all records formatted in one call")
     args = ap.parse_args()
     ctx = _lib.Context(0)
-    loci = run(ctx, args.out, ref_vcf=args.ref_vcf, prune=args.prune_alleles)
+    loci = run(ctx, args.out, ref_vcf=args.ref_vcf, prune=args.prune_alleles, device_fields=args.device_fields)
     for l in loci:
         if l["status"] != "ok":
             print(f"{l['region']['name']:>16} {l['region']['chrom']}:{l['region']['start']}-{l['region']['stop']}  skipped: {l['status']}")

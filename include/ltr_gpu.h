@@ -616,6 +616,39 @@ const double*  ltr_genotype_result_sample_total_ll(const ltr_genotype_result* r,
 const int32_t* ltr_genotype_result_gts(const ltr_genotype_result* r, int64_t l);
 const double*  ltr_genotype_result_read_ll(const ltr_genotype_result* r, int64_t l);
 
+/*
+ * The numbers SeqStutterGenotyper::write_vcf_record (:894-1366) derives from the posteriors and the per-read matrix before it
+ * prints, for one repeat block of one locus: views, owned by whoever handed them out.  S samples, R reads, V alleles of the block.
+ *   best_gts .. phased_gls   Genotyper::extract_genotypes_and_likelihoods (genotyper.cpp:132-256), as ltr_genotype_fields;
+ *                            gl_diffs = calc_gl_diff (:109-130), pls = calc_PLs (:102-107); n_gl = haploid ? V : V(V+1)/2,
+ *                            n_pgl = haploid ? V : V*V; gls / pls / phased_gls NULL unless asked for
+ *   n_aligned, n_snp, n_s1, n_s2   reads of the sample, those with |log_p1 - log_p2| > 1e-10, and their sides (:1006-1012)
+ *   read_allele              [R] allele of the block in the read's more likely strand haplotype (:965-967, :1038-1040)
+ */
+typedef struct ltr_locus_fields {
+  int32_t S, R, V, block, n_gl, n_pgl;
+  const int32_t* best_gts;          /* [S x 2] */
+  const double  *log_phased, *log_unphased, *hap_log_phased, *hap_log_unphased, *gl_diffs;   /* [S] */
+  const double  *gls; const int32_t* pls; const double* phased_gls;                          /* NULL unless asked */
+  const int32_t *n_aligned, *n_snp, *n_s1, *n_s2;                                            /* [S] */
+  const int32_t* read_allele;       /* [R] */
+} ltr_locus_fields;
+
+/* ltr_plan_genotype and, on the blocks where they lie on the device, the fields of every locus (ltr_plan_fields.hip):
+ * the same passes and the same bits in every accessor above, then one kernel, one (locus, sample) per workgroup.
+ * gb->haps is required (hap_to_allele of the FINAL block list, :240-248, is taken from it on the host).
+ * The context of the plan must outlive the result.
+ * A sample for which the passes found no optimal haplotype pair (gts = -1: NaN scores) has best_gts = -1 and 0 in every other
+ * number of its own; ltr_genotype_result_vcf_records refuses such a locus (LTR_ERR_INVALID, the locus named). */
+typedef struct ltr_fields_request {
+  const int32_t* block;        /* [n_loci] block each record is for; NULL = the first is_repeat block of the final list */
+  int32_t want_gls, want_pls, want_phased_gls;
+  int32_t want_posteriors;     /* 0: the S x H' x H' blocks are NOT downloaded (ltr_genotype_result_log_sample_posteriors returns NULL) */
+} ltr_fields_request;
+int ltr_plan_genotype_fields(ltr_plan* plan, const ltr_genotype_batch* gb, const ltr_fields_request* fr, ltr_genotype_result** out);
+/* views into the result (LTR_ERR_INVALID for a result of ltr_plan_genotype, which has none) */
+int ltr_genotype_result_fields(const ltr_genotype_result* r, int64_t l, ltr_locus_fields* out);
+
 /* Genotyper's output switches (genotyper.cpp:339-346; CLI --output-gls etc., hipstr_main.cpp:178-183). */
 typedef struct ltr_vcf_options {
   int32_t output_gls, output_pls, output_phased_gls, output_allreads, output_mallreads, output_filters, output_haplotype_data;
@@ -656,6 +689,28 @@ int32_t ltr_get_alleles(const ltr_vcf_locus* v, int32_t* pos, char* out, int64_t
 /* write_vcf_record for the long-read path (no alignment traces: DFLANKINDEL = 0): the VCF line without the
  * trailing newline, NUL-terminated.  Returns its length or a negative status. */
 int64_t ltr_vcf_record(const ltr_vcf_locus* v, const ltr_vcf_options* opt, char* out, int64_t cap, int32_t* pos);
+/* The two halves of ltr_vcf_record, which is their composition.
+ * ltr_vcf_fields: the arithmetic (:916-927 = extract_genotypes_and_likelihoods, :929-1043 the per-read bookkeeping) on the
+ * host; want_* as the output switches (gls are always computed: GLDIFF needs them).  The set owns the arrays
+ * ltr_vcf_field_set_view points into.
+ * ltr_vcf_record_from_fields: the text (:894-913 alleles, :1045-1366 counts, INFO, FORMAT, one column per sample; ALLREADS
+ * through ExtractCigar, extract_indels.cpp:18-91).  Of v it does not read log_aln_probs, log_p1, log_p2, log_sample_posteriors,
+ * sample_total_ll, best_haplotypes (they may be NULL).  LTR_ERR_INVALID, nothing written, when f is NULL, its S / R / V are
+ * not the locus', an allele index is not below V, or an array a switch of *opt needs is NULL. */
+typedef struct ltr_vcf_field_set ltr_vcf_field_set;
+int  ltr_vcf_fields(const ltr_vcf_locus* v, int32_t want_gls, int32_t want_pls, int32_t want_phased_gls, ltr_vcf_field_set** out);
+const ltr_locus_fields* ltr_vcf_field_set_view(const ltr_vcf_field_set* f);
+void ltr_vcf_field_set_free(ltr_vcf_field_set* f);
+int64_t ltr_vcf_record_from_fields(const ltr_vcf_locus* v, const ltr_locus_fields* f, const ltr_vcf_options* opt, char* out, int64_t cap, int32_t* pos);
+/* Every locus' record of a ltr_plan_genotype_fields result through ltr_vcf_record_from_fields, on the library's worker pool
+ * under the host-thread budget (ltr_ctx_set_host_threads); the text does not depend on the number of threads.
+ * loci [n_loci]: hap and block of each are ignored (ltr_genotype_result_blocks and the block the fields were made for are used).
+ * *text: the records back to back in locus order, each followed by '\n', NUL-terminated, to be released with
+ * ltr_vcf_text_free; record l is [rec_off[l], rec_off[l + 1] - 1) (rec_off [n_loci + 1]); pos [n_loci] optional.
+ * On an error (LTR_ERR_INVALID, ltr_last_error names the locus) *text stays NULL and rec_off / pos are not written. */
+int  ltr_genotype_result_vcf_records(const ltr_genotype_result* r, const ltr_vcf_locus* loci, const ltr_vcf_options* opt,
+                                     char** text, int64_t* rec_off, int32_t* pos);
+void ltr_vcf_text_free(char* text);
 /* Genotyper::get_vcf_header (genotyper.cpp:258-336): ##fileformat, ##command, ##reference, the FASTA's ##contig lines
  * (contig_lines = the text ltr_fasta_contig_lines gives, or NULL), the ##INFO / ##FORMAT definitions of every field
  * ltr_vcf_record writes (the optional ones by *opt, NULL = defaults), the #CHROM line with the sample names.

@@ -162,6 +162,62 @@ class GenotypeBatch(C.Structure):
     ]
 
 
+class FieldsRequest(C.Structure):
+    """struct ltr_fields_request."""
+
+    _fields_ = [("block", C.POINTER(C.c_int32)), ("want_gls", C.c_int32), ("want_pls", C.c_int32), ("want_phased_gls", C.c_int32),
+                ("want_posteriors", C.c_int32)]
+
+
+class LocusFields(C.Structure):
+    """struct ltr_locus_fields."""
+
+    _I32, _F64 = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+    _fields_ = [("S", C.c_int32), ("R", C.c_int32), ("V", C.c_int32), ("block", C.c_int32), ("n_gl", C.c_int32), ("n_pgl", C.c_int32),
+                ("best_gts", _I32), ("log_phased", _F64), ("log_unphased", _F64), ("hap_log_phased", _F64), ("hap_log_unphased", _F64),
+                ("gl_diffs", _F64), ("gls", _F64), ("pls", _I32), ("phased_gls", _F64),
+                ("n_aligned", _I32), ("n_snp", _I32), ("n_s1", _I32), ("n_s2", _I32), ("read_allele", _I32)]
+
+    _SHAPES = dict(best_gts=lambda f: (f.S, 2), log_phased=lambda f: (f.S,), log_unphased=lambda f: (f.S,), hap_log_phased=lambda f: (f.S,),
+                   hap_log_unphased=lambda f: (f.S,), gl_diffs=lambda f: (f.S,), gls=lambda f: (f.S, f.n_gl), pls=lambda f: (f.S, f.n_gl),
+                   phased_gls=lambda f: (f.S, f.n_pgl), n_aligned=lambda f: (f.S,), n_snp=lambda f: (f.S,), n_s1=lambda f: (f.S,),
+                   n_s2=lambda f: (f.S,), read_allele=lambda f: (f.R,))
+
+    def to_dict(self):
+        """Copies: dict(S, R, V, block, n_gl, n_pgl, <array name>: numpy array or None)."""
+        import numpy as np
+        d = dict(S=self.S, R=self.R, V=self.V, block=self.block, n_gl=self.n_gl, n_pgl=self.n_pgl)
+        for name, shape in self._SHAPES.items():
+            ptr, sh = getattr(self, name), shape(self)
+            dt = np.int32 if name in ("best_gts", "pls", "n_aligned", "n_snp", "n_s1", "n_s2", "read_allele") else np.float64
+            if not ptr:
+                d[name] = None
+            elif int(np.prod(sh)) == 0:
+                d[name] = np.zeros(sh, dtype=dt)
+            else:
+                d[name] = np.ctypeslib.as_array(ptr, shape=(int(np.prod(sh)),)).astype(dt, copy=True).reshape(sh)
+        return d
+
+    @classmethod
+    def from_dict(cls, d):
+        """(struct, the arrays it points into) from a to_dict() image (None = NULL)."""
+        import numpy as np
+        f, keep = cls(), []
+        for k in ("S", "R", "V", "block", "n_gl", "n_pgl"):
+            setattr(f, k, int(d[k]))
+        for name in cls._SHAPES:
+            a = d.get(name)
+            if a is None:
+                continue
+            dt = np.int32 if name in ("best_gts", "pls", "n_aligned", "n_snp", "n_s1", "n_s2", "read_allele") else np.float64
+            a = np.ascontiguousarray(a, dtype=dt)
+            if a.size == 0:
+                a = np.zeros(1, dtype=dt)                        # (a valid pointer for an empty array)
+            keep.append(a)
+            setattr(f, name, a.ctypes.data_as(cls._I32 if dt == np.int32 else cls._F64))
+        return f, keep
+
+
 def blocks_from_struct(b):
     """A struct ltr_haplotype_blocks as the list of dicts PackedHaplotype takes."""
     blocks, k = [], 0

@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("LTR_GPU_LIB") or os.path.join(CSRC, "libltr_gpu.so")   # override: A/B builds only
 KERNEL_TUS = ["ltr_k_one.hip", "ltr_k_pack.hip", "ltr_k_plan.hip", "ltr_k_wg.hip", "ltr_k_wgt.hip", "ltr_k_exact.hip", "ltr_plan.cpp"]      # one family of DP kernels each
-SOURCES = ["ltr_ctx.hip", "ltr_plan_build.hip", "ltr_plan_run.hip", "ltr_posterior.hip", "ltr_plan_genotype.hip"] + KERNEL_TUS + ["ltr_short.hip", "ltr_nw.hip", "ltr_host.cpp", "ltr_genotype.cpp", "ltr_vcf.cpp", "ltr_prep.cpp", "ltr_io.cpp", "ltr_bam.cpp", "ltr_vcf_in.cpp"]
+SOURCES = ["ltr_ctx.hip", "ltr_plan_build.hip", "ltr_plan_run.hip", "ltr_posterior.hip", "ltr_plan_genotype.hip", "ltr_plan_fields.hip"] + KERNEL_TUS + ["ltr_short.hip", "ltr_nw.hip", "ltr_host.cpp", "ltr_genotype.cpp", "ltr_vcf.cpp", "ltr_prep.cpp", "ltr_io.cpp", "ltr_bam.cpp", "ltr_vcf_in.cpp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-honor-nans", "-std=c++17", "-fPIC", "-shared", "-pthread", "-Wall"]
 LINK_LIBS = ["-lz"]                                         # BGZF blocks (ltr_bgzf.h: BAM, VCF writer, tabix-indexed VCF input)
 
@@ -45,6 +45,8 @@ EXPORTS = [
     "ltr_genotype_result_new_to_old", "ltr_genotype_result_allele_mapping", "ltr_genotype_result_removed", "ltr_genotype_result_num_aff_blocks",
     "ltr_genotype_result_num_aff_alleles", "ltr_genotype_result_blocks", "ltr_genotype_result_log_sample_posteriors",
     "ltr_genotype_result_sample_total_ll", "ltr_genotype_result_gts", "ltr_genotype_result_read_ll",
+    "ltr_plan_genotype_fields", "ltr_genotype_result_fields", "ltr_genotype_result_vcf_records", "ltr_vcf_text_free",
+    "ltr_vcf_fields", "ltr_vcf_field_set_view", "ltr_vcf_field_set_free", "ltr_vcf_record_from_fields",
 ]
 
 
@@ -849,6 +851,30 @@ class Plan:
         return self.genotype_packed(self.pack_genotype(loci_blocks, locus_read_off, pool_index, log_p1, log_p2, sample_label, n_samples,
                                                        haploid, sample_filtered, prune, want_read_ll))
 
+    def genotype_fields(self, loci_blocks=None, locus_read_off=None, pool_index=None, log_p1=None, log_p2=None, sample_label=None,
+                        n_samples=None, haploid=False, sample_filtered=None, prune=True, want_read_ll=False, block=None,
+                        want_gls=False, want_pls=False, want_phased_gls=False, want_posteriors=False, packed=None):
+        """ltr_plan_genotype_fields: ltr_plan_genotype and the VCF fields of every locus computed on the device (GT, Q, PQ,
+        GLDIFF, DP, DSNP, PSNP, MALLREADS' alleles; GL / PL / PHASEDGL on request).  block: per locus, None = the first repeat
+        block.  Posterior blocks / per-read matrices are downloaded only when asked for.  packed: a pack_genotype image (its
+        want_read_ll holds).  Returns a GenotypeResult (close() it, or use it as a context manager)."""
+        if packed is None:
+            packed = self.pack_genotype(loci_blocks, locus_read_off, pool_index, log_p1, log_p2, sample_label, n_samples, haploid,
+                                        sample_filtered, prune, want_read_ll)
+        L = lib()
+        _bind_genotype(L)
+        fr = _abi.FieldsRequest()
+        blk = None if block is None else np.ascontiguousarray(block, dtype=np.int32)
+        if blk is not None:
+            if len(blk) != len(packed["n_samples"]):
+                raise LtrError(-1, "genotype_fields: one block index per locus")
+            fr.block = blk.ctypes.data_as(C.POINTER(C.c_int32))
+        fr.want_gls, fr.want_pls, fr.want_phased_gls = int(bool(want_gls)), int(bool(want_pls)), int(bool(want_phased_gls))
+        fr.want_posteriors = int(bool(want_posteriors))
+        h = C.c_void_p()
+        self.ctx._check(L.ltr_plan_genotype_fields(self._h, C.byref(packed["gb"]), C.byref(fr), C.byref(h)))
+        return GenotypeResult(self.ctx, h, packed)
+
     def set_timing(self, on=True):
         """on: False / True (every launch as it is launched) / 2 (the multi-width one-wave launch class by class)."""
         self.ctx._check(lib().ltr_plan_set_timing(self._h, int(on)))
@@ -1063,6 +1089,115 @@ def vcf_record(packed_vcf_locus, options=None):
     return buf.raw[:n].decode(), pos.value
 
 
+def vcf_fields(packed_vcf_locus, want=("gls", "pls", "phased_gls")):
+    """ltr_vcf_fields: the arithmetic half of ltr_vcf_record on the host -- the LocusFields.to_dict() image."""
+    L = lib()
+    _bind_genotype(L)
+    h = C.c_void_p()
+    rc = L.ltr_vcf_fields(C.byref(packed_vcf_locus.struct), int("gls" in want), int("pls" in want), int("phased_gls" in want), C.byref(h))
+    if rc != 0:
+        raise LtrError(rc, "ltr_vcf_fields")
+    try:
+        return L.ltr_vcf_field_set_view(h).contents.to_dict()
+    finally:
+        L.ltr_vcf_field_set_free(h)
+
+
+def vcf_record_from_fields(packed_vcf_locus, fields, options=None):
+    """ltr_vcf_record_from_fields: (VCF line, 1-based position) from a fields image (vcf_fields / GenotypeResult.fields)."""
+    L = lib()
+    _bind_genotype(L)
+    if fields is None:
+        f, keep, ref = None, None, None
+    else:
+        f, keep = _abi.LocusFields.from_dict(fields)
+        ref = C.byref(f)
+    buf = C.create_string_buffer(1 << 22)
+    pos = C.c_int32(0)
+    n = L.ltr_vcf_record_from_fields(C.byref(packed_vcf_locus.struct), ref, None if options is None else C.byref(options), buf, len(buf), C.byref(pos))
+    if n < 0:
+        raise LtrError(int(n), "ltr_vcf_record_from_fields")
+    return buf.raw[:n].decode(), pos.value
+
+
+class GenotypeResult:
+    """A ltr_genotype_result of Plan.genotype_fields, kept on the library's side until close()."""
+
+    def __init__(self, ctx, handle, packed):
+        self.ctx, self._h, self._packed = ctx, handle, packed
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        if self._h:
+            lib().ltr_genotype_result_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:                                                     # (interpreter shutdown, or an __init__ that did not finish)
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def n_loci(self):
+        return int(lib().ltr_genotype_result_n_loci(self._h))
+
+    def fields(self, l):
+        """The LocusFields.to_dict() image of locus l (copies)."""
+        f = _abi.LocusFields()
+        rc = lib().ltr_genotype_result_fields(self._h, int(l), C.byref(f))
+        if rc != 0:
+            raise LtrError(rc, "ltr_genotype_result_fields")
+        return f.to_dict()
+
+    def locus(self, l):
+        """What Plan.genotype returns for locus l: post / read_ll are None when they were not asked for."""
+        L, h, packed = lib(), self._h, self._packed
+        take = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dtype=dt)
+        ns, lro = packed["n_samples"], packed["locus_read_off"]
+        S, R, Hn = int(ns[l]), int(lro[l + 1] - lro[l]), L.ltr_genotype_result_n_haps(h, l)
+        old = packed["loci_blocks"][l]
+        Ho = int(np.prod([len(b["alleles"]) for b in old], dtype=np.int64))
+        removed = []
+        for b in range(len(old)):
+            ptr = C.POINTER(C.c_int32)()
+            n = L.ltr_genotype_result_removed(h, l, b, C.byref(ptr))
+            removed.append([ptr[i] for i in range(n)])
+        post, rll = L.ltr_genotype_result_log_sample_posteriors(h, l), L.ltr_genotype_result_read_ll(h, l)
+        return dict(
+            n_haps=Hn, new_to_old=take(L.ltr_genotype_result_new_to_old(h, l), Hn, np.int32),
+            allele_mapping=take(L.ltr_genotype_result_allele_mapping(h, l), Ho, np.int32), removed=removed,
+            num_aff_blocks=L.ltr_genotype_result_num_aff_blocks(h, l), num_aff_alleles=L.ltr_genotype_result_num_aff_alleles(h, l),
+            blocks=_abi.blocks_from_struct(L.ltr_genotype_result_blocks(h, l).contents) if any(removed) else old,
+            post=take(post, S * Hn * Hn, np.float64).reshape(S, Hn, Hn) if post else None,
+            sample_total_ll=take(L.ltr_genotype_result_sample_total_ll(h, l), S, np.float64),
+            gts=take(L.ltr_genotype_result_gts(h, l), 2 * S, np.int32).reshape(S, 2),
+            read_ll=take(rll, R * Hn, np.float64).reshape(R, Hn) if rll else None)
+
+    def vcf_records(self, packed_vcf_loci, options=None):
+        """ltr_genotype_result_vcf_records: (list of VCF lines, positions) for every locus, formatted on the worker pool.
+        packed_vcf_loci: one _abi.PackedVcfLocus per locus (its blocks / block are replaced by the result's own)."""
+        L = lib()
+        n = self.n_loci
+        if len(packed_vcf_loci) != n:
+            raise LtrError(-1, "vcf_records: one locus description per locus")
+        arr = (_abi.VcfLocus * max(n, 1))(*[p.struct for p in packed_vcf_loci])
+        text = C.c_void_p()
+        off = np.zeros(n + 1, dtype=np.int64)
+        pos = np.zeros(max(n, 1), dtype=np.int32)
+        self.ctx._check(L.ltr_genotype_result_vcf_records(self._h, arr, None if options is None else C.byref(options), C.byref(text), _p(off), _p(pos)))
+        try:
+            raw = C.string_at(text, int(off[n]))
+        finally:
+            L.ltr_vcf_text_free(text)
+        return [raw[off[l]:off[l + 1] - 1].decode() for l in range(n)], pos[:n].copy()
+
+
 def _bind_genotype(L):
     vp, i64, i32 = C.c_void_p, C.c_int64, C.c_int32
     L.ltr_plan_genotype.argtypes = [vp, C.POINTER(_abi.GenotypeBatch), C.POINTER(vp)]
@@ -1074,6 +1209,16 @@ def _bind_genotype(L):
         fn = getattr(L, "ltr_genotype_result_" + f)
         fn.argtypes, fn.restype = [vp, i64], rt
     L.ltr_genotype_result_removed.argtypes, L.ltr_genotype_result_removed.restype = [vp, i64, i32, C.POINTER(C.POINTER(i32))], i32
+    L.ltr_plan_genotype_fields.argtypes = [vp, C.POINTER(_abi.GenotypeBatch), C.POINTER(_abi.FieldsRequest), C.POINTER(vp)]
+    L.ltr_genotype_result_fields.argtypes = [vp, i64, C.POINTER(_abi.LocusFields)]
+    L.ltr_genotype_result_vcf_records.argtypes = [vp, C.POINTER(_abi.VcfLocus), C.POINTER(_abi.VcfOptions), C.POINTER(vp), vp, vp]
+    L.ltr_vcf_text_free.argtypes, L.ltr_vcf_text_free.restype = [vp], None
+    L.ltr_vcf_fields.argtypes = [C.POINTER(_abi.VcfLocus), i32, i32, i32, C.POINTER(vp)]
+    L.ltr_vcf_field_set_view.argtypes, L.ltr_vcf_field_set_view.restype = [vp], C.POINTER(_abi.LocusFields)
+    L.ltr_vcf_field_set_free.argtypes, L.ltr_vcf_field_set_free.restype = [vp], None
+    L.ltr_vcf_record_from_fields.restype = i64
+    L.ltr_vcf_record_from_fields.argtypes = [C.POINTER(_abi.VcfLocus), C.POINTER(_abi.LocusFields), C.POINTER(_abi.VcfOptions), C.c_char_p, i64,
+                                             C.POINTER(i32)]
 
 
 def prune_hap_blocks(blocks, block, unused):

@@ -280,6 +280,8 @@ int short_batch_run(ltr_ctx* ctx, ShortBatch* b);
 // Haplotype::next() order (reference Haplotype.cpp:123-196): allele index per block for
 // every combination, combination-major.
 int haplotype_counts(const ltr_haplotype_blocks* hap, std::vector<int32_t>* counts, int64_t* ncombs);
+// ltr_vcf_record_from_fields into a string (ltr_vcf.cpp): the length of the text or a negative status
+int64_t vcf_record_string(const ltr_vcf_locus* v, const ltr_locus_fields* f, const ltr_vcf_options* opt, std::string* text, int32_t* pos);
 
 // A block list that owns its arrays (view points into them; not copyable once filled).
 struct OwnedHapBlocks {

@@ -9,6 +9,7 @@
 #include <memory>
 
 #include "ltr_ctx.h"
+#include "ltr_plan_fields.h"
 
 namespace {
 
@@ -175,15 +176,6 @@ __global__ void ltr_genotype_gather_kernel(const GtLocus* __restrict__ loci, con
   }
 }
 
-// a locus that lost alleles
-struct Pruned {
-  ltr::OwnedHapBlocks blocks;                    // HapBlock::remove_alleles of every block
-  std::vector<int32_t> new_to_old, allele_mapping;
-  std::vector<std::vector<int32_t>> removed;     // per block
-  int32_t aff_blocks = 0, aff_alleles = 0, Hn = 0;
-  int64_t post_off = 0;                          // its [S x Hn x Hn] block in post2
-};
-
 void set_priors(GtUnit* u, int32_t H, int haploid) {
   // int_log(v) == log(v) (mathops.cpp:14-22); priors of genotyper.cpp:21-33
   const double lH = std::log((double)H), lH1 = std::log((double)(H + 1));
@@ -229,19 +221,6 @@ PassShape shape_of(const GtUnit* units, size_t n_units) {
 
 }  // namespace
 
-struct ltr_genotype_result {
-  int64_t n_loci = 0;
-  std::vector<int32_t> S, H, n_blocks;           // per locus
-  std::vector<int64_t> unit_off, post1_off;      // [n_loci + 1]
-  std::unique_ptr<double[]> post1, post2, read_ll;      // first-pass blocks (plan's H), second-pass blocks of the pruned loci
-  std::vector<double> stl;                       // [units] final
-  std::vector<int32_t> gts;                      // [2 units] final
-  std::vector<int32_t> identity;                 // 0 .. max H - 1: new_to_old / allele_mapping of a locus that lost nothing
-  std::vector<std::unique_ptr<Pruned>> pruned;   // per locus, null: nothing removed
-  std::vector<const ltr_haplotype_blocks*> haps; // the caller's block lists
-  std::vector<int64_t> read_ll_off;              // [n_loci + 1] (want_read_ll)
-};
-
 #define G_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { ltr::set_error(ctx, std::string(#call) + ": " + hipGetErrorString(e_)); rc = LTR_ERR_HIP; goto done; } } while (0)
 
 namespace {
@@ -285,9 +264,9 @@ hipError_t upload_lists(ltr_ctx* ctx, hipStream_t st, const PassShape& ps, int32
 
 }  // namespace
 
-extern "C" {
-
-int ltr_plan_genotype(ltr_plan* plan, const ltr_genotype_batch* gb, ltr_genotype_result** out) {
+// ltr_plan_genotype (fr == null) and ltr_plan_genotype_fields: the same passes; with fr the fields kernel runs on their
+// buffers before they go back to the pool, and the posterior blocks are fetched only when fr asks for them.
+static int plan_genotype(ltr_plan* plan, const ltr_genotype_batch* gb, const ltr_fields_request* fr, ltr_genotype_result** out) {
   if (out) *out = nullptr;
   if (!plan || !gb || !gb->pb || !out) return LTR_ERR_INVALID;
   ltr_ctx* ctx = plan->ctx;
@@ -296,7 +275,8 @@ int ltr_plan_genotype(ltr_plan* plan, const ltr_genotype_batch* gb, ltr_genotype
   if (!plan->executed) { ltr::set_error(ctx, "ltr_plan_genotype: execute the plan first"); return LTR_ERR_INVALID; }
   const int64_t nl = pb->n_loci;
   if (nl != (int64_t)plan->locus_P.size()) { ltr::set_error(ctx, "genotype batch and plan disagree on the number of loci"); return LTR_ERR_INVALID; }
-  if (!gb->haps && nl > 0 && gb->prune) { ltr::set_error(ctx, "ltr_plan_genotype: no haplotype blocks"); return LTR_ERR_INVALID; }
+  if (!gb->haps && nl > 0 && (gb->prune || fr)) { ltr::set_error(ctx, "ltr_plan_genotype: no haplotype blocks"); return LTR_ERR_INVALID; }
+  const bool need_haps = gb->prune || fr, fetch_post = !fr || fr->want_posteriors;
   if (nl > 0 && (!pb->locus_read_off || !pb->n_samples || (pb->n_reads > 0 && (!pb->pool_index || !pb->log_p1 || !pb->log_p2 || !pb->sample_label)))) {
     ltr::set_error(ctx, "ltr_plan_genotype: incomplete posterior batch"); return LTR_ERR_INVALID;
   }
@@ -334,13 +314,21 @@ int ltr_plan_genotype(ltr_plan* plan, const ltr_genotype_batch* gb, ltr_genotype
   GtUnit* units = reinterpret_cast<GtUnit*>(ctx->gt_units.p);
   std::vector<uint8_t> aligned(nu, 0);
   std::atomic<int> bad(0);
-  std::atomic<int64_t> bad_haps(-1);
+  std::atomic<int64_t> bad_haps(-1), bad_block(-1);
+  if (fr) { res->has_fields = true; res->ctx = ctx; res->haploid = pb->haploid ? 1 : 0; res->f_block.assign((size_t)nl, 0); res->f_V.assign((size_t)nl, 0); }
   ltr::parallel_for(nl, 64, [&](int64_t l) {
     const int64_t r0 = pb->locus_read_off[l], r1 = pb->locus_read_off[l + 1], u0 = res->unit_off[(size_t)l];
     const int32_t S = pb->n_samples[l], H = plan->locus_H[(size_t)l], P = plan->locus_P[(size_t)l];
-    if (gb->prune) {     // (prune == 0 never reads the block lists: 100 000 of them scattered over the caller's heap cost 2 ms of cache misses)
+    if (need_haps) {     // (prune == 0 never reads the block lists: 100 000 of them scattered over the caller's heap cost 2 ms of cache misses)
       if (!gb->haps[l] || ltr_haplotype_num_combs(gb->haps[l]) != H) { bad_haps.store(l); return; }
       res->n_blocks[(size_t)l] = gb->haps[l]->n_blocks;
+    }
+    if (fr) {            // the block of the record: pruning keeps the blocks, so the caller's list tells
+      const ltr_haplotype_blocks* hb = gb->haps[l];
+      int32_t b = fr->block ? fr->block[l] : 0;
+      if (!fr->block) while (b < hb->n_blocks && !hb->is_repeat[b]) ++b;
+      if (b < 0 || b >= hb->n_blocks) { bad_block.store(l); return; }
+      res->f_block[(size_t)l] = b;
     }
     for (int64_t r = r0; r < r1; ++r) {
       const int32_t q = pb->pool_index[r], s = pb->sample_label[r];
@@ -360,11 +348,23 @@ int ltr_plan_genotype(ltr_plan* plan, const ltr_genotype_batch* gb, ltr_genotype
     ltr::set_error(ctx, "haplotype blocks of locus " + std::to_string(l) + " do not enumerate the plan's " + std::to_string(plan->locus_H[(size_t)l]) + " haplotypes");
     return LTR_ERR_INVALID;
   }
+  if (bad_block.load() >= 0) {
+    ltr::set_error(ctx, "ltr_plan_genotype_fields: locus " + std::to_string(bad_block.load()) + (fr->block ? ": block out of range" : ": no repeat block"));
+    return LTR_ERR_INVALID;
+  }
   if (bad.load()) { ltr::set_error(ctx, "pool index / sample label out of range"); return LTR_ERR_INVALID; }
-  if (nu == 0) { *out = res.release(); return LTR_OK; }       // (no sample anywhere: nothing to compute; read_ll stays NULL)
+  if (nu == 0) {                                               // (no sample anywhere: nothing to compute; read_ll stays NULL)
+    if (fr) {
+      res->f_gl_off.assign((size_t)nl + 1, 0); res->f_pgl_off.assign((size_t)nl + 1, 0);
+      res->f_read_off.assign(pb->locus_read_off, pb->locus_read_off + nl + 1);
+      for (int64_t l = 0; l < nl; ++l) res->f_V[(size_t)l] = gb->haps[l]->n_alleles[res->f_block[(size_t)l]];
+      res->f_i32.reset(new int32_t[std::max<size_t>(nr, 1)]()); res->f_f64.reset(new double[1]());
+    }
+    *out = res.release(); return LTR_OK;
+  }
 
   const int64_t npost1 = res->post1_off[(size_t)nl];
-  res->post1.reset(new double[(size_t)std::max<int64_t>(npost1, 1)]);
+  if (fetch_post) res->post1.reset(new double[(size_t)std::max<int64_t>(npost1, 1)]);
   const PassShape sh1 = shape_of(units, nu);
   LTR_DBG("genotype: %zu units laid out", nu);
   GtUnit *d_units = nullptr, *d_units2 = nullptr; GtLocus* d_loci = nullptr;
@@ -372,6 +372,9 @@ int ltr_plan_genotype(ltr_plan* plan, const ltr_genotype_batch* gb, ltr_genotype
   const int32_t *d_list = nullptr, *d_unf = nullptr;
   std::vector<int32_t> stage;
   double *d_p1 = nullptr, *d_p2 = nullptr, *d_post = nullptr, *d_stl = nullptr, *d_post2 = nullptr, *d_stl2 = nullptr, *d_rll = nullptr;
+  ltrf::FieldUnit* d_funits = nullptr; ltrf::FieldLocus* d_floci = nullptr; int32_t *d_ftab = nullptr, *d_fi32 = nullptr, *d_fpls = nullptr;
+  double *d_ff64 = nullptr, *d_fgls = nullptr, *d_fpgls = nullptr, *d_fcells = nullptr;
+  std::vector<ltrf::FieldUnit> funits; std::vector<ltrf::FieldLocus> floci; std::vector<int32_t> ftab;
   int rc = LTR_OK;
   hipStream_t st = plan->last_stream;
   std::vector<GtUnit> units2; std::vector<int32_t> map; std::vector<GtLocus> gl; std::vector<int64_t> affected;
@@ -402,7 +405,7 @@ int ltr_plan_genotype(ltr_plan* plan, const ltr_genotype_batch* gb, ltr_genotype
   LTR_DBG("genotype: first pass queued");
   G_TRY(hipStreamSynchronize(st));                             // (the host needs the best pairs; the posterior blocks follow below)
   LTR_DBG("genotype: first pass done");
-  G_TRY(hipMemcpyAsync(res->post1.get(), d_post, (size_t)npost1 * 8, hipMemcpyDeviceToHost, st));
+  if (fetch_post) G_TRY(hipMemcpyAsync(res->post1.get(), d_post, (size_t)npost1 * 8, hipMemcpyDeviceToHost, st));
 
   LTR_DBG("genotype: first posteriors fetched");
   // ---- between the passes (host, all loci at once): get_unused_alleles (:250-308), the new block lists and column maps ----
@@ -433,7 +436,7 @@ int ltr_plan_genotype(ltr_plan* plan, const ltr_genotype_batch* gb, ltr_genotype
         if (!removed[(size_t)b].empty()) ++aff_blocks;
       }
       if (aff_alleles == 0) return;                            // :641
-      std::unique_ptr<Pruned> p(new Pruned());
+      std::unique_ptr<LtrPruned> p(new LtrPruned());
       if (ltr::prune_hap_blocks(hb, removed, &p->blocks) != LTR_OK || ltr::remap_haplotypes(hb, &p->blocks.view, &p->allele_mapping, nullptr) != LTR_OK) {
         perr.store(1); return;
       }
@@ -448,7 +451,7 @@ int ltr_plan_genotype(ltr_plan* plan, const ltr_genotype_batch* gb, ltr_genotype
       rc = LTR_ERR_INVALID; goto done;
     }
     for (int64_t l = 0; l < nl; ++l) {
-      Pruned* p = res->pruned[(size_t)l].get();
+      LtrPruned* p = res->pruned[(size_t)l].get();
       if (!p) continue;
       const int32_t S = res->S[(size_t)l];
       const int64_t map_off = (int64_t)map.size();
@@ -473,7 +476,7 @@ int ltr_plan_genotype(ltr_plan* plan, const ltr_genotype_batch* gb, ltr_genotype
   if (!units2.empty()) {
     const size_t nu2 = units2.size();
     sh2 = shape_of(units2.data(), nu2);
-    res->post2.reset(new double[(size_t)std::max<int64_t>(npost2, 1)]);
+    if (fetch_post) res->post2.reset(new double[(size_t)std::max<int64_t>(npost2, 1)]);
     stl2.resize(nu2); gts2.resize(2 * nu2);
     G_TRY(ctx->pool.alloc((void**)&d_units2, nu2 * sizeof(GtUnit)));
     G_TRY(ctx->pool.alloc((void**)&d_post2, (size_t)std::max<int64_t>(npost2, 1) * 8));
@@ -483,7 +486,7 @@ int ltr_plan_genotype(ltr_plan* plan, const ltr_genotype_batch* gb, ltr_genotype
     G_TRY(upload_lists(ctx, st, sh2, &d_lists2, &d_list, &d_unf, &stage));
     launch_pass(sh2, st, d_units2, plan->last_out, d_pool, d_p1, d_p2, d_label, d_map, d_list, d_unf, d_post2, d_stl2, d_gts2);
     G_TRY(hipGetLastError());
-    G_TRY(hipMemcpyAsync(res->post2.get(), d_post2, (size_t)npost2 * 8, hipMemcpyDeviceToHost, st));
+    if (fetch_post) G_TRY(hipMemcpyAsync(res->post2.get(), d_post2, (size_t)npost2 * 8, hipMemcpyDeviceToHost, st));
     G_TRY(hipMemcpyAsync(stl2.data(), d_stl2, nu2 * 8, hipMemcpyDeviceToHost, st));
     G_TRY(hipMemcpyAsync(gts2.data(), d_gts2, nu2 * 8, hipMemcpyDeviceToHost, st));
   }
@@ -493,7 +496,7 @@ int ltr_plan_genotype(ltr_plan* plan, const ltr_genotype_batch* gb, ltr_genotype
     res->read_ll_off.assign((size_t)nl + 1, 0);
     int64_t mo = 0;
     for (int64_t l = 0; l < nl; ++l) {
-      const Pruned* p = res->pruned[(size_t)l].get();
+      const LtrPruned* p = res->pruned[(size_t)l].get();
       GtLocus& g = gl[(size_t)l];
       g.ll_off = plan->locus_ll_off[(size_t)l]; g.out_off = res->read_ll_off[(size_t)l]; g.map_off = p ? mo : -1;
       g.r0 = (int32_t)pb->locus_read_off[l]; g.r1 = (int32_t)pb->locus_read_off[l + 1]; g.H = res->H[(size_t)l]; g.Hn = p ? p->Hn : g.H;
@@ -508,6 +511,117 @@ int ltr_plan_genotype(ltr_plan* plan, const ltr_genotype_batch* gb, ltr_genotype
     hipLaunchKernelGGL(ltr_genotype_gather_kernel, dim3((unsigned)nl), dim3(64), 0, st, d_loci, plan->last_out, d_pool, d_map, d_rll);
     G_TRY(hipGetLastError());
     if (nrll) G_TRY(hipMemcpyAsync(res->read_ll.get(), d_rll, (size_t)nrll * 8, hipMemcpyDeviceToHost, st));
+  }
+  // ---- the VCF fields of every locus (ltr_plan_fields.hip), on the final posterior blocks where they lie ----
+  if (fr) {
+    res->f_gl_off.assign((size_t)nl + 1, 0); res->f_pgl_off.assign((size_t)nl + 1, 0);
+    res->f_read_off.assign(pb->locus_read_off, pb->locus_read_off + nl + 1);
+    floci.resize((size_t)nl);
+    std::vector<int64_t> unit2_off((size_t)nl, -1);             // first unit of a pruned locus in the second pass
+    { int64_t k = 0; for (int64_t l : affected) { unit2_off[(size_t)l] = k; k += res->S[(size_t)l]; } }
+    int64_t tab = 0, mo = 0;
+    for (int64_t l = 0; l < nl; ++l) {                           // sizes and offsets (the block lists are warm from the checks above)
+      const LtrPruned* p = res->pruned[(size_t)l].get();
+      const ltr_haplotype_blocks* hb = p ? &p->blocks.view : gb->haps[l];
+      ltrf::FieldLocus& F = floci[(size_t)l];
+      const int32_t S = res->S[(size_t)l], H = res->H[(size_t)l], Hn = p ? p->Hn : H, V = hb->n_alleles[res->f_block[(size_t)l]];
+      res->f_V[(size_t)l] = V;
+      F.ll_off = plan->locus_ll_off[(size_t)l]; F.map_off = p ? mo : -1; F.tab_off = tab;
+      F.gl_off = res->f_gl_off[(size_t)l]; F.pgl_off = res->f_pgl_off[(size_t)l];
+      F.r0 = (int32_t)pb->locus_read_off[l]; F.r1 = (int32_t)pb->locus_read_off[l + 1]; F.H = H; F.Hn = Hn; F.V = V; F.haploid = pb->haploid ? 1 : 0;
+      F.n_gl = pb->haploid ? V : V * (V + 1) / 2; F.n_pgl = pb->haploid ? V : V * V;
+      // priors (genotyper.cpp:21-33; the heterozygous one of a haploid call is 0, :210) and configuration terms (:204-241) as ltr_genotype.cpp:108-111
+      const double lH = std::log((double)Hn), lH1 = std::log((double)(Hn + 1)), lV = std::log((double)V), l2 = std::log(2.0);
+      const double hom_prior = pb->haploid ? -lH : l2 - lH - lH1, het_prior = pb->haploid ? 0.0 : -lH - lH1;
+      const double gl_cfg = pb->haploid ? l2 + lH - lV : l2 + 2 * (lH - lV), pgl_cfg = pb->haploid ? lH - lV : 2 * (lH - lV);
+      F.hom_gl = hom_prior + gl_cfg; F.het_gl = het_prior + gl_cfg; F.hom_pgl = hom_prior + pgl_cfg; F.het_pgl = het_prior + pgl_cfg;
+      if (p) mo += p->Hn;
+      tab += 2 * (int64_t)Hn + V + 1;
+      res->f_gl_off[(size_t)l + 1] = F.gl_off + (int64_t)S * F.n_gl;
+      res->f_pgl_off[(size_t)l + 1] = F.pgl_off + (int64_t)S * F.n_pgl;
+    }
+    ftab.resize((size_t)tab);
+    std::atomic<int> ferr(0);
+    ltr::parallel_for(nl, 64, [&](int64_t l) {                   // haps_to_alleles of the FINAL list (:240-248) and the haplotypes of every allele
+      const LtrPruned* p = res->pruned[(size_t)l].get();
+      const ltr_haplotype_blocks* hb = p ? &p->blocks.view : gb->haps[l];
+      const ltrf::FieldLocus& F = floci[(size_t)l];
+      std::vector<int32_t> counts; int64_t nc = 0;
+      if (ltr::haplotype_counts(hb, &counts, &nc) != LTR_OK || nc != F.Hn) { ferr.store(1); return; }
+      int32_t* h2a = ftab.data() + F.tab_off; int32_t* first = h2a + F.Hn; int32_t* list = first + F.V + 1;
+      for (int32_t a = 0; a <= F.V; ++a) first[a] = 0;
+      for (int32_t h = 0; h < F.Hn; ++h) {
+        const int32_t a = counts[(size_t)((int64_t)h * hb->n_blocks + res->f_block[(size_t)l])];
+        if (a < 0 || a >= F.V) { ferr.store(1); return; }
+        h2a[h] = a; first[a + 1]++;
+      }
+      for (int32_t a = 0; a < F.V; ++a) first[a + 1] += first[a];
+      std::vector<int32_t> at(first, first + F.V);
+      for (int32_t h = 0; h < F.Hn; ++h) list[at[(size_t)h2a[h]]++] = h;
+    }, 16);
+    if (ferr.load()) { ltr::set_error(ctx, "ltr_plan_genotype_fields: malformed haplotype blocks"); rc = LTR_ERR_INVALID; goto done; }
+    // units: those of up to kFieldSmallH haplotypes first (one wavefront each), then the others; a V x V table beyond LDS goes to a workspace
+    funits.resize(nu);
+    size_t n_small = 0;
+    int64_t ncells = 0; int cap_small = 1, cap_large = 1;
+    for (int64_t l = 0; l < nl; ++l) if (floci[(size_t)l].Hn <= ltrf::kFieldSmallH) n_small += (size_t)res->S[(size_t)l];
+    {
+      size_t ks = 0, kl = n_small;
+      for (int64_t l = 0; l < nl; ++l) {
+        const LtrPruned* p = res->pruned[(size_t)l].get();
+        const ltrf::FieldLocus& F = floci[(size_t)l];
+        const bool small = F.Hn <= ltrf::kFieldSmallH;
+        const int64_t vv = (int64_t)F.V * F.V;
+        for (int32_t s = 0; s < res->S[(size_t)l]; ++s) {
+          ltrf::FieldUnit& u = funits[small ? ks++ : kl++];
+          u.locus = (int32_t)l; u.sample = s; u.out = (int32_t)(res->unit_off[(size_t)l] + s);
+          u.pass = p ? 1 : 0; u.src = p ? (int32_t)(unit2_off[(size_t)l] + s) : u.out;
+          u.post_off = (p ? p->post_off : res->post1_off[(size_t)l]) + (int64_t)s * F.Hn * F.Hn;
+          if (vv > ltrf::kFieldCellCap) { u.cell_off = ncells; ncells += vv; }
+          else { u.cell_off = -1; int& cap = small ? cap_small : cap_large; cap = std::max(cap, (int)vv); }
+        }
+      }
+    }
+    const int64_t ngl = res->f_gl_off[(size_t)nl], npgl = res->f_pgl_off[(size_t)nl];
+    const size_t ni32 = 6 * nu + nr;
+    res->f_i32.reset(new int32_t[ni32]); res->f_f64.reset(new double[5 * nu]);
+    if (fr->want_gls) res->f_gls.reset(new double[(size_t)std::max<int64_t>(ngl, 1)]);
+    if (fr->want_pls) res->f_pls.reset(new int32_t[(size_t)std::max<int64_t>(ngl, 1)]);
+    if (fr->want_phased_gls) res->f_pgls.reset(new double[(size_t)std::max<int64_t>(npgl, 1)]);
+    G_TRY(ctx->pool.alloc((void**)&d_funits, nu * sizeof(ltrf::FieldUnit)));
+    G_TRY(ctx->pool.alloc((void**)&d_floci, (size_t)nl * sizeof(ltrf::FieldLocus)));
+    G_TRY(ctx->pool.alloc((void**)&d_ftab, ftab.size() * 4));
+    G_TRY(ctx->pool.alloc((void**)&d_fi32, ni32 * 4));
+    G_TRY(ctx->pool.alloc((void**)&d_ff64, 5 * nu * 8));
+    G_TRY(ctx->pool.alloc((void**)&d_fgls, (size_t)std::max<int64_t>(ngl, 1) * 8));
+    if (fr->want_pls) G_TRY(ctx->pool.alloc((void**)&d_fpls, (size_t)std::max<int64_t>(ngl, 1) * 4));
+    if (fr->want_phased_gls) G_TRY(ctx->pool.alloc((void**)&d_fpgls, (size_t)std::max<int64_t>(npgl, 1) * 8));
+    if (ncells) G_TRY(ctx->pool.alloc((void**)&d_fcells, (size_t)ncells * 8));
+    G_TRY(hipMemcpyAsync(d_funits, funits.data(), nu * sizeof(ltrf::FieldUnit), hipMemcpyHostToDevice, st));
+    G_TRY(hipMemcpyAsync(d_floci, floci.data(), (size_t)nl * sizeof(ltrf::FieldLocus), hipMemcpyHostToDevice, st));
+    G_TRY(hipMemcpyAsync(d_ftab, ftab.data(), ftab.size() * 4, hipMemcpyHostToDevice, st));
+    // a unit without an optimal pair (best_gts = -1) writes nothing else: its numbers read 0, not what the pool held before
+    G_TRY(hipMemsetAsync(d_fi32, 0, 6 * nu * 4, st));
+    G_TRY(hipMemsetAsync(d_ff64, 0, 5 * nu * 8, st));
+    if (ngl) G_TRY(hipMemsetAsync(d_fgls, 0, (size_t)ngl * 8, st));
+    if (fr->want_pls && ngl) G_TRY(hipMemsetAsync(d_fpls, 0, (size_t)ngl * 4, st));
+    if (fr->want_phased_gls && npgl) G_TRY(hipMemsetAsync(d_fpgls, 0, (size_t)npgl * 8, st));
+    if (nr) G_TRY(hipMemsetAsync(d_fi32 + 6 * nu, 0xff, nr * 4, st));   // (a read whose label no unit claims cannot exist: the labels were checked; -1 would be refused by the formatter)
+    {
+      ltrf::FieldArgs a;
+      a.units = d_funits; a.loci = d_floci; a.tab = d_ftab;
+      a.ll = plan->last_out; a.pool_index = d_pool; a.lp1 = d_p1; a.lp2 = d_p2; a.label = d_label; a.map = d_map;
+      a.post[0] = d_post; a.post[1] = d_post2; a.stl[0] = d_stl; a.stl[1] = d_stl2; a.gts[0] = d_gts; a.gts[1] = d_gts2;
+      a.best_gts = d_fi32; a.counts = d_fi32 + 2 * nu; a.scalars = d_ff64; a.nu = (int64_t)nu;
+      a.gls = d_fgls; a.pls = d_fpls; a.pgls = d_fpgls; a.cells = d_fcells; a.read_allele = d_fi32 + 6 * nu;
+      ltrf::launch_fields(st, a, n_small, cap_small, nu - n_small, cap_large);
+    }
+    G_TRY(hipGetLastError());
+    G_TRY(hipMemcpyAsync(res->f_i32.get(), d_fi32, ni32 * 4, hipMemcpyDeviceToHost, st));
+    G_TRY(hipMemcpyAsync(res->f_f64.get(), d_ff64, 5 * nu * 8, hipMemcpyDeviceToHost, st));
+    if (fr->want_gls && ngl) G_TRY(hipMemcpyAsync(res->f_gls.get(), d_fgls, (size_t)ngl * 8, hipMemcpyDeviceToHost, st));
+    if (fr->want_pls && ngl) G_TRY(hipMemcpyAsync(res->f_pls.get(), d_fpls, (size_t)ngl * 4, hipMemcpyDeviceToHost, st));
+    if (fr->want_phased_gls && npgl) G_TRY(hipMemcpyAsync(res->f_pgls.get(), d_fpgls, (size_t)npgl * 8, hipMemcpyDeviceToHost, st));
   }
   G_TRY(hipStreamSynchronize(st));
   LTR_DBG("genotype: second pass and gather done");
@@ -525,11 +639,21 @@ int ltr_plan_genotype(ltr_plan* plan, const ltr_genotype_batch* gb, ltr_genotype
 done:
   if (rc != LTR_OK) (void)hipStreamSynchronize(st);            // (buffers go back to the context's pool: nothing may still use them)
   for (void* p : {(void*)d_units, (void*)d_units2, (void*)d_loci, (void*)d_pool, (void*)d_label, (void*)d_map, (void*)d_lists1, (void*)d_lists2,
-                  (void*)d_gts, (void*)d_gts2, (void*)d_p1, (void*)d_p2, (void*)d_post, (void*)d_stl, (void*)d_post2, (void*)d_stl2, (void*)d_rll})
+                  (void*)d_gts, (void*)d_gts2, (void*)d_p1, (void*)d_p2, (void*)d_post, (void*)d_stl, (void*)d_post2, (void*)d_stl2, (void*)d_rll,
+                  (void*)d_funits, (void*)d_floci, (void*)d_ftab, (void*)d_fi32, (void*)d_fpls, (void*)d_ff64, (void*)d_fgls, (void*)d_fpgls, (void*)d_fcells})
     ctx->pool.release(p);
   if (rc == LTR_OK) *out = res.release();
   return rc;
   LTR_GUARD_END(ctx)
+}
+
+extern "C" {
+
+int ltr_plan_genotype(ltr_plan* plan, const ltr_genotype_batch* gb, ltr_genotype_result** out) { return plan_genotype(plan, gb, nullptr, out); }
+int ltr_plan_genotype_fields(ltr_plan* plan, const ltr_genotype_batch* gb, const ltr_fields_request* fr, ltr_genotype_result** out) {
+  if (out) *out = nullptr;
+  if (!fr) return LTR_ERR_INVALID;
+  return plan_genotype(plan, gb, fr, out);
 }
 
 void ltr_genotype_result_free(ltr_genotype_result* r) { delete r; }
@@ -551,7 +675,7 @@ const int32_t* ltr_genotype_result_allele_mapping(const ltr_genotype_result* r, 
 int32_t ltr_genotype_result_removed(const ltr_genotype_result* r, int64_t l, int32_t block, const int32_t** alleles) {
   if (alleles) *alleles = nullptr;
   GT_LOCUS(r, l, LTR_ERR_INVALID);
-  const Pruned* p = r->pruned[(size_t)l].get();
+  const LtrPruned* p = r->pruned[(size_t)l].get();
   if (!p) return block < 0 ? LTR_ERR_INVALID : 0;
   if (block < 0 || block >= r->n_blocks[(size_t)l]) return LTR_ERR_INVALID;
   if (!p || p->removed[(size_t)block].empty()) return 0;
@@ -572,6 +696,7 @@ const ltr_haplotype_blocks* ltr_genotype_result_blocks(const ltr_genotype_result
 }
 const double* ltr_genotype_result_log_sample_posteriors(const ltr_genotype_result* r, int64_t l) {
   GT_LOCUS(r, l, nullptr);
+  if (!r->post1) return nullptr;                               // (ltr_plan_genotype_fields without want_posteriors)
   return r->pruned[(size_t)l] ? r->post2.get() + r->pruned[(size_t)l]->post_off : r->post1.get() + r->post1_off[(size_t)l];
 }
 const double* ltr_genotype_result_sample_total_ll(const ltr_genotype_result* r, int64_t l) {

@@ -11,7 +11,9 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <cstdlib>
 #include <map>
+#include <memory>
 #include <set>
 #include <sstream>
 #include <string>
@@ -21,7 +23,6 @@
 
 namespace {
 
-const double kLogOneHalf = -0.6931471805599453094;   // LOG_ONE_HALF, mathops.cpp:10
 const double kTolerance = 1e-10;                      // TOLERANCE, mathops.cpp:12
 
 std::string allele_of(const ltr_haplotype_blocks* hap, int block, int allele) {
@@ -30,15 +31,6 @@ std::string allele_of(const ltr_haplotype_blocks* hap, int block, int allele) {
   k += allele;
   return std::string(reinterpret_cast<const char*>(hap->allele_bytes) + hap->allele_off[k],
                      (size_t)(hap->allele_off[k + 1] - hap->allele_off[k]));
-}
-
-// log_sum_exp over a vector (mathops.cpp:40-53): max, then sum of exp(x - max) in index order
-double log_sum_exp(const std::vector<double>& v) {
-  double mx = v[0];
-  for (size_t i = 1; i < v.size(); ++i) mx = std::max(mx, v[i]);
-  double tot = 0.0;
-  for (size_t i = 0; i < v.size(); ++i) tot += std::exp(v[i] - mx);
-  return mx + std::log(tot);
 }
 
 // Genotyper::condense_read_counts (genotyper.h:50-63): key|count pairs in key order, ';' separated
@@ -361,19 +353,101 @@ int32_t ltr_get_alleles(const ltr_vcf_locus* v, int32_t* pos, char* out, int64_t
   } catch (...) { return LTR_ERR_INVALID; }
 }
 
-// write_vcf_record (:894-1366) for one repeat block of one locus: CHROM .. FORMAT and one column per
-// requested sample.  Returns the length of the text written to `out` (no trailing newline) or < 0.
-int64_t ltr_vcf_record(const ltr_vcf_locus* v, const ltr_vcf_options* opt_in, char* out, int64_t cap, int32_t* pos_out) {
-  if (!v || !v->hap || !out || v->n_reads < 0 || v->n_samples <= 0 || v->block < 0 || v->block >= v->hap->n_blocks) return LTR_ERR_INVALID;
+// The arithmetic half of write_vcf_record: extract_genotypes_and_likelihoods (:916-927) and the per-read bookkeeping
+// (:929-1043, long path: no traces).  ltr_plan_fields.hip computes the same numbers on the device.
+struct ltr_vcf_field_set {
+  ltr_locus_fields view;
+  std::vector<int32_t> gts, pls, n_aligned, n_snp, n_s1, n_s2, read_allele;
+  std::vector<double> lphased, lunphased, hphased, hunphased, gldiff, gls, pgls;
+};
+
+int ltr_vcf_fields(const ltr_vcf_locus* v, int32_t want_gls, int32_t want_pls, int32_t want_phased_gls, ltr_vcf_field_set** out) {
+  if (out) *out = nullptr;
+  if (!out || !v || !v->hap || v->n_reads < 0 || v->n_samples <= 0 || v->block < 0 || v->block >= v->hap->n_blocks) return LTR_ERR_INVALID;
   if (!v->log_aln_probs || !v->log_p1 || !v->log_p2 || !v->sample_label || !v->log_sample_posteriors || !v->sample_total_ll ||
-      !v->best_haplotypes || !v->chrom || !v->sample_names) return LTR_ERR_INVALID;
+      !v->best_haplotypes) return LTR_ERR_INVALID;
   try {
-    ltr_vcf_options opt;
-    if (opt_in) opt = *opt_in; else ltr_default_vcf_options(&opt);
     const bool haploid = v->haploid != 0;
     const int S = v->n_samples, R = v->n_reads;
     const int64_t H = ltr_haplotype_num_combs(v->hap);
     if (H <= 0) return LTR_ERR_INVALID;
+    const int V = v->hap->n_alleles[v->block];
+    if (V <= 0) return LTR_ERR_INVALID;
+    std::unique_ptr<ltr_vcf_field_set> fs(new ltr_vcf_field_set());
+    // genotypes and likelihoods (:916-927) -- ltr_extract_genotypes is extract_genotypes_and_likelihoods
+    std::vector<int32_t> h2a((size_t)H);
+    int rc = ltr_haps_to_alleles(v->hap, v->block, h2a.data());
+    if (rc != LTR_OK) return rc;
+    const int n_gl = haploid ? V : V * (V + 1) / 2, n_pgl = haploid ? V : V * V;
+    fs->gts.resize((size_t)2 * S);
+    if (want_pls) fs->pls.resize((size_t)S * n_gl);
+    fs->lphased.resize((size_t)S); fs->lunphased.resize((size_t)S); fs->hphased.resize((size_t)S); fs->hunphased.resize((size_t)S);
+    fs->gldiff.resize((size_t)S); fs->gls.resize((size_t)S * n_gl);
+    if (want_phased_gls) fs->pgls.resize((size_t)S * n_pgl);
+    ltr_genotype_fields gf;
+    gf.best_gts = fs->gts.data(); gf.log_phased_posteriors = fs->lphased.data(); gf.log_unphased_posteriors = fs->lunphased.data();
+    gf.hap_log_phased_posteriors = fs->hphased.data(); gf.hap_log_unphased_posteriors = fs->hunphased.data();
+    gf.gls = fs->gls.data(); gf.gl_diffs = fs->gldiff.data(); gf.pls = want_pls ? fs->pls.data() : nullptr;
+    gf.phased_gls = want_phased_gls ? fs->pgls.data() : nullptr;
+    rc = ltr_extract_genotypes(S, (int32_t)H, V, h2a.data(), haploid ? 1 : 0, v->log_sample_posteriors, v->sample_total_ll, v->best_haplotypes, &gf);
+    if (rc != LTR_OK) return rc;
+
+    // per-read bookkeeping (:929-1043), long path: no traces.  (The phase of each read, :958-960, feeds only the disabled
+    // allele-bias fields, :1232-1233: not computed.)
+    fs->n_aligned.assign((size_t)S, 0); fs->n_snp.assign((size_t)S, 0); fs->n_s1.assign((size_t)S, 0); fs->n_s2.assign((size_t)S, 0);
+    fs->read_allele.resize((size_t)R);
+    for (int r = 0; r < R; ++r) {
+      const int s = v->sample_label[r];
+      if (s < 0 || s >= S) return LTR_ERR_INVALID;
+      const double* ll = v->log_aln_probs + (size_t)r * H;
+      const int ha = v->best_haplotypes[2 * s], hb = v->best_haplotypes[2 * s + 1];
+      if (ha < 0 || ha >= H || hb < 0 || hb >= H) return LTR_ERR_INVALID;
+      int strand = 0;
+      if (!haploid && ha != hb) strand = (v->log_p1[r] + ll[ha] > v->log_p2[r] + ll[hb]) ? 0 : 1;          // :965-967
+      const int best_hap = strand == 0 ? ha : hb;
+      fs->n_aligned[(size_t)s]++;
+      if (std::fabs(v->log_p1[r] - v->log_p2[r]) > kTolerance) {                                           // :1006-1012
+        fs->n_snp[(size_t)s]++;
+        if (v->log_p1[r] > v->log_p2[r]) fs->n_s1[(size_t)s]++; else fs->n_s2[(size_t)s]++;
+      }
+      fs->read_allele[(size_t)r] = h2a[(size_t)best_hap];                                                  // :1038-1040
+    }
+    ltr_locus_fields& f = fs->view;
+    f.S = S; f.R = R; f.V = V; f.block = v->block; f.n_gl = n_gl; f.n_pgl = n_pgl;
+    f.best_gts = fs->gts.data(); f.log_phased = fs->lphased.data(); f.log_unphased = fs->lunphased.data();
+    f.hap_log_phased = fs->hphased.data(); f.hap_log_unphased = fs->hunphased.data(); f.gl_diffs = fs->gldiff.data();
+    f.gls = want_gls ? fs->gls.data() : nullptr; f.pls = want_pls ? fs->pls.data() : nullptr;
+    f.phased_gls = want_phased_gls ? fs->pgls.data() : nullptr;
+    f.n_aligned = fs->n_aligned.data(); f.n_snp = fs->n_snp.data(); f.n_s1 = fs->n_s1.data(); f.n_s2 = fs->n_s2.data();
+    f.read_allele = fs->read_allele.data();
+    *out = fs.release();
+    return LTR_OK;
+  } catch (const std::bad_alloc&) { return LTR_ERR_NOMEM; } catch (...) { return LTR_ERR_INVALID; }
+}
+const ltr_locus_fields* ltr_vcf_field_set_view(const ltr_vcf_field_set* f) { return f ? &f->view : nullptr; }
+void ltr_vcf_field_set_free(ltr_vcf_field_set* f) { delete f; }
+
+// The text half of write_vcf_record (:894-913, :1045-1366) for one repeat block of one locus: CHROM .. FORMAT and one column
+// per requested sample, from the fields.  Returns the length of the text written to `out` (no trailing newline) or < 0.
+static int64_t record_text(const ltr_vcf_locus* v, const ltr_locus_fields* f, const ltr_vcf_options* opt_in, std::string* text_out, int32_t* pos_out) {
+  if (!v || !f || !v->hap || !text_out || v->n_reads < 0 || v->n_samples <= 0 || v->block < 0 || v->block >= v->hap->n_blocks) return LTR_ERR_INVALID;
+  if (!v->sample_label || !v->chrom || !v->sample_names) return LTR_ERR_INVALID;
+  if (f->S != v->n_samples || f->R != v->n_reads || f->V != v->hap->n_alleles[v->block]) return LTR_ERR_INVALID;
+  if (!f->best_gts || !f->log_phased || !f->log_unphased || !f->hap_log_phased || !f->hap_log_unphased || !f->gl_diffs || !f->n_aligned ||
+      !f->n_snp || !f->n_s1 || !f->n_s2 || (f->R > 0 && !f->read_allele)) return LTR_ERR_INVALID;
+  try {
+    ltr_vcf_options opt;
+    if (opt_in) opt = *opt_in; else ltr_default_vcf_options(&opt);
+    const bool haploid = v->haploid != 0;
+    const int S = v->n_samples, R = v->n_reads, V = f->V;
+    const int n_gl = haploid ? V : V * (V + 1) / 2, n_pgl = haploid ? V : V * V;
+    if (f->n_gl != n_gl || f->n_pgl != n_pgl) return LTR_ERR_INVALID;
+    if ((opt.output_gls && !f->gls) || (opt.output_pls && !f->pls) || (!haploid && opt.output_phased_gls && !f->phased_gls)) return LTR_ERR_INVALID;
+    for (int s = 0; s < 2 * S; ++s) if (f->best_gts[s] < 0 || f->best_gts[s] >= V) return LTR_ERR_INVALID;
+    for (int r = 0; r < R; ++r) if (f->read_allele[r] < 0 || f->read_allele[r] >= V || v->sample_label[r] < 0 || v->sample_label[r] >= S) return LTR_ERR_INVALID;
+    const int32_t* gts = f->best_gts;
+    const double *lphased = f->log_phased, *lunphased = f->log_unphased, *hphased = f->hap_log_phased, *hunphased = f->hap_log_unphased, *gldiff = f->gl_diffs;
+    const int32_t *n_aligned = f->n_aligned, *n_snp = f->n_snp, *n_s1 = f->n_s1, *n_s2 = f->n_s2;
     std::ostringstream o;
     o.precision(2);
     o.setf(std::ios::fixed, std::ios::floatfield);             // :898-899
@@ -381,52 +455,21 @@ int64_t ltr_vcf_record(const ltr_vcf_locus* v, const ltr_vcf_options* opt_in, ch
     int32_t pos = 0;
     std::vector<std::string> alleles; std::vector<bool> inexact;
     get_alleles(v, &pos, &alleles, &inexact);
-    const int V = (int)alleles.size();
+    if ((int)alleles.size() != V) return LTR_ERR_INVALID;
     std::vector<int> bp_diffs;                                 // :906-913
     for (int i = 0; i < V; ++i)
       bp_diffs.push_back(alleles[(size_t)i] == "<DEL>" ? -(int)alleles[0].size() : (int)alleles[(size_t)i].size() - (int)alleles[0].size());
 
-    // genotypes and likelihoods (:916-927) -- ltr_extract_genotypes is extract_genotypes_and_likelihoods
-    std::vector<int32_t> h2a((size_t)H);
-    int rc = ltr_haps_to_alleles(v->hap, v->block, h2a.data());
-    if (rc != LTR_OK) return rc;
-    const int n_gl = haploid ? V : V * (V + 1) / 2, n_pgl = haploid ? V : V * V;
-    std::vector<int32_t> gts((size_t)2 * S), pls((size_t)S * n_gl);
-    std::vector<double> lphased((size_t)S), lunphased((size_t)S), hphased((size_t)S), hunphased((size_t)S), gldiff((size_t)S),
-        gls((size_t)S * n_gl), pgls((size_t)S * n_pgl);
-    ltr_genotype_fields gf;
-    gf.best_gts = gts.data(); gf.log_phased_posteriors = lphased.data(); gf.log_unphased_posteriors = lunphased.data();
-    gf.hap_log_phased_posteriors = hphased.data(); gf.hap_log_unphased_posteriors = hunphased.data();
-    gf.gls = gls.data(); gf.gl_diffs = gldiff.data(); gf.pls = opt.output_pls ? pls.data() : nullptr;
-    gf.phased_gls = opt.output_phased_gls ? pgls.data() : nullptr;
-    rc = ltr_extract_genotypes(S, (int32_t)H, V, h2a.data(), haploid ? 1 : 0, v->log_sample_posteriors, v->sample_total_ll, v->best_haplotypes, &gf);
-    if (rc != LTR_OK) return rc;
-
-    // per-read bookkeeping (:929-1043), long path: no traces
-    std::vector<int> n_aligned((size_t)S, 0), n_snp((size_t)S, 0), n_flank((size_t)S, 0), n_s1((size_t)S, 0), n_s2((size_t)S, 0);
+    // the reads' base pair differences per sample, in read order (:1015-1022 ALLREADS, :1038-1040 MALLREADS)
+    std::vector<int> n_flank((size_t)S, 0);
     std::vector<std::vector<int>> bps((size_t)S), ml_bps((size_t)S);
-    std::vector<std::vector<double>> phases((size_t)S);
     for (int r = 0; r < R; ++r) {
       const int s = v->sample_label[r];
-      if (s < 0 || s >= S) return LTR_ERR_INVALID;
-      const double* ll = v->log_aln_probs + (size_t)r * H;
-      const int ha = v->best_haplotypes[2 * s], hb = v->best_haplotypes[2 * s + 1];
-      if (ha < 0 || ha >= H || hb < 0 || hb >= H) return LTR_ERR_INVALID;
-      const double tot = std::log(std::exp(ll[ha] + v->log_p1[r] + kLogOneHalf) + std::exp(ll[hb] + v->log_p2[r] + kLogOneHalf));   // :958
-      phases[(size_t)s].push_back(kLogOneHalf + v->log_p1[r] + ll[ha] - tot);
-      int strand = 0;
-      if (!haploid && ha != hb) strand = (v->log_p1[r] + ll[ha] > v->log_p2[r] + ll[hb]) ? 0 : 1;          // :965-967
-      const int best_hap = strand == 0 ? ha : hb;
-      n_aligned[(size_t)s]++;
-      if (std::fabs(v->log_p1[r] - v->log_p2[r]) > kTolerance) {                                           // :1006-1012
-        n_snp[(size_t)s]++;
-        if (v->log_p1[r] > v->log_p2[r]) n_s1[(size_t)s]++; else n_s2[(size_t)s]++;
-      }
       if (v->alns) {                                                                                       // :1015-1022
         if (v->aln_deleted && v->aln_deleted[r]) bps[(size_t)s].push_back(-(int)alleles[0].size());
         else { int d = 0; if (extract_cigar(v->alns[r], v->region_start - 5, v->region_stop + 5, &d)) bps[(size_t)s].push_back(d); }
       }
-      ml_bps[(size_t)s].push_back(bp_diffs[(size_t)h2a[(size_t)best_hap]]);                               // :1038-1040
+      ml_bps[(size_t)s].push_back(bp_diffs[(size_t)f->read_allele[r]]);
     }
 
     // allele counts over the requested samples (:1045-1071); the requested samples are looked up by name
@@ -509,8 +552,8 @@ int64_t ltr_vcf_record(const ltr_vcf_locus* v, const ltr_vcf_options* opt_in, ch
       if (V == 1) o << ":" << "."; else o << ":" << gldiff[(size_t)s];
       if (opt.output_allreads) o << ":" << condense(bps[(size_t)s]);
       if (opt.output_mallreads) o << ":" << condense(ml_bps[(size_t)s]);
-      const double* gl = gls.data() + (size_t)s * n_gl;
-      const int32_t* pl = pls.data() + (size_t)s * n_gl;
+      const double* gl = f->gls ? f->gls + (size_t)s * n_gl : nullptr;
+      const int32_t* pl = f->pls ? f->pls + (size_t)s * n_gl : nullptr;
       if (haploid) {
         if (opt.output_gls) { o << ":" << gl[0]; for (int a = 1; a < V; ++a) o << "," << gl[n2o[(size_t)a]]; }
         if (opt.output_pls) { o << ":" << pl[0]; for (int a = 1; a < V; ++a) o << "," << pl[n2o[(size_t)a]]; }
@@ -519,7 +562,7 @@ int64_t ltr_vcf_record(const ltr_vcf_locus* v, const ltr_vcf_options* opt_in, ch
         if (opt.output_gls) { o << ":" << gl[0]; for (int a = 1; a < V; ++a) for (int b = 0; b <= a; ++b) o << "," << gl[tri(a, b)]; }
         if (opt.output_pls) { o << ":" << pl[0]; for (int a = 1; a < V; ++a) for (int b = 0; b <= a; ++b) o << "," << pl[tri(a, b)]; }
         if (opt.output_phased_gls) {
-          const double* pg = pgls.data() + (size_t)s * n_pgl;
+          const double* pg = f->phased_gls + (size_t)s * n_pgl;
           o << ":" << pg[0];
           for (int a = 0; a < V; ++a) for (int b = 0; b < V; ++b) { if (a == 0 && b == 0) continue; o << "," << pg[n2o[(size_t)a] * V + n2o[(size_t)b]]; }
         }
@@ -527,15 +570,48 @@ int64_t ltr_vcf_record(const ltr_vcf_locus* v, const ltr_vcf_options* opt_in, ch
       if (opt.output_haplotype_data) o << ":" << std::exp(hunphased[(size_t)s]) << ":" << std::exp(hphased[(size_t)s]);
       if (opt.output_filters) o << ":PASS";
     }
-    const std::string text = o.str();
-    if ((int64_t)text.size() + 1 > cap) return LTR_ERR_INVALID;
-    std::memcpy(out, text.data(), text.size());
-    out[text.size()] = '\0';
+    *text_out = o.str();
     if (pos_out) *pos_out = pos;
-    (void)phases; (void)log_sum_exp;                            // (phase1/phase2 read counts feed only the disabled allele-bias fields, :1232-1233)
-    return (int64_t)text.size();
+    return (int64_t)text_out->size();
   } catch (const std::bad_alloc&) { return LTR_ERR_NOMEM; } catch (...) { return LTR_ERR_INVALID; }
 }
+
+int64_t ltr_vcf_record_from_fields(const ltr_vcf_locus* v, const ltr_locus_fields* f, const ltr_vcf_options* opt, char* out, int64_t cap, int32_t* pos_out) {
+  if (!out) return LTR_ERR_INVALID;
+  std::string text; int32_t pos = 0;
+  const int64_t n = record_text(v, f, opt, &text, &pos);
+  if (n < 0) return n;
+  if (n + 1 > cap) return LTR_ERR_INVALID;
+  std::memcpy(out, text.data(), text.size());
+  out[text.size()] = '\0';
+  if (pos_out) *pos_out = pos;
+  return n;
+}
+
+// write_vcf_record (:894-1366): the fields, then the text
+int64_t ltr_vcf_record(const ltr_vcf_locus* v, const ltr_vcf_options* opt_in, char* out, int64_t cap, int32_t* pos_out) {
+  if (!v || !out) return LTR_ERR_INVALID;
+  ltr_vcf_options opt;
+  if (opt_in) opt = *opt_in; else ltr_default_vcf_options(&opt);
+  ltr_vcf_field_set* fs = nullptr;
+  const int rc = ltr_vcf_fields(v, opt.output_gls, opt.output_pls, opt.output_phased_gls, &fs);
+  if (rc != LTR_OK) return rc;
+  const int64_t n = ltr_vcf_record_from_fields(v, &fs->view, &opt, out, cap, pos_out);
+  ltr_vcf_field_set_free(fs);
+  return n;
+}
+
+void ltr_vcf_text_free(char* text) { std::free(text); }
+
+}  // extern "C"
+
+namespace ltr {
+int64_t vcf_record_string(const ltr_vcf_locus* v, const ltr_locus_fields* f, const ltr_vcf_options* opt, std::string* text, int32_t* pos) {
+  return record_text(v, f, opt, text, pos);
+}
+}  // namespace ltr
+
+extern "C" {
 
 // Genotyper::get_vcf_header (genotyper.cpp:258-336): file format, command, reference, the FASTA's ##contig lines
 // (FastaReader::write_all_contigs_to_vcf = ltr_fasta_contig_lines), the INFO and FORMAT definitions of the fields
