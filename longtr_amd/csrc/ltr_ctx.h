@@ -1,13 +1,16 @@
-// ltr_ctx.h -- the context and the plan as the four units that implement them see them: ltr_ctx.hip (context, model tables,
-// caches), ltr_plan_build.hip (ltr_plan_create / _destroy), ltr_plan_run.hip (execute, fetch, statistics), ltr_posterior.hip.
-// Private to those four: everything else (ltr_host.cpp, ltr_short.hip, ltr_nw.hip, ..) goes through the ltr::ctx_* accessors
+// ltr_ctx.h -- the context and the plan as the units that implement them see them: ltr_ctx.hip (context, model tables, caches),
+// ltr_plan_build.hip (ltr_plan_create / _destroy), ltr_plan_run.hip (execute, fetch, statistics) and the consumers of a plan's
+// scores, ltr_posterior.hip, ltr_plan_genotype.hip, ltr_plan_fields.hip.
+// Private to those six: everything else (ltr_host.cpp, ltr_short.hip, ltr_nw.hip, ..) goes through the ltr::ctx_* accessors
 // of ltr_internal.h, which is what lets tests/host_sanitize/harness.cpp supply a context of its own.
 #ifndef LTR_CTX_H_
 #define LTR_CTX_H_
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <set>
 #include <string>
@@ -63,6 +66,38 @@ struct DevPool {
     std::lock_guard<std::mutex> lk(mu);
     for (auto& kv : idle) (void)hipFree(kv.second);
     idle.clear(); cached = 0;
+  }
+};
+
+// The device blocks of ONE call on ONE stream, and the host staging memory its queued copies read or write.
+// Invariant: on every way out of the call -- a normal return, an error return, an exception on its way to LTR_GUARD_END -- the
+// stream is drained before any block goes back to the pool and before any host memory handed out here is freed.  Host memory
+// of the call's own that queued copies touch must outlive the lease: declare it BEFORE the lease (members of a per-call struct
+// with the lease last), or take it from host().
+struct DevLease {
+  DevPool& pool;
+  const hipStream_t st;
+  std::vector<void*> blocks;
+  std::vector<std::unique_ptr<char[]>> staging;
+  bool drained = false;
+  DevLease(DevPool& p, hipStream_t s) : pool(p), st(s) {}
+  DevLease(const DevLease&) = delete;
+  template <class T> hipError_t alloc(T** out, size_t bytes) {
+    blocks.push_back(nullptr);                                  // (the slot first: growing the list may throw, and must not lose a block)
+    const hipError_t e = pool.alloc(&blocks.back(), bytes);
+    *out = static_cast<T*>(blocks.back());
+    return e;
+  }
+  template <class T> T* host(size_t n) {                        // n zeroed objects
+    std::unique_ptr<char[]> m(new char[std::max<size_t>(n, 1) * sizeof(T)]());
+    staging.push_back(std::move(m));
+    return reinterpret_cast<T*>(staging.back().get());
+  }
+  // the call's last wait, after everything has been queued: the destructor does not wait again
+  hipError_t drain() { const hipError_t e = hipStreamSynchronize(st); drained = e == hipSuccess; return e; }
+  ~DevLease() {
+    if (!drained && !(blocks.empty() && staging.empty())) (void)hipStreamSynchronize(st);   // (nothing handed out: nothing queued on it)
+    for (void* p : blocks) pool.release(p);
   }
 };
 
@@ -149,6 +184,8 @@ constexpr int kHapPad = 96;                     // zero bytes either side of the
       return (e_ == hipErrorNoDevice || e_ == hipErrorInvalidDevice) ? LTR_ERR_NO_DEVICE : LTR_ERR_HIP; \
     }                                                                                        \
   } while (0)
+// ... and of the calls that hold a DevLease (which drains the stream and gives the blocks back on the way out)
+#define DEV_TRY(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { ltr::set_error(ctx, std::string(#call) + ": " + hipGetErrorString(e_)); return LTR_ERR_HIP; } } while (0)
 
 struct ltr_plan : ltrp::BatchPlan {     // (what ltrp::describe_batch decided: sizes, class ranges, per-locus layout)
   ltr_ctx* ctx = nullptr;
@@ -221,7 +258,7 @@ struct ltr_plan : ltrp::BatchPlan {     // (what ltrp::describe_batch decided: s
   bool kernel_ms_counted = true;
 };
 
-// ---- what the four units need from each other ----
+// ---- what the units need from each other ----
 #pragma GCC visibility push(hidden)
 // ltr_ctx.hip
 int build_tables(ltr_ctx* ctx, int64_t len, bool same_size = false);

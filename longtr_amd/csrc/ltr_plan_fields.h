@@ -1,11 +1,11 @@
 // ltr_plan_fields.h -- what ltr_plan_genotype.hip (the passes) and ltr_plan_fields.hip (the VCF fields of every locus of a
-// genotyped plan) share: the result object and the launch of the fields kernel.
+// genotyped plan) share: the result object and the fields stage.
 #pragma once
 
 #include <memory>
 #include <vector>
 
-#include "ltr_ctx.h"
+#include "ltr_posterior_common.h"
 
 // a locus that lost alleles
 struct LtrPruned {
@@ -39,38 +39,14 @@ struct ltr_genotype_result {
   std::unique_ptr<int32_t[]> f_pls;
 };
 
-namespace ltrf {
+// the device outputs of a posterior pass (null: the pass did not run)
+struct DevPass { double* post = nullptr; double* stl = nullptr; int* gts = nullptr; };
 
-// one locus of the fields kernel
-struct FieldLocus {
-  int64_t ll_off, map_off;       // the locus block in the LL buffer ([P x H]); new_to_old in the map buffer, -1: identity
-  int64_t tab_off;               // in the table buffer: hap_to_allele [Hn], allele_first [V + 1], haps_by_allele [Hn] (allele, then haplotype, ascending)
-  int64_t gl_off, pgl_off;       // sample 0 of the locus in gls / pls and in phased_gls
-  int32_t r0, r1, H, Hn, V, haploid, n_gl, n_pgl;
-  double hom_gl, het_gl, hom_pgl, het_pgl;   // prior + configuration term of a homozygous / heterozygous cell (genotyper.cpp:204-241; host libm)
-};
-// one (locus, sample)
-struct FieldUnit {
-  int64_t post_off;              // its [Hn x Hn] block in the posterior buffer of its pass
-  int64_t cell_off;              // its [V x V] genotype posteriors in the workspace; -1: they fit LDS
-  int32_t locus, sample, out;    // out: slot in the per-unit outputs
-  int32_t src, pass;             // slot in the total / best-pair buffers of pass 0 (first) or 1 (second)
-};
-struct FieldArgs {
-  const FieldUnit* units; const FieldLocus* loci; const int32_t* tab;
-  const double* ll; const int32_t* pool_index; const double* lp1; const double* lp2; const int32_t* label; const int32_t* map;
-  const double* post[2]; const double* stl[2]; const int* gts[2];
-  int32_t* best_gts; int32_t* counts;            // [2 nu]; n_aligned, n_snp, n_s1, n_s2: [4][nu]
-  double* scalars;                               // log_phased, log_unphased, hap_log_phased, hap_log_unphased, gl_diffs: [5][nu]
-  int64_t nu;
-  double* gls; int32_t* pls; double* pgls;       // pls, pgls: null = not wanted
-  double* cells; int32_t* read_allele;
-};
-
-constexpr int kFieldSmallH = 8;        // like the posterior passes: up to 8 haplotypes run in workgroups of one wavefront, the others of four
-constexpr int kFieldCellCap = 2048;    // largest V x V table kept in LDS (16 KB)
-
-// units [0, n_small) in workgroups of 64 threads, [n_small, n_small + n_large) of 256; cell_cap_*: doubles of LDS for the V x V table
-void launch_fields(hipStream_t st, const FieldArgs& a, size_t n_small, int cell_cap_small, size_t n_large, int cell_cap_large);
-
-}  // namespace ltrf
+#pragma GCC visibility push(hidden)
+// The fields stage of ltr_plan_genotype_fields (ltr_plan_fields.hip): layout, tables, the kernel on the passes' buffers where they
+// lie, copies into res.  pass[0] / pass[1]: the first / second pass; d_map: the column maps of the pruned loci (null: none).
+int ltr_plan_fields_stage(ltr_plan* plan, const ltr_genotype_batch* gb, const ltr_fields_request* fr, ltr_genotype_result* res,
+                          const DevReads& rd, const int32_t* d_map, const DevPass pass[2], DevLease& lease);
+// ... of a batch without a single sample: the per-locus sizes, nothing to compute
+void ltr_plan_fields_empty(const ltr_genotype_batch* gb, ltr_genotype_result* res);
+#pragma GCC visibility pop

@@ -10,15 +10,47 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <atomic>
 #include <string>
 
 #include "ltr_plan_fields.h"
 
+namespace ltrf {                  // (the kernel's argument types, of this unit only)
+
+// one locus of the fields kernel
+struct FieldLocus {
+  int64_t ll_off, map_off;       // the locus block in the LL buffer ([P x H]); new_to_old in the map buffer, -1: identity
+  int64_t tab_off;               // in the table buffer: hap_to_allele [Hn], allele_first [V + 1], haps_by_allele [Hn] (allele, then haplotype, ascending)
+  int64_t gl_off, pgl_off;       // sample 0 of the locus in gls / pls and in phased_gls
+  int32_t r0, r1, H, Hn, V, haploid, n_gl, n_pgl;
+  double hom_gl, het_gl, hom_pgl, het_pgl;   // prior + configuration term of a homozygous / heterozygous cell (genotyper.cpp:204-241; host libm)
+};
+// one (locus, sample)
+struct FieldUnit {
+  int64_t post_off;              // its [Hn x Hn] block in the posterior buffer of its pass
+  int64_t cell_off;              // its [V x V] genotype posteriors in the workspace; -1: they fit LDS
+  int32_t locus, sample, out;    // out: slot in the per-unit outputs
+  int32_t src, pass;             // slot in the total / best-pair buffers of pass 0 (first) or 1 (second)
+};
+struct FieldArgs {
+  const FieldUnit* units; const FieldLocus* loci; const int32_t* tab;
+  const double* ll; const int32_t* pool_index; const double* lp1; const double* lp2; const int32_t* label; const int32_t* map;
+  const double* post[2]; const double* stl[2]; const int* gts[2];
+  int32_t* best_gts; int32_t* counts;            // [2 nu]; n_aligned, n_snp, n_s1, n_s2: [4][nu]
+  double* scalars;                               // log_phased, log_unphased, hap_log_phased, hap_log_unphased, gl_diffs: [5][nu]
+  int64_t nu;
+  double* gls; int32_t* pls; double* pgls;       // pls, pgls: null = not wanted
+  double* cells; int32_t* read_allele;
+};
+
+constexpr int kFieldSmallH = 8;        // like the posterior passes: up to 8 haplotypes run in workgroups of one wavefront, the others of four
+constexpr int kFieldCellCap = 2048;    // largest V x V table kept in LDS (16 KB)
+
+}  // namespace ltrf
+
 namespace {
 
-using ltrf::FieldArgs;
-using ltrf::FieldLocus;
-using ltrf::FieldUnit;
+using namespace ltrf;
 
 // fastexp / fastlog of fastonebigheader.h:189-204, :321-337 in float, as ltr_genotype.cpp:24-41
 __device__ __forceinline__ float f_approx_pow2(float p) {
@@ -47,12 +79,6 @@ __device__ __forceinline__ double f_fast_lse2(double a, double b, double log_thr
 }
 __device__ __forceinline__ double f_lse2(double a, double b) {   // mathops.cpp:55-60
   return (a > b) ? a + log(1 + exp(b - a)) : b + log(1 + exp(a - b));
-}
-__device__ __forceinline__ double f_ll(const double* __restrict__ row, const int32_t* __restrict__ cmap, int a) {   // gt_ll of ltr_plan_genotype.hip
-  const int src = cmap ? cmap[a] : a;
-  double v = src >= 0 ? row[src] : -100000.0;                   // seq_stutter_genotyper.cpp:367
-  if (v < -600.0) v = -600.0;                                   // genotyper.cpp:57-58
-  return v;
 }
 // maximum over the workgroup (exact whatever the order); s_red: NT doubles
 template <int NT>
@@ -169,7 +195,7 @@ __global__ __launch_bounds__(NT) void ltr_genotype_fields_kernel(const FieldArgs
     int strand = 0;
     if (!L.haploid && ha != hb) {
       const double* row = A.ll + L.ll_off + (int64_t)A.pool_index[r] * L.H;
-      strand = (p1 + f_ll(row, cmap, ha) > p2 + f_ll(row, cmap, hb)) ? 0 : 1;      // :965-967
+      strand = (p1 + ltr_clamped_ll(row, cmap, ha) > p2 + ltr_clamped_ll(row, cmap, hb)) ? 0 : 1;      // :965-967
     }
     A.read_allele[r] = strand == 0 ? ga : gb;
     atomicAdd(&s_cnt[0], 1);
@@ -182,10 +208,7 @@ __global__ __launch_bounds__(NT) void ltr_genotype_fields_kernel(const FieldArgs
   if (tid < 4) A.counts[(int64_t)tid * A.nu + u.out] = s_cnt[tid];
 }
 
-}  // namespace
-
-namespace ltrf {
-
+// units [0, n_small) in workgroups of 64 threads, [n_small, n_small + n_large) of 256; cell_cap_*: doubles of LDS for the V x V table
 void launch_fields(hipStream_t st, const FieldArgs& a, size_t n_small, int cell_cap_small, size_t n_large, int cell_cap_large) {
   const double log_thresh = std::log(0.001);                     // LOG_THRESH, mathops.h:36
   if (n_small)
@@ -194,7 +217,149 @@ void launch_fields(hipStream_t st, const FieldArgs& a, size_t n_small, int cell_
     hipLaunchKernelGGL(ltr_genotype_fields_kernel<256>, dim3((unsigned)n_large), dim3(256), (size_t)cell_cap_large * sizeof(double), st, a, (int)n_small, log_thresh);
 }
 
-}  // namespace ltrf
+// sizes and offsets of every locus (res->f_V, f_gl_off, f_pgl_off, f_read_off; floci when the kernel will run); the table entries needed
+int64_t layout_loci(const ltr_plan* plan, const ltr_genotype_batch* gb, ltr_genotype_result* res, FieldLocus* floci) {
+  const ltr_posterior_batch* pb = gb->pb;
+  const int64_t nl = res->n_loci;
+  res->f_gl_off.assign((size_t)nl + 1, 0); res->f_pgl_off.assign((size_t)nl + 1, 0);
+  res->f_read_off.assign(pb->locus_read_off, pb->locus_read_off + nl + 1);
+  int64_t tab = 0, mo = 0;
+  for (int64_t l = 0; l < nl; ++l) {                             // (the block lists are warm from the caller's checks)
+    const LtrPruned* p = res->pruned[(size_t)l].get();
+    const ltr_haplotype_blocks* hb = p ? &p->blocks.view : gb->haps[l];
+    const int32_t S = res->S[(size_t)l], H = res->H[(size_t)l], Hn = p ? p->Hn : H, V = hb->n_alleles[res->f_block[(size_t)l]];
+    res->f_V[(size_t)l] = V;
+    if (!floci) continue;
+    FieldLocus& F = floci[(size_t)l];
+    F.ll_off = plan->locus_ll_off[(size_t)l]; F.map_off = p ? mo : -1; F.tab_off = tab;
+    F.gl_off = res->f_gl_off[(size_t)l]; F.pgl_off = res->f_pgl_off[(size_t)l];
+    F.r0 = (int32_t)pb->locus_read_off[l]; F.r1 = (int32_t)pb->locus_read_off[l + 1]; F.H = H; F.Hn = Hn; F.V = V; F.haploid = pb->haploid ? 1 : 0;
+    F.n_gl = pb->haploid ? V : V * (V + 1) / 2; F.n_pgl = pb->haploid ? V : V * V;
+    // priors (the heterozygous one of a haploid call is 0, genotyper.cpp:210) and configuration terms (:204-241) as ltr_genotype.cpp:108-111
+    double hom_prior, het_prior;
+    ltr_log_priors(Hn, pb->haploid, &hom_prior, &het_prior);
+    if (pb->haploid) het_prior = 0.0;
+    const double lH = std::log((double)Hn), lV = std::log((double)V), l2 = std::log(2.0);
+    const double gl_cfg = pb->haploid ? l2 + lH - lV : l2 + 2 * (lH - lV), pgl_cfg = pb->haploid ? lH - lV : 2 * (lH - lV);
+    F.hom_gl = hom_prior + gl_cfg; F.het_gl = het_prior + gl_cfg; F.hom_pgl = hom_prior + pgl_cfg; F.het_pgl = het_prior + pgl_cfg;
+    if (p) mo += p->Hn;
+    tab += 2 * (int64_t)Hn + V + 1;
+    res->f_gl_off[(size_t)l + 1] = F.gl_off + (int64_t)S * F.n_gl;
+    res->f_pgl_off[(size_t)l + 1] = F.pgl_off + (int64_t)S * F.n_pgl;
+  }
+  return tab;
+}
+
+// haps_to_alleles of the FINAL list (:240-248) and the haplotypes of every allele, per locus at F.tab_off; false: malformed blocks
+bool fill_tables(const ltr_genotype_batch* gb, const ltr_genotype_result* res, const FieldLocus* floci, int32_t* ftab) {
+  std::atomic<int> ferr(0);
+  ltr::parallel_for(res->n_loci, 64, [&](int64_t l) {
+    const LtrPruned* p = res->pruned[(size_t)l].get();
+    const ltr_haplotype_blocks* hb = p ? &p->blocks.view : gb->haps[l];
+    const FieldLocus& F = floci[(size_t)l];
+    std::vector<int32_t> counts; int64_t nc = 0;
+    if (ltr::haplotype_counts(hb, &counts, &nc) != LTR_OK || nc != F.Hn) { ferr.store(1); return; }
+    int32_t* h2a = ftab + F.tab_off; int32_t* first = h2a + F.Hn; int32_t* list = first + F.V + 1;
+    for (int32_t a = 0; a <= F.V; ++a) first[a] = 0;
+    for (int32_t h = 0; h < F.Hn; ++h) {
+      const int32_t a = counts[(size_t)((int64_t)h * hb->n_blocks + res->f_block[(size_t)l])];
+      if (a < 0 || a >= F.V) { ferr.store(1); return; }
+      h2a[h] = a; first[a + 1]++;
+    }
+    for (int32_t a = 0; a < F.V; ++a) first[a + 1] += first[a];
+    std::vector<int32_t> at(first, first + F.V);
+    for (int32_t h = 0; h < F.Hn; ++h) list[at[(size_t)h2a[h]]++] = h;
+  }, 16);
+  return ferr.load() == 0;
+}
+
+// units: those of up to kFieldSmallH haplotypes first (one wavefront each), then the others; a V x V table beyond LDS goes to a workspace
+struct UnitLayout { size_t n_small = 0; int64_t ncells = 0; int cap_small = 1, cap_large = 1; };
+UnitLayout layout_field_units(const ltr_genotype_result* res, const FieldLocus* floci, FieldUnit* funits) {
+  const int64_t nl = res->n_loci;
+  UnitLayout L;
+  for (int64_t l = 0; l < nl; ++l) if (floci[(size_t)l].Hn <= kFieldSmallH) L.n_small += (size_t)res->S[(size_t)l];
+  size_t ks = 0, kl = L.n_small;
+  int64_t unit2 = 0;                                             // first unit of a pruned locus in the second pass
+  for (int64_t l = 0; l < nl; ++l) {
+    const LtrPruned* p = res->pruned[(size_t)l].get();
+    const FieldLocus& F = floci[(size_t)l];
+    const bool small = F.Hn <= kFieldSmallH;
+    const int64_t vv = (int64_t)F.V * F.V;
+    for (int32_t s = 0; s < res->S[(size_t)l]; ++s) {
+      FieldUnit& u = funits[small ? ks++ : kl++];
+      u.locus = (int32_t)l; u.sample = s; u.out = (int32_t)(res->unit_off[(size_t)l] + s);
+      u.pass = p ? 1 : 0; u.src = p ? (int32_t)(unit2 + s) : u.out;
+      u.post_off = (p ? p->post_off : res->post1_off[(size_t)l]) + (int64_t)s * F.Hn * F.Hn;
+      if (vv > kFieldCellCap) { u.cell_off = L.ncells; L.ncells += vv; }
+      else { u.cell_off = -1; int& cap = small ? L.cap_small : L.cap_large; cap = std::max(cap, (int)vv); }
+    }
+    if (p) unit2 += res->S[(size_t)l];
+  }
+  return L;
+}
+
+}  // namespace
+
+void ltr_plan_fields_empty(const ltr_genotype_batch* gb, ltr_genotype_result* res) {
+  layout_loci(nullptr, gb, res, nullptr);
+  res->f_i32.reset(new int32_t[std::max<size_t>((size_t)gb->pb->n_reads, 1)]()); res->f_f64.reset(new double[1]());
+}
+
+int ltr_plan_fields_stage(ltr_plan* plan, const ltr_genotype_batch* gb, const ltr_fields_request* fr, ltr_genotype_result* res,
+                          const DevReads& rd, const int32_t* d_map, const DevPass pass[2], DevLease& lease) {
+  ltr_ctx* ctx = plan->ctx;
+  hipStream_t st = lease.st;
+  const int64_t nl = res->n_loci;
+  const size_t nu = (size_t)res->unit_off[(size_t)nl], nr = (size_t)gb->pb->n_reads;
+  FieldLocus* floci = lease.host<FieldLocus>((size_t)nl);
+  const size_t ntab = (size_t)layout_loci(plan, gb, res, floci);
+  int32_t* ftab = lease.host<int32_t>(ntab);
+  if (!fill_tables(gb, res, floci, ftab)) { ltr::set_error(ctx, "ltr_plan_genotype_fields: malformed haplotype blocks"); return LTR_ERR_INVALID; }
+  FieldUnit* funits = lease.host<FieldUnit>(nu);
+  const UnitLayout ul = layout_field_units(res, floci, funits);
+  const int64_t ngl = res->f_gl_off[(size_t)nl], npgl = res->f_pgl_off[(size_t)nl];
+  const size_t ni32 = 6 * nu + nr;
+  res->f_i32.reset(new int32_t[ni32]); res->f_f64.reset(new double[5 * nu]);
+  if (fr->want_gls) res->f_gls.reset(new double[(size_t)std::max<int64_t>(ngl, 1)]);
+  if (fr->want_pls) res->f_pls.reset(new int32_t[(size_t)std::max<int64_t>(ngl, 1)]);
+  if (fr->want_phased_gls) res->f_pgls.reset(new double[(size_t)std::max<int64_t>(npgl, 1)]);
+  FieldUnit* d_funits = nullptr; FieldLocus* d_floci = nullptr; int32_t *d_ftab = nullptr, *d_fi32 = nullptr, *d_fpls = nullptr;
+  double *d_ff64 = nullptr, *d_fgls = nullptr, *d_fpgls = nullptr, *d_fcells = nullptr;
+  DEV_TRY(ctx, lease.alloc(&d_funits, nu * sizeof(FieldUnit)));
+  DEV_TRY(ctx, lease.alloc(&d_floci, (size_t)nl * sizeof(FieldLocus)));
+  DEV_TRY(ctx, lease.alloc(&d_ftab, ntab * 4));
+  DEV_TRY(ctx, lease.alloc(&d_fi32, ni32 * 4));
+  DEV_TRY(ctx, lease.alloc(&d_ff64, 5 * nu * 8));
+  DEV_TRY(ctx, lease.alloc(&d_fgls, (size_t)std::max<int64_t>(ngl, 1) * 8));
+  if (fr->want_pls) DEV_TRY(ctx, lease.alloc(&d_fpls, (size_t)std::max<int64_t>(ngl, 1) * 4));
+  if (fr->want_phased_gls) DEV_TRY(ctx, lease.alloc(&d_fpgls, (size_t)std::max<int64_t>(npgl, 1) * 8));
+  if (ul.ncells) DEV_TRY(ctx, lease.alloc(&d_fcells, (size_t)ul.ncells * 8));
+  DEV_TRY(ctx, hipMemcpyAsync(d_funits, funits, nu * sizeof(FieldUnit), hipMemcpyHostToDevice, st));
+  DEV_TRY(ctx, hipMemcpyAsync(d_floci, floci, (size_t)nl * sizeof(FieldLocus), hipMemcpyHostToDevice, st));
+  DEV_TRY(ctx, hipMemcpyAsync(d_ftab, ftab, ntab * 4, hipMemcpyHostToDevice, st));
+  // a unit without an optimal pair (best_gts = -1) writes nothing else: its numbers read 0, not what the pool held before
+  DEV_TRY(ctx, hipMemsetAsync(d_fi32, 0, 6 * nu * 4, st));
+  DEV_TRY(ctx, hipMemsetAsync(d_ff64, 0, 5 * nu * 8, st));
+  if (ngl) DEV_TRY(ctx, hipMemsetAsync(d_fgls, 0, (size_t)ngl * 8, st));
+  if (fr->want_pls && ngl) DEV_TRY(ctx, hipMemsetAsync(d_fpls, 0, (size_t)ngl * 4, st));
+  if (fr->want_phased_gls && npgl) DEV_TRY(ctx, hipMemsetAsync(d_fpgls, 0, (size_t)npgl * 8, st));
+  if (nr) DEV_TRY(ctx, hipMemsetAsync(d_fi32 + 6 * nu, 0xff, nr * 4, st));   // (a read whose label no unit claims cannot exist: the labels were checked; -1 would be refused by the formatter)
+  FieldArgs a;
+  a.units = d_funits; a.loci = d_floci; a.tab = d_ftab;
+  a.ll = plan->last_out; a.pool_index = rd.pool_index; a.lp1 = rd.lp1; a.lp2 = rd.lp2; a.label = rd.label; a.map = d_map;
+  for (int k = 0; k < 2; ++k) { a.post[k] = pass[k].post; a.stl[k] = pass[k].stl; a.gts[k] = pass[k].gts; }
+  a.best_gts = d_fi32; a.counts = d_fi32 + 2 * nu; a.scalars = d_ff64; a.nu = (int64_t)nu;
+  a.gls = d_fgls; a.pls = d_fpls; a.pgls = d_fpgls; a.cells = d_fcells; a.read_allele = d_fi32 + 6 * nu;
+  launch_fields(st, a, ul.n_small, ul.cap_small, nu - ul.n_small, ul.cap_large);
+  DEV_TRY(ctx, hipGetLastError());
+  DEV_TRY(ctx, hipMemcpyAsync(res->f_i32.get(), d_fi32, ni32 * 4, hipMemcpyDeviceToHost, st));
+  DEV_TRY(ctx, hipMemcpyAsync(res->f_f64.get(), d_ff64, 5 * nu * 8, hipMemcpyDeviceToHost, st));
+  if (fr->want_gls && ngl) DEV_TRY(ctx, hipMemcpyAsync(res->f_gls.get(), d_fgls, (size_t)ngl * 8, hipMemcpyDeviceToHost, st));
+  if (fr->want_pls && ngl) DEV_TRY(ctx, hipMemcpyAsync(res->f_pls.get(), d_fpls, (size_t)ngl * 4, hipMemcpyDeviceToHost, st));
+  if (fr->want_phased_gls && npgl) DEV_TRY(ctx, hipMemcpyAsync(res->f_pgls.get(), d_fpgls, (size_t)npgl * 8, hipMemcpyDeviceToHost, st));
+  return LTR_OK;
+}
 
 extern "C" {
 

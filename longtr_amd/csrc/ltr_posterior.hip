@@ -4,7 +4,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "ltr_ctx.h"
+#include "ltr_posterior_common.h"
 
 using namespace ltrp;                            // class table, Rules, classify_pair, sort_by_class (ltr_plan.h)
 
@@ -40,9 +40,9 @@ __global__ void ltr_clamp_kernel(double* ll, int64_t count) {
   if (i < count && ll[i] < -600.0) ll[i] = -600.0;
 }
 
-// per sample: log_sum_exp normalise (genotyper.cpp:67-75, mathops.cpp:47-53) + argmax (:85-100).
-// Single thread per sample on purpose: the sum must run in index order to match the
-// reference's rounding, and H*H is tiny.
+// per sample: log_sum_exp normalise (genotyper.cpp:67-75, mathops.cpp:47-53) + argmax (:85-100), one thread each.
+// The text of ltr_normalise_argmax (ltr_posterior_common.h), kept in place: with H uniform over the launch the inlined routine
+// compiles to a different branch layout, and the counter summaries of profiles/ are matched to this unit's device code.
 __global__ void ltr_posterior_finish_kernel(int S, int H, double* __restrict__ post,
                                             double* __restrict__ stl, int* __restrict__ gts) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
@@ -95,31 +95,15 @@ __global__ void ltr_posterior_batch_kernel(const PostUnit* __restrict__ units, c
   }
 }
 
-// normalise + argmax per unit (index-ordered sum, first maximum: genotyper.cpp:67-75, :85-100)
+// normalise + argmax per unit
 __global__ void ltr_posterior_batch_finish_kernel(int n_units, const PostUnit* __restrict__ units, double* __restrict__ post,
                                                   double* __restrict__ stl, int* __restrict__ gts) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n_units) return;
-  const int H = units[k].H, nd = H * H;
-  double* p = post + units[k].post_off;
-  double mx = p[0];
-  for (int i = 1; i < nd; ++i) if (mx < p[i]) mx = p[i];
-  double tot = 0.0;
-  for (int i = 0; i < nd; ++i) tot += exp(p[i] - mx);
-  const double total = mx + log(tot);
-  stl[k] = total;
-  double best = -1.7976931348623157e308; int b1 = -1, b2 = -1;
-  for (int i = 0; i < nd; ++i) {
-    const double v = p[i] - total;
-    p[i] = v;
-    if (v > best) { best = v; b1 = i / H; b2 = i % H; }
-  }
-  gts[2 * k] = b1; gts[2 * k + 1] = b2;
+  ltr_normalise_argmax(post + units[k].post_off, units[k].H, stl, gts, k);
 }
 
 }  // namespace
-
-#define P_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { ltr::set_error(ctx, std::string(#call) + ": " + hipGetErrorString(e_)); rc = LTR_ERR_HIP; goto done; } } while (0)
 
 extern "C" {
 
@@ -130,54 +114,43 @@ int ltr_posteriors(ltr_ctx* ctx, int32_t S, int32_t R, int32_t H,
   if (!ctx || S <= 0 || R < 0 || H <= 0 || !ll || !lp1 || !lp2 || !sample_label || !post || !stl) return LTR_ERR_INVALID;
   ltr::TimedCall timed(ctx, ltr::kTimerPosterior);             // total_posterior_time_, genotyper.cpp:46,:80-81
   std::lock_guard<std::mutex> lk(ctx->mu);
+  LTR_GUARD_BEGIN
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   for (int32_t r = 0; r < R; ++r) if (sample_label[r] < 0 || sample_label[r] >= S) { ltr::set_error(ctx, "sample label out of range"); return LTR_ERR_INVALID; }
-  // int_log(v) == log(v) (mathops.cpp:14-22); priors of genotyper.cpp:21-33
-  const double lH = std::log((double)H), lH1 = std::log((double)(H + 1));
-  const double homoz = haploid ? -lH : std::log(2.0) - lH - lH1;
-  const double hetz = haploid ? -1.7976931348623157e308 / 2 : -lH - lH1;
+  double homoz, hetz;
+  ltr_log_priors(H, haploid, &homoz, &hetz);
   const size_t nll = (size_t)R * H, npost = (size_t)S * H * H;
   double *d_ll = nullptr, *d_p1 = nullptr, *d_p2 = nullptr, *d_post = nullptr, *d_stl = nullptr;
   int *d_lab = nullptr, *d_gts = nullptr;
-  int rc = LTR_OK;
   hipStream_t st = ctx->stream;
-  P_TRY(ctx->pool.alloc((void**)&d_ll, std::max<size_t>(nll, 1) * 8));
-  P_TRY(ctx->pool.alloc((void**)&d_p1, std::max<size_t>(R, 1) * 8));
-  P_TRY(ctx->pool.alloc((void**)&d_p2, std::max<size_t>(R, 1) * 8));
-  P_TRY(ctx->pool.alloc((void**)&d_lab, std::max<size_t>(R, 1) * 4));
-  P_TRY(ctx->pool.alloc((void**)&d_post, npost * 8));
-  P_TRY(ctx->pool.alloc((void**)&d_stl, (size_t)S * 8));
-  P_TRY(ctx->pool.alloc((void**)&d_gts, (size_t)S * 8));
+  DevLease lease(ctx->pool, st);                               // (every host buffer the copies touch is the caller's or the lease's)
+  DEV_TRY(ctx, lease.alloc(&d_ll, std::max<size_t>(nll, 1) * 8));
+  DEV_TRY(ctx, lease.alloc(&d_p1, std::max<size_t>(R, 1) * 8));
+  DEV_TRY(ctx, lease.alloc(&d_p2, std::max<size_t>(R, 1) * 8));
+  DEV_TRY(ctx, lease.alloc(&d_lab, std::max<size_t>(R, 1) * 4));
+  DEV_TRY(ctx, lease.alloc(&d_post, npost * 8));
+  DEV_TRY(ctx, lease.alloc(&d_stl, (size_t)S * 8));
+  DEV_TRY(ctx, lease.alloc(&d_gts, (size_t)S * 8));
   if (R > 0) {
-    P_TRY(hipMemcpyAsync(d_ll, ll, nll * 8, hipMemcpyHostToDevice, st));
-    P_TRY(hipMemcpyAsync(d_p1, lp1, (size_t)R * 8, hipMemcpyHostToDevice, st));
-    P_TRY(hipMemcpyAsync(d_p2, lp2, (size_t)R * 8, hipMemcpyHostToDevice, st));
-    P_TRY(hipMemcpyAsync(d_lab, sample_label, (size_t)R * 4, hipMemcpyHostToDevice, st));
+    DEV_TRY(ctx, hipMemcpyAsync(d_ll, ll, nll * 8, hipMemcpyHostToDevice, st));
+    DEV_TRY(ctx, hipMemcpyAsync(d_p1, lp1, (size_t)R * 8, hipMemcpyHostToDevice, st));
+    DEV_TRY(ctx, hipMemcpyAsync(d_p2, lp2, (size_t)R * 8, hipMemcpyHostToDevice, st));
+    DEV_TRY(ctx, hipMemcpyAsync(d_lab, sample_label, (size_t)R * 4, hipMemcpyHostToDevice, st));
   }
   hipLaunchKernelGGL(ltr_posterior_kernel, dim3((unsigned)S), dim3(256), 0, st, S, R, H, d_ll, d_p1, d_p2, d_lab, homoz, hetz, d_post);
   if (nll) hipLaunchKernelGGL(ltr_clamp_kernel, dim3((unsigned)((nll + 255) / 256)), dim3(256), 0, st, d_ll, (int64_t)nll);
   hipLaunchKernelGGL(ltr_posterior_finish_kernel, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st, S, H, d_post, d_stl, d_gts);
-  P_TRY(hipGetLastError());
-  if (nll) P_TRY(hipMemcpyAsync(ll, d_ll, nll * 8, hipMemcpyDeviceToHost, st));
-  P_TRY(hipMemcpyAsync(post, d_post, npost * 8, hipMemcpyDeviceToHost, st));
-  P_TRY(hipMemcpyAsync(stl, d_stl, (size_t)S * 8, hipMemcpyDeviceToHost, st));
-  {
-    std::vector<int32_t> g((size_t)2 * S);
-    P_TRY(hipMemcpyAsync(g.data(), d_gts, (size_t)S * 8, hipMemcpyDeviceToHost, st));
-    P_TRY(hipStreamSynchronize(st));
-    if (gts) std::memcpy(gts, g.data(), (size_t)S * 8);
-  }
+  DEV_TRY(ctx, hipGetLastError());
+  if (nll) DEV_TRY(ctx, hipMemcpyAsync(ll, d_ll, nll * 8, hipMemcpyDeviceToHost, st));
+  DEV_TRY(ctx, hipMemcpyAsync(post, d_post, npost * 8, hipMemcpyDeviceToHost, st));
+  DEV_TRY(ctx, hipMemcpyAsync(stl, d_stl, (size_t)S * 8, hipMemcpyDeviceToHost, st));
+  int32_t* g = lease.host<int32_t>((size_t)2 * S);             // (gts may be null; taken here, behind the queued work)
+  DEV_TRY(ctx, hipMemcpyAsync(g, d_gts, (size_t)S * 8, hipMemcpyDeviceToHost, st));
+  DEV_TRY(ctx, lease.drain());
+  if (gts) std::memcpy(gts, g, (size_t)S * 8);
   if (total_ll) { double t = 0.0; for (int32_t s = 0; s < S; ++s) t += stl[s]; *total_ll = t; }   // sum(), genotyper.cpp:78
-done:
-  if (rc != LTR_OK) (void)hipStreamSynchronize(st);            // (buffers go back to the context's pool: nothing may still use them)
-  ctx->pool.release(d_ll);
-  ctx->pool.release(d_p1);
-  ctx->pool.release(d_p2);
-  ctx->pool.release(d_lab);
-  ctx->pool.release(d_post);
-  ctx->pool.release(d_stl);
-  ctx->pool.release(d_gts);
-  return rc;
+  return LTR_OK;
+  LTR_GUARD_END(ctx)
 }
 
 // Genotyper::calc_log_sample_posteriors + get_optimal_haplotypes for EVERY locus of a resident
@@ -190,8 +163,9 @@ int ltr_plan_posteriors(ltr_plan* plan, const ltr_posterior_batch* pb, double* p
   if (pb->n_loci != (int64_t)plan->locus_P.size()) { ltr::set_error(ctx, "posterior batch and plan disagree on the number of loci"); return LTR_ERR_INVALID; }
   ltr::TimedCall timed(ctx, ltr::kTimerPosterior);             // total_posterior_time_, genotyper.cpp:46,:80-81
   std::lock_guard<std::mutex> lk(ctx->mu);
+  LTR_GUARD_BEGIN
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  std::vector<PostUnit> units;
+  std::vector<PostUnit> units;                                 // (before the lease: a queued copy reads it)
   int64_t post_off = 0;
   for (int64_t l = 0; l < pb->n_loci; ++l) {
     const int64_t r0 = pb->locus_read_off[l], r1 = pb->locus_read_off[l + 1];
@@ -201,60 +175,38 @@ int ltr_plan_posteriors(ltr_plan* plan, const ltr_posterior_batch* pb, double* p
       if (pb->pool_index[r] < 0 || pb->pool_index[r] >= P || pb->sample_label[r] < 0 || pb->sample_label[r] >= S) {
         ltr::set_error(ctx, "pool index / sample label out of range"); return LTR_ERR_INVALID;
       }
-    // int_log(v) == log(v) (mathops.cpp:14-22); priors of genotyper.cpp:21-33
-    const double lH = std::log((double)H), lH1 = std::log((double)(H + 1));
     for (int32_t sm = 0; sm < S; ++sm) {
       PostUnit u;
       u.ll_off = plan->locus_ll_off[(size_t)l]; u.post_off = post_off; u.r0 = (int32_t)r0; u.r1 = (int32_t)r1; u.H = H; u.sample = sm;
-      u.homoz = pb->haploid ? -lH : std::log(2.0) - lH - lH1;
-      u.hetz = pb->haploid ? -1.7976931348623157e308 / 2 : -lH - lH1;
+      ltr_log_priors(H, pb->haploid, &u.homoz, &u.hetz);
       units.push_back(u);
       post_off += (int64_t)H * H;
     }
   }
-  const size_t nu = units.size(), nr = (size_t)pb->n_reads;
+  const size_t nu = units.size();
   if (nu == 0) return LTR_OK;
-  PostUnit* d_units = nullptr; int32_t *d_pool = nullptr, *d_lab = nullptr; int* d_gts = nullptr;
-  double *d_p1 = nullptr, *d_p2 = nullptr, *d_post = nullptr, *d_stl = nullptr;
-  int rc = LTR_OK;
+  PostUnit* d_units = nullptr; int* d_gts = nullptr;
+  double *d_post = nullptr, *d_stl = nullptr;
+  DevReads rd;
   hipStream_t st = plan->last_stream;
-  P_TRY(ctx->pool.alloc((void**)&d_units, nu * sizeof(PostUnit)));
-  P_TRY(ctx->pool.alloc((void**)&d_pool, std::max<size_t>(nr, 1) * 4));
-  P_TRY(ctx->pool.alloc((void**)&d_lab, std::max<size_t>(nr, 1) * 4));
-  P_TRY(ctx->pool.alloc((void**)&d_p1, std::max<size_t>(nr, 1) * 8));
-  P_TRY(ctx->pool.alloc((void**)&d_p2, std::max<size_t>(nr, 1) * 8));
-  P_TRY(ctx->pool.alloc((void**)&d_post, (size_t)post_off * 8));
-  P_TRY(ctx->pool.alloc((void**)&d_stl, nu * 8));
-  P_TRY(ctx->pool.alloc((void**)&d_gts, nu * 8));
-  P_TRY(hipMemcpyAsync(d_units, units.data(), nu * sizeof(PostUnit), hipMemcpyHostToDevice, st));
-  if (nr) {
-    P_TRY(hipMemcpyAsync(d_pool, pb->pool_index, nr * 4, hipMemcpyHostToDevice, st));
-    P_TRY(hipMemcpyAsync(d_lab, pb->sample_label, nr * 4, hipMemcpyHostToDevice, st));
-    P_TRY(hipMemcpyAsync(d_p1, pb->log_p1, nr * 8, hipMemcpyHostToDevice, st));
-    P_TRY(hipMemcpyAsync(d_p2, pb->log_p2, nr * 8, hipMemcpyHostToDevice, st));
-  }
-  hipLaunchKernelGGL(ltr_posterior_batch_kernel, dim3((unsigned)nu), dim3(128), 0, st, d_units, plan->last_out, d_pool, d_p1, d_p2, d_lab, d_post);
+  DevLease lease(ctx->pool, st);
+  DEV_TRY(ctx, lease.alloc(&d_units, nu * sizeof(PostUnit)));
+  DEV_TRY(ctx, hipMemcpyAsync(d_units, units.data(), nu * sizeof(PostUnit), hipMemcpyHostToDevice, st));
+  if (int rc = upload_reads(ctx, lease, pb, &rd)) return rc;
+  DEV_TRY(ctx, lease.alloc(&d_post, (size_t)post_off * 8));
+  DEV_TRY(ctx, lease.alloc(&d_stl, nu * 8));
+  DEV_TRY(ctx, lease.alloc(&d_gts, nu * 8));
+  hipLaunchKernelGGL(ltr_posterior_batch_kernel, dim3((unsigned)nu), dim3(128), 0, st, d_units, plan->last_out, rd.pool_index, rd.lp1, rd.lp2, rd.label, d_post);
   hipLaunchKernelGGL(ltr_posterior_batch_finish_kernel, dim3((unsigned)((nu + 63) / 64)), dim3(64), 0, st, (int)nu, d_units, d_post, d_stl, d_gts);
-  P_TRY(hipGetLastError());
-  P_TRY(hipMemcpyAsync(post, d_post, (size_t)post_off * 8, hipMemcpyDeviceToHost, st));
-  P_TRY(hipMemcpyAsync(sample_total_ll, d_stl, nu * 8, hipMemcpyDeviceToHost, st));
-  {
-    std::vector<int32_t> g(2 * nu);
-    P_TRY(hipMemcpyAsync(g.data(), d_gts, nu * 8, hipMemcpyDeviceToHost, st));
-    P_TRY(hipStreamSynchronize(st));
-    if (gts) std::memcpy(gts, g.data(), nu * 8);
-  }
-done:
-  if (rc != LTR_OK) (void)hipStreamSynchronize(st);
-  ctx->pool.release(d_units);
-  ctx->pool.release(d_pool);
-  ctx->pool.release(d_lab);
-  ctx->pool.release(d_p1);
-  ctx->pool.release(d_p2);
-  ctx->pool.release(d_post);
-  ctx->pool.release(d_stl);
-  ctx->pool.release(d_gts);
-  return rc;
+  DEV_TRY(ctx, hipGetLastError());
+  DEV_TRY(ctx, hipMemcpyAsync(post, d_post, (size_t)post_off * 8, hipMemcpyDeviceToHost, st));
+  DEV_TRY(ctx, hipMemcpyAsync(sample_total_ll, d_stl, nu * 8, hipMemcpyDeviceToHost, st));
+  int32_t* g = lease.host<int32_t>(2 * nu);                    // (gts may be null; taken here, behind the queued work)
+  DEV_TRY(ctx, hipMemcpyAsync(g, d_gts, nu * 8, hipMemcpyDeviceToHost, st));
+  DEV_TRY(ctx, lease.drain());
+  if (gts) std::memcpy(gts, g, nu * 8);
+  return LTR_OK;
+  LTR_GUARD_END(ctx)
 }
 
 }  // extern "C"
