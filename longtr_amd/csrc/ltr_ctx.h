@@ -2,15 +2,14 @@
 // ltr_plan_build.hip (ltr_plan_create / _destroy), ltr_plan_run.hip (execute, fetch, statistics) and the consumers of a plan's
 // scores, ltr_posterior.hip, ltr_plan_genotype.hip, ltr_plan_fields.hip.
 // Private to those six: everything else (ltr_host.cpp, ltr_short.hip, ltr_nw.hip, ..) goes through the ltr::ctx_* accessors
-// of ltr_internal.h, which is what lets tests/host_sanitize/harness.cpp supply a context of its own.
+// of ltr_internal.h, which is what lets tests/host_sanitize/harness.cpp supply a context of its own.  The lease a call holds its
+// device blocks and events by (ltr_lease.h) is seen by these six and by ltr_short.hip and ltr_nw.hip, which hand it the context.
 #ifndef LTR_CTX_H_
 #define LTR_CTX_H_
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <map>
-#include <memory>
 #include <mutex>
 #include <set>
 #include <string>
@@ -18,89 +17,10 @@
 
 #include "ltr_internal.h"
 #include "ltr_kernels.h"
+#include "ltr_lease.h"
 #include "ltr_plan.h"
 
-// Device allocations of a context are recycled: a plan for one locus needs ten small buffers, and
-// hipMalloc / hipFree (a device-wide synchronisation each) would dominate the per-locus call.
-// Blocks up to 64 MB are rounded to a power of two and parked here on release (at most 512 MB);
-// larger ones go straight back to the runtime.
-// (RawBuf, the grow-only host array of the work arrays below: ltr_plan.h)
-struct DevPool {
-  // (sized for 288 GB of HBM: the blocks of a 10 k-locus plan -- 130 MB of reads, 180 MB of haplotype codes -- are
-  // parked too, so a pipeline of large plans never waits in hipMalloc / hipFree, which synchronise the device)
-  static constexpr size_t kMaxBlock = (size_t)2 << 30, kMaxCached = (size_t)8 << 30;
-  std::multimap<size_t, void*> idle;
-  std::map<void*, size_t> live;
-  size_t cached = 0;
-  std::mutex mu;
-  static size_t size_class(size_t n) { size_t c = 256; while (c < n) c <<= 1; return c; }
-  hipError_t alloc(void** out, size_t n) {
-    std::lock_guard<std::mutex> lk(mu);
-    size_t c = n;
-    if (n <= kMaxBlock) {
-      c = size_class(n);
-      auto it = idle.find(c);
-      if (it != idle.end()) { *out = it->second; idle.erase(it); cached -= c; live[*out] = c; return hipSuccess; }
-    }
-    hipError_t e = hipMalloc(out, c);
-    if (e == hipErrorOutOfMemory) {                             // give the parked blocks (up to 8 GB) back and try once more
-      for (auto& kv : idle) (void)hipFree(kv.second);
-      idle.clear(); cached = 0;
-      (void)hipGetLastError();
-      e = hipMalloc(out, c);
-    }
-    if (e == hipSuccess) live[*out] = c;
-    return e;
-  }
-  void release(void* p) {
-    if (!p) return;
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = live.find(p);
-    if (it == live.end()) { (void)hipFree(p); return; }
-    const size_t c = it->second;
-    live.erase(it);
-    if (c <= kMaxBlock && cached + c <= kMaxCached) { idle.emplace(c, p); cached += c; }
-    else (void)hipFree(p);
-  }
-  void clear() {
-    std::lock_guard<std::mutex> lk(mu);
-    for (auto& kv : idle) (void)hipFree(kv.second);
-    idle.clear(); cached = 0;
-  }
-};
-
-// The device blocks of ONE call on ONE stream, and the host staging memory its queued copies read or write.
-// Invariant: on every way out of the call -- a normal return, an error return, an exception on its way to LTR_GUARD_END -- the
-// stream is drained before any block goes back to the pool and before any host memory handed out here is freed.  Host memory
-// of the call's own that queued copies touch must outlive the lease: declare it BEFORE the lease (members of a per-call struct
-// with the lease last), or take it from host().
-struct DevLease {
-  DevPool& pool;
-  const hipStream_t st;
-  std::vector<void*> blocks;
-  std::vector<std::unique_ptr<char[]>> staging;
-  bool drained = false;
-  DevLease(DevPool& p, hipStream_t s) : pool(p), st(s) {}
-  DevLease(const DevLease&) = delete;
-  template <class T> hipError_t alloc(T** out, size_t bytes) {
-    blocks.push_back(nullptr);                                  // (the slot first: growing the list may throw, and must not lose a block)
-    const hipError_t e = pool.alloc(&blocks.back(), bytes);
-    *out = static_cast<T*>(blocks.back());
-    return e;
-  }
-  template <class T> T* host(size_t n) {                        // n zeroed objects
-    std::unique_ptr<char[]> m(new char[std::max<size_t>(n, 1) * sizeof(T)]());
-    staging.push_back(std::move(m));
-    return reinterpret_cast<T*>(staging.back().get());
-  }
-  // the call's last wait, after everything has been queued: the destructor does not wait again
-  hipError_t drain() { const hipError_t e = hipStreamSynchronize(st); drained = e == hipSuccess; return e; }
-  ~DevLease() {
-    if (!drained && !(blocks.empty() && staging.empty())) (void)hipStreamSynchronize(st);   // (nothing handed out: nothing queued on it)
-    for (void* p : blocks) pool.release(p);
-  }
-};
-
+// (DevPool, DevLease, DEV_TRY: ltr_lease.h.  RawBuf, the grow-only host array of the work arrays below: ltr_plan.h)
 struct ltr_ctx {
   int device = -1;
   DevPool pool;
@@ -184,8 +104,6 @@ constexpr int kHapPad = 96;                     // zero bytes either side of the
       return (e_ == hipErrorNoDevice || e_ == hipErrorInvalidDevice) ? LTR_ERR_NO_DEVICE : LTR_ERR_HIP; \
     }                                                                                        \
   } while (0)
-// ... and of the calls that hold a DevLease (which drains the stream and gives the blocks back on the way out)
-#define DEV_TRY(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { ltr::set_error(ctx, std::string(#call) + ": " + hipGetErrorString(e_)); return LTR_ERR_HIP; } } while (0)
 
 struct ltr_plan : ltrp::BatchPlan {     // (what ltrp::describe_batch decided: sizes, class ranges, per-locus layout)
   ltr_ctx* ctx = nullptr;
@@ -262,9 +180,7 @@ struct ltr_plan : ltrp::BatchPlan {     // (what ltrp::describe_batch decided: s
 #pragma GCC visibility push(hidden)
 // ltr_ctx.hip
 int build_tables(ltr_ctx* ctx, int64_t len, bool same_size = false);
-// recycled events / pinned blocks of a context (see ltr_ctx: compact plans)
-hipEvent_t ctx_take_event(ltr_ctx* ctx, bool timing);
-void ctx_give_event(ltr_ctx* ctx, hipEvent_t e, bool timing);
+// recycled pinned blocks of a context (see ltr_ctx: compact plans; its recycled events: ltr_lease.h)
 double* ctx_take_pinned(ltr_ctx* ctx, size_t bytes, size_t* cap_out, double** dev_out);
 void ctx_give_pinned(ltr_ctx* ctx, void* p);
 // ltr_plan_build.hip

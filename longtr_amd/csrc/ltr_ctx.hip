@@ -48,8 +48,6 @@ DebugKnobs ctx_debug(const ltr_ctx* ctx) { return ctx->dbg; }
 ltr_stutter_params ctx_stutter_params(const ltr_ctx* ctx) { return ctx->stutter; }
 int ctx_device(const ltr_ctx* ctx) { return ctx->device; }
 void* ctx_stream(const ltr_ctx* ctx) { return (void*)ctx->stream; }
-int ctx_pool_alloc(ltr_ctx* ctx, void** out, size_t bytes) { return (int)ctx->pool.alloc(out, bytes); }
-void ctx_pool_release(ltr_ctx* ctx, void* p) { ctx->pool.release(p); }
 void* ctx_big_scratch(ltr_ctx* ctx, size_t bytes) {
   if (bytes > ctx->big_bytes) {
     if (ctx->d_big) { (void)hipDeviceSynchronize(); (void)hipFree(ctx->d_big); ctx->d_big = nullptr; ctx->big_bytes = 0; }
@@ -281,7 +279,8 @@ int ltr_ctx_create(int device_ordinal, ltr_ctx** out) {
 
 }  // extern "C"
 
-// recycled events / pinned blocks of a context (see ltr_ctx: compact plans)
+// what a DevLease takes from its context (ltr_lease.h); recycled events / pinned blocks (see ltr_ctx: compact plans)
+DevPool& ctx_pool(ltr_ctx* ctx) { return ctx->pool; }
 hipEvent_t ctx_take_event(ltr_ctx* ctx, bool timing) {
   {
     std::lock_guard<std::mutex> lk(ctx->cache_mu);

@@ -252,8 +252,7 @@ ltr_align_params ctx_params(const ltr_ctx* ctx);
 ltr_stutter_params ctx_stutter_params(const ltr_ctx* ctx);
 int ctx_device(const ltr_ctx* ctx);
 void* ctx_stream(const ltr_ctx* ctx);      // hipStream_t
-int ctx_pool_alloc(ltr_ctx* ctx, void** out, size_t bytes);   // device memory from the context's pool; 0 = ok, else a hipError_t
-void ctx_pool_release(ltr_ctx* ctx, void* p);
+// (device memory of the context's pool and its recycled events: through a DevLease, ltr_lease.h)
 void* ctx_big_scratch(ltr_ctx* ctx, size_t bytes);   // one grow-only device block kept by the context (NW trace); NULL = out of memory; one user at a time
 std::unique_lock<std::mutex> ctx_call_lock(ltr_ctx* ctx);   // held for a whole ltr_calc_hap_aln_probs / haplotype-alignment call: they stage in the two arrays below / in ctx_big_scratch
 uint8_t* ctx_host_bytes(ltr_ctx* ctx, int which, size_t bytes);   // one of four grow-only staging arrays kept by the context (uninitialised)

@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "ltr_internal.h"
+#include "ltr_lease.h"
 
 namespace {
 
@@ -356,6 +357,255 @@ void adjust_indels(std::string& ref_al, std::string& alt_al, int32_t ref_pos, co
   }
 }
 
+// ---- ltr_haplotype_align_to_ref in stages over one per-call struct ----
+constexpr int kClasses = 6;                                     // launch classes: strip widths 4, 8, 12, 16, 20 + the workgroup kernel
+// (every even width 4 .. 20 -- nine classes, fuller lanes -- was tried on MI355X, same workload: kernels 10.3 ms, no change, and
+// the widths that are not multiples of four failed the parity test (trace words of a partly filled last word): not kept)
+
+// The ORDER of the members carries the invariant of DevLease (ltr_lease.h): the host memory queued copies read or write and the
+// lock the context's trace block and staging bytes are borrowed under come first, the lease last -- on every way out the streams
+// are drained before that memory is freed, and the lock is released after the drain.
+struct NwCall {
+  std::vector<NwTask> tasks;
+  std::vector<int32_t> ref_pos0, str_pos;                      // adjust_indels: blocks_[0]->start(), blocks_[1]->start()
+  std::vector<uint8_t> seqs;
+  int64_t out_bytes = 0;
+  std::vector<int32_t> cls_tasks[kClasses], index, h_len;
+  int32_t cls_max_l2[kClasses] = {0}, wg_max_l1 = 1, wg_max_l2 = 1;
+  int64_t cls_grid[kClasses] = {0}, cls_stride[kClasses] = {0}, cls_off[kClasses] = {0}, cls_first[kClasses + 1] = {0}, trace_bytes = 256;
+  uint8_t* h_out = nullptr;                                    // (pinned staging of the context: the download goes over the DMA engines)
+  const bool dbg; const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();   // ltr_ctx_set_debug "trace": a timestamped phase profile on stderr
+  std::unique_lock<std::mutex> big_lock;                        // (taken where the context's trace block is borrowed)
+  uint8_t* d_out = nullptr; int32_t* d_len = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;                      // device time of the kernels (ltr_timers.nw_kernel_ms)
+  DevLease lease;
+  explicit NwCall(ltr_ctx* ctx) : dbg(ltr::ctx_debug(ctx).trace != 0), lease(ctx, (hipStream_t)ltr::ctx_stream(ctx)) {}
+  void trace(const char* what) const {
+    if (dbg) std::fprintf(stderr, "[ltr] haplotype_align_to_ref %8.2f ms: %s\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), what);
+  }
+};
+
+// tasks: (reference haplotype, haplotype k) for every haplotype, sequences pooled.  Two passes: sizes and offsets in locus
+// order (serial, a few integers per haplotype), then the bytes on all host cores (20 MB per 3000 config-3 loci)
+int nw_tasks(ltr_ctx* ctx, const ltr_haplotype_blocks* const* haps, int64_t n_loci, NwCall& c) {
+  std::vector<NwTask>& tasks = c.tasks;
+  std::vector<int64_t> locus_task((size_t)n_loci + 1, 0);
+  std::vector<std::vector<int32_t>> locus_counts((size_t)n_loci);
+  int64_t pool_bytes = 64;                                     // (padded: the wavefront kernel streams rows without clamping)
+  for (int64_t l = 0; l < n_loci; ++l) {
+    const ltr_haplotype_blocks* h = haps[l];
+    if (!h || h->n_blocks != 3) { ltr::set_error(ctx, "ltr_haplotype_align_to_ref: a haplotype needs three blocks (Haplotype::adjust_indels asserts it)"); return LTR_ERR_INVALID; }
+    std::vector<int32_t>& counts = locus_counts[(size_t)l];
+    int64_t H = 0;
+    const int rc = ltr::haplotype_counts(h, &counts, &H);
+    if (rc != LTR_OK) return rc;
+    const int64_t ref_off = pool_bytes;
+    int64_t ref_len = 0;
+    for (int64_t k = 0; k < H; ++k) {
+      int64_t len = 0, slot = 0;
+      for (int b = 0; b < h->n_blocks; ++b) {
+        const int64_t a = slot + counts[(size_t)(k * h->n_blocks + b)];
+        len += h->allele_off[a + 1] - h->allele_off[a];
+        slot += h->n_alleles[b];
+      }
+      if (k == 0) ref_len = len;
+      if (ref_len < 1 || len < 1 || ref_len > (1 << 20) || len > (1 << 20)) { ltr::set_error(ctx, "empty or oversized haplotype"); return LTR_ERR_INVALID; }
+      NwTask t;
+      t.ref_off = ref_off; t.alt_off = pool_bytes; t.L1 = (int32_t)ref_len; t.L2 = (int32_t)len; t.out_off = c.out_bytes;
+      pool_bytes += len;
+      c.out_bytes += ref_len + len;
+      tasks.push_back(t);
+      c.ref_pos0.push_back(h->block_start[0]); c.str_pos.push_back(h->block_start[1]);
+    }
+    locus_task[(size_t)l + 1] = (int64_t)tasks.size();
+  }
+  c.seqs.assign((size_t)pool_bytes + 128, 0);
+  ltr::parallel_for(n_loci, 64, [&](int64_t l) {
+    const ltr_haplotype_blocks* h = haps[l];
+    const std::vector<int32_t>& counts = locus_counts[(size_t)l];
+    for (int64_t t = locus_task[(size_t)l]; t < locus_task[(size_t)l + 1]; ++t) {
+      const int64_t k = t - locus_task[(size_t)l];
+      uint8_t* dst = c.seqs.data() + tasks[(size_t)t].alt_off;
+      int64_t slot = 0;
+      for (int b = 0; b < h->n_blocks; ++b) {
+        const int64_t a = slot + counts[(size_t)(k * h->n_blocks + b)];
+        const int64_t len = h->allele_off[a + 1] - h->allele_off[a];
+        std::memcpy(dst, h->allele_bytes + h->allele_off[a], (size_t)len);
+        dst += len; slot += h->n_alleles[b];
+      }
+    }
+  }, 16);
+  c.trace("sequences pooled");
+  return LTR_OK;
+}
+
+// Launch classes: references of up to 64 x 20 bases take the wavefront kernel (strip width 4 .. 20), longer ones the
+// workgroup-per-pair kernel.  Every class has a region of its own in the trace block and a stream of its own: the launches run side
+// by side, widest strips (longest pairs) first, and inside a class the pairs are popped longest first -- a pair is 1 - 3 ms of one
+// wavefront and a class of a 3000-locus call a handful of pairs per resident wavefront, so a launch on its own ends in a tail as
+// long as a pair with most of the GPU idle (rocprofv3, round 3: VALU issue 0.35 - 0.65 per launch).  Measured on MI355X, 21 k
+// haplotypes of 3000 config-3 loci, kernels first to last: one stream, task order 14.0 ms; profiles/r05/nw_rate.log.
+void nw_classes(NwCall& c, int n_cu) {
+  const std::vector<NwTask>& tasks = c.tasks;
+  for (int64_t k = 0; k < (int64_t)tasks.size(); ++k) {
+    const int w = (tasks[(size_t)k].L1 + 63) / 64;
+    const int cl = (w <= kNwWaveMaxW) ? (std::max(w, 1) + 3) / 4 - 1 : kClasses - 1;
+    c.cls_tasks[cl].push_back((int32_t)k);
+    c.cls_max_l2[cl] = std::max(c.cls_max_l2[cl], tasks[(size_t)k].L2);
+    if (cl == kClasses - 1) { c.wg_max_l1 = std::max(c.wg_max_l1, tasks[(size_t)k].L1); c.wg_max_l2 = std::max(c.wg_max_l2, tasks[(size_t)k].L2); }
+  }
+  constexpr int64_t kTraceCap = (int64_t)16 << 30;              // of the context's trace block, all classes together
+  // longest first inside a class: rows of the alternate, then the reference's length, ties in task order (the classes side by side
+  // on the host cores, plain keys: a comparator that looks the tasks up was 1.1 ms for 21 k haplotypes)
+  ltr::parallel_for(kClasses, 1, [&](int64_t cl) {
+    struct Key { int32_t l2, l1, task; };
+    std::vector<Key> keys; keys.reserve(c.cls_tasks[cl].size());
+    for (const int32_t t : c.cls_tasks[cl]) keys.push_back({tasks[(size_t)t].L2, tasks[(size_t)t].L1, t});
+    std::sort(keys.begin(), keys.end(), [](const Key& x, const Key& y) { return x.l2 != y.l2 ? x.l2 > y.l2 : (x.l1 != y.l1 ? x.l1 > y.l1 : x.task < y.task); });
+    for (size_t i = 0; i < keys.size(); ++i) c.cls_tasks[cl][i] = keys[i].task;
+  }, 1);
+  for (int pass = 0; pass < 2; ++pass) {
+    // (pass 1, only when the regions of pass 0 add up to more than the cap: every class with its share of the wavefronts)
+    const double shrink = pass == 0 ? 1.0 : (double)kTraceCap / (double)c.trace_bytes * 0.98;
+    if (pass == 1 && c.trace_bytes <= kTraceCap) break;
+    c.trace_bytes = 256;
+    for (int cl = 0; cl < kClasses; ++cl) {
+      if (pass == 0) {
+        c.cls_first[cl + 1] = c.cls_first[cl] + (int64_t)c.cls_tasks[cl].size();
+        c.index.insert(c.index.end(), c.cls_tasks[cl].begin(), c.cls_tasks[cl].end());
+      }
+      if (c.cls_tasks[cl].empty()) continue;
+      c.cls_off[cl] = c.trace_bytes;
+      if (cl < kClasses - 1) {
+        const int W = 4 * (cl + 1);
+        c.cls_stride[cl] = (((int64_t)(c.cls_max_l2[cl] + 64) * 64 * W) + 255) / 256 * 256;       // per wavefront
+        int64_t waves = std::min<int64_t>((int64_t)c.cls_tasks[cl].size(), (int64_t)n_cu * 12);
+        waves = std::max<int64_t>(1, std::min<int64_t>((int64_t)((double)waves * shrink), ((int64_t)6 << 30) / c.cls_stride[cl]));
+        c.cls_grid[cl] = (waves + kNwWaveBlock - 1) / kNwWaveBlock;
+        c.trace_bytes += c.cls_grid[cl] * kNwWaveBlock * c.cls_stride[cl];
+      } else {
+        c.cls_stride[cl] = (((int64_t)(c.wg_max_l1 + 1) * (c.wg_max_l2 + 1)) + 255) / 256 * 256;   // per workgroup
+        int64_t g = std::min<int64_t>((int64_t)c.cls_tasks[cl].size(), (int64_t)n_cu * 2);    // LDS (54 KB) admits two workgroups per CU
+        c.cls_grid[cl] = std::max<int64_t>(1, std::min<int64_t>((int64_t)std::max(1.0, (double)g * shrink), ((int64_t)6 << 30) / c.cls_stride[cl]));
+        c.trace_bytes += c.cls_grid[cl] * c.cls_stride[cl];
+      }
+    }
+  }
+  c.trace("classes sorted");
+}
+
+// device stage: blocks, the borrowed trace block, uploads, the mask kernel, then the class launches side by side -- forked from
+// the context's stream behind ev0, every side stream joined back into it by an event
+int nw_device(ltr_ctx* ctx, NwCall& c, int n_cu) {
+  DevLease& lease = c.lease; const hipStream_t st = lease.st;
+  const int64_t nt = (int64_t)c.tasks.size();
+  const int64_t diag_stride = (c.wg_max_l2 > kNwLdsRows && !c.cls_tasks[kClasses - 1].empty()) ? (int64_t)9 * (c.wg_max_l2 + 1) : 0;
+  uint8_t *d_seqs = nullptr, *d_masks = nullptr, *d_trace = nullptr;
+  NwTask* d_tasks = nullptr; float* d_diag = nullptr; int32_t* d_index = nullptr; uint32_t* d_queue = nullptr;
+  DEV_TRY(ctx, lease.alloc(&d_seqs, c.seqs.size()));
+  DEV_TRY(ctx, lease.alloc(&d_masks, c.seqs.size()));
+  DEV_TRY(ctx, lease.alloc(&d_tasks, (size_t)nt * sizeof(NwTask)));
+  DEV_TRY(ctx, lease.alloc(&d_index, (size_t)nt * sizeof(int32_t)));
+  c.big_lock = ltr::ctx_call_lock(ctx);                         // one borrower of the context's big block at a time (a second host thread waits here)
+  d_trace = (uint8_t*)ltr::ctx_big_scratch(ctx, (size_t)c.trace_bytes);     // (kept by the context between calls: gigabytes)
+  if (!d_trace) { ltr::set_error(ctx, "out of device memory (NW trace)"); return LTR_ERR_NOMEM; }
+  if (diag_stride) DEV_TRY(ctx, lease.alloc(&d_diag, (size_t)(c.cls_grid[kClasses - 1] * diag_stride) * sizeof(float)));
+  DEV_TRY(ctx, lease.alloc(&c.d_out, (size_t)std::max<int64_t>(c.out_bytes, 1)));
+  DEV_TRY(ctx, lease.alloc(&c.d_len, (size_t)nt * sizeof(int32_t)));
+  DEV_TRY(ctx, lease.alloc(&d_queue, kClasses * sizeof(uint32_t)));
+  c.trace("device blocks");
+  DEV_TRY(ctx, hipMemcpyAsync(d_seqs, c.seqs.data(), c.seqs.size(), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(ltr_nw_mask_kernel, dim3((unsigned)std::min<size_t>((c.seqs.size() + 255) / 256, (size_t)n_cu * 8)), dim3(256), 0, st, d_seqs, d_masks, (int64_t)c.seqs.size());
+  DEV_TRY(ctx, hipGetLastError());
+  DEV_TRY(ctx, hipMemcpyAsync(d_tasks, c.tasks.data(), (size_t)nt * sizeof(NwTask), hipMemcpyHostToDevice, st));
+  DEV_TRY(ctx, hipMemcpyAsync(d_index, c.index.data(), (size_t)nt * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  DEV_TRY(ctx, hipMemsetAsync(d_queue, 0, kClasses * sizeof(uint32_t), st));
+  DEV_TRY(ctx, lease.event(&c.ev0, true)); DEV_TRY(ctx, lease.event(&c.ev1, true));
+  DEV_TRY(ctx, hipEventRecord(c.ev0, st));
+  for (int q = 0; q < kClasses; ++q) {
+    const int cl = (q < kClasses - 1) ? kClasses - 2 - q : kClasses - 1;      // strip widths 20, 16, .., 4, then the workgroup kernel
+    const int n_c = (int)c.cls_tasks[cl].size();
+    if (n_c == 0) continue;
+    hipStream_t sc = (hipStream_t)ltr::ctx_side_stream(ctx, q);            // (q = 0: the context's stream itself)
+    lease.also(sc);
+    if (sc != st) DEV_TRY(ctx, hipStreamWaitEvent(sc, c.ev0, 0));
+    const int32_t* idx = d_index + c.cls_first[cl];
+    uint8_t* tr = d_trace + c.cls_off[cl];
+    const dim3 g((unsigned)c.cls_grid[cl]), wb(64 * kNwWaveBlock);
+    switch (cl) {
+      case 0: hipLaunchKernelGGL((ltr_nw_wave_kernel<4>), g, wb, 0, sc, d_tasks, idx, n_c, d_queue + cl, d_seqs, d_masks, tr, c.cls_stride[cl], c.d_out, c.d_len); break;
+      case 1: hipLaunchKernelGGL((ltr_nw_wave_kernel<8>), g, wb, 0, sc, d_tasks, idx, n_c, d_queue + cl, d_seqs, d_masks, tr, c.cls_stride[cl], c.d_out, c.d_len); break;
+      case 2: hipLaunchKernelGGL((ltr_nw_wave_kernel<12>), g, wb, 0, sc, d_tasks, idx, n_c, d_queue + cl, d_seqs, d_masks, tr, c.cls_stride[cl], c.d_out, c.d_len); break;
+      case 3: hipLaunchKernelGGL((ltr_nw_wave_kernel<16>), g, wb, 0, sc, d_tasks, idx, n_c, d_queue + cl, d_seqs, d_masks, tr, c.cls_stride[cl], c.d_out, c.d_len); break;
+      case 4: hipLaunchKernelGGL((ltr_nw_wave_kernel<20>), g, wb, 0, sc, d_tasks, idx, n_c, d_queue + cl, d_seqs, d_masks, tr, c.cls_stride[cl], c.d_out, c.d_len); break;
+      default:
+        hipLaunchKernelGGL(ltr_nw_kernel, g, dim3(kNwThreads), 0, sc, d_tasks, idx, n_c, d_queue + cl, d_seqs, tr, c.cls_stride[cl],
+                           d_diag, diag_stride, c.d_out, c.d_len);
+    }
+    DEV_TRY(ctx, hipGetLastError());
+    if (sc != st) {
+      hipEvent_t ev_join = nullptr;
+      DEV_TRY(ctx, lease.event(&ev_join, false));
+      DEV_TRY(ctx, hipEventRecord(ev_join, sc));
+      DEV_TRY(ctx, hipStreamWaitEvent(st, ev_join, 0));
+    }
+  }
+  DEV_TRY(ctx, hipEventRecord(c.ev1, st));
+  c.trace("launches queued");
+  return LTR_OK;
+}
+
+// column codes and their lengths back: the call's one wait (every side stream was joined into the context's stream)
+int nw_download(ltr_ctx* ctx, NwCall& c) {
+  const size_t nt = c.tasks.size();
+  c.h_len.resize(nt);
+  c.h_out = ltr::ctx_host_bytes(ctx, 0, (size_t)std::max<int64_t>(c.out_bytes, 1));       // (under the context's call lock, taken in nw_device)
+  DEV_TRY(ctx, hipMemcpyAsync(c.h_out, c.d_out, (size_t)c.out_bytes, hipMemcpyDeviceToHost, c.lease.st));
+  DEV_TRY(ctx, hipMemcpyAsync(c.h_len.data(), c.d_len, nt * sizeof(int32_t), hipMemcpyDeviceToHost, c.lease.st));
+  DEV_TRY(ctx, c.lease.drain());
+  c.trace("codes downloaded");
+  { float ms = 0.f; if (hipEventElapsedTime(&ms, c.ev0, c.ev1) == hipSuccess) ltr::add_time(ctx, ltr::kTimerNwKernel, 0.0, (double)ms); }
+  return LTR_OK;
+}
+
+// host, all cores: reverse, adjust_indels, M / I / D (Haplotype.cpp:66-82)
+int nw_strings(ltr_ctx* ctx, const NwCall& c, char* aln_info, int64_t cap, int64_t* info_off) {
+  const int64_t nt = (int64_t)c.tasks.size();
+  for (int64_t k = 0; k < nt; ++k) info_off[k + 1] = info_off[k] + c.h_len[(size_t)k];       // (adjust_indels keeps the length)
+  if (info_off[nt] > cap) { ltr::set_error(ctx, "ltr_haplotype_align_to_ref: output buffer too small (ltr_haplotype_aln_info_capacity)"); return LTR_ERR_INVALID; }
+  ltr::parallel_for(nt, 64, [&](int64_t k) {
+    const int n = c.h_len[(size_t)k];
+    // the two aligned strings (traceAlignment's stringstreams, reversed, :247-312) from the device's column codes, front to back
+    const uint8_t* ops = c.h_out + c.tasks[(size_t)k].out_off;
+    char* dst = aln_info + info_off[k];
+    {
+      // adjust_indels only ever touches a gap that starts while the reference position is still left of the repeat block
+      // (`ref_pos < str_pos` in both of its branches): when the first str_pos - ref_pos0 columns are all matches it changes
+      // nothing, and the M / I / D string is the column codes read backwards -- no strings built (most haplotypes differ from
+      // the reference allele inside the repeat only; the strings + adjust_indels pass was 2.4 - 4.8 of the call's 15.4 ms).
+      const int flank = std::min(n, std::max(0, c.str_pos[(size_t)k] - c.ref_pos0[(size_t)k]));
+      bool plain = true;
+      for (int i = 0; i < flank; ++i) if (ops[n - 1 - i] != 0) { plain = false; break; }
+      if (plain) {
+        for (int i = 0; i < n; ++i) { const uint8_t op = ops[n - 1 - i]; dst[i] = op == 0 ? 'M' : (op == 1 ? 'D' : 'I'); }
+        return;
+      }
+    }
+    const uint8_t* rs = c.seqs.data() + c.tasks[(size_t)k].ref_off;
+    const uint8_t* as = c.seqs.data() + c.tasks[(size_t)k].alt_off;
+    std::string ref_al((size_t)n, '-'), alt_al((size_t)n, '-');
+    for (int i = 0, ri = 0, ai = 0; i < n; ++i) {
+      const uint8_t op = ops[n - 1 - i];
+      if (op != 2) ref_al[(size_t)i] = (char)rs[ri++];
+      if (op != 1) alt_al[(size_t)i] = (char)as[ai++];
+    }
+    adjust_indels(ref_al, alt_al, c.ref_pos0[(size_t)k], c.str_pos[(size_t)k]);
+    for (int i = 0; i < n; ++i) dst[i] = (ref_al[(size_t)i] == '-') ? 'I' : ((alt_al[(size_t)i] == '-') ? 'D' : 'M');
+  }, 16);
+  c.trace("strings rebuilt");
+  return LTR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -395,239 +645,18 @@ int ltr_haplotype_align_to_ref(ltr_ctx* ctx, const ltr_haplotype_blocks* const* 
   ltr::TimedCall timed(ctx, ltr::kTimerHapBuild);              // total_hap_build_time_ (seq_stutter_genotyper.cpp:417,:479-480)
   LTR_GUARD_BEGIN
   if (hipSetDevice(ltr::ctx_device(ctx)) != hipSuccess) { ltr::set_error(ctx, "hipSetDevice failed"); return LTR_ERR_NO_DEVICE; }
-  const bool nw_dbg = ltr::ctx_debug(ctx).trace != 0;                 // ltr_ctx_set_debug "trace": a timestamped phase profile on stderr
-  const auto nw_t0 = std::chrono::steady_clock::now();
-#define NW_TRACE(what) do { if (nw_dbg) std::fprintf(stderr, "[ltr] haplotype_align_to_ref %8.2f ms: %s\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - nw_t0).count(), what); } while (0)
-  // ---- tasks: (reference haplotype, haplotype k) for every haplotype, sequences pooled.  Two passes: sizes and offsets in locus
-  // order (serial, a few integers per haplotype), then the bytes on all host cores (20 MB per 3000 config-3 loci) ----
-  std::vector<NwTask> tasks;
-  std::vector<int32_t> ref_pos0, str_pos;                      // adjust_indels: blocks_[0]->start(), blocks_[1]->start()
-  std::vector<int64_t> locus_task((size_t)n_loci + 1, 0);
-  std::vector<std::vector<int32_t>> locus_counts((size_t)n_loci);
-  int64_t out_bytes = 0, pool_bytes = 64;                      // (padded: the wavefront kernel streams rows without clamping)
-  int32_t max_l1 = 1, max_l2 = 1;
-  for (int64_t l = 0; l < n_loci; ++l) {
-    const ltr_haplotype_blocks* h = haps[l];
-    if (!h || h->n_blocks != 3) { ltr::set_error(ctx, "ltr_haplotype_align_to_ref: a haplotype needs three blocks (Haplotype::adjust_indels asserts it)"); return LTR_ERR_INVALID; }
-    std::vector<int32_t>& counts = locus_counts[(size_t)l];
-    int64_t H = 0;
-    const int rc = ltr::haplotype_counts(h, &counts, &H);
-    if (rc != LTR_OK) return rc;
-    const int64_t ref_off = pool_bytes;
-    int64_t ref_len = 0;
-    for (int64_t k = 0; k < H; ++k) {
-      int64_t len = 0, slot = 0;
-      for (int b = 0; b < h->n_blocks; ++b) {
-        const int64_t a = slot + counts[(size_t)(k * h->n_blocks + b)];
-        len += h->allele_off[a + 1] - h->allele_off[a];
-        slot += h->n_alleles[b];
-      }
-      if (k == 0) ref_len = len;
-      if (ref_len < 1 || len < 1 || ref_len > (1 << 20) || len > (1 << 20)) { ltr::set_error(ctx, "empty or oversized haplotype"); return LTR_ERR_INVALID; }
-      NwTask t;
-      t.ref_off = ref_off; t.alt_off = pool_bytes; t.L1 = (int32_t)ref_len; t.L2 = (int32_t)len; t.out_off = out_bytes;
-      pool_bytes += len;
-      out_bytes += ref_len + len;
-      max_l1 = std::max(max_l1, t.L1); max_l2 = std::max(max_l2, t.L2);
-      tasks.push_back(t);
-      ref_pos0.push_back(h->block_start[0]); str_pos.push_back(h->block_start[1]);
-    }
-    locus_task[(size_t)l + 1] = (int64_t)tasks.size();
-  }
-  std::vector<uint8_t> seqs((size_t)pool_bytes + 128, 0);
-  ltr::parallel_for(n_loci, 64, [&](int64_t l) {
-    const ltr_haplotype_blocks* h = haps[l];
-    const std::vector<int32_t>& counts = locus_counts[(size_t)l];
-    for (int64_t t = locus_task[(size_t)l]; t < locus_task[(size_t)l + 1]; ++t) {
-      const int64_t k = t - locus_task[(size_t)l];
-      uint8_t* dst = seqs.data() + tasks[(size_t)t].alt_off;
-      int64_t slot = 0;
-      for (int b = 0; b < h->n_blocks; ++b) {
-        const int64_t a = slot + counts[(size_t)(k * h->n_blocks + b)];
-        const int64_t len = h->allele_off[a + 1] - h->allele_off[a];
-        std::memcpy(dst, h->allele_bytes + h->allele_off[a], (size_t)len);
-        dst += len; slot += h->n_alleles[b];
-      }
-    }
-  }, 16);
-  NW_TRACE("sequences pooled");
-  const int64_t nt = (int64_t)tasks.size();
+  NwCall c(ctx);
+  int rc = nw_tasks(ctx, haps, n_loci, c);
+  if (rc != LTR_OK) return rc;
   info_off[0] = 0;
-  if (nt == 0) return LTR_OK;
-  // ---- launch classes: references of up to 64 x 20 bases take the wavefront kernel (strip width 4 .. 20), longer
-  // ones the workgroup-per-pair kernel ----
-  constexpr int kClasses = 6;                                   // strip widths 4, 8, 12, 16, 20 + the workgroup kernel
-  // (every even width 4 .. 20 -- nine classes, fuller lanes -- was tried on MI355X, same workload: kernels 10.3 ms, no change, and
-  // the widths that are not multiples of four failed the parity test (trace words of a partly filled last word): not kept)
-  std::vector<int32_t> cls_tasks[kClasses];
-  int32_t cls_max_l2[kClasses] = {0}, wg_max_l1 = 1, wg_max_l2 = 1;
-  for (int64_t k = 0; k < nt; ++k) {
-    const int w = (tasks[(size_t)k].L1 + 63) / 64;
-    const int c = (w <= kNwWaveMaxW) ? (std::max(w, 1) + 3) / 4 - 1 : kClasses - 1;
-    cls_tasks[c].push_back((int32_t)k);
-    cls_max_l2[c] = std::max(cls_max_l2[c], tasks[(size_t)k].L2);
-    if (c == kClasses - 1) { wg_max_l1 = std::max(wg_max_l1, tasks[(size_t)k].L1); wg_max_l2 = std::max(wg_max_l2, tasks[(size_t)k].L2); }
-  }
+  if (c.tasks.empty()) return LTR_OK;
   int n_cu = 0;
   (void)ltr_ctx_device_info(ctx, nullptr, 0, &n_cu, nullptr);
   n_cu = std::max(n_cu, 1);
-  // Every class has a region of its own in the trace block and a stream of its own: the launches run side by side, widest strips
-  // (longest pairs) first, and inside a class the pairs are popped longest first -- a pair is 1 - 3 ms of one wavefront and a class
-  // of a 3000-locus call a handful of pairs per resident wavefront, so a launch on its own ends in a tail as long as a pair with most
-  // of the GPU idle (rocprofv3, round 3: VALU issue 0.35 - 0.65 per launch).  Measured on MI355X, 21 k haplotypes of 3000 config-3
-  // loci, kernels first to last: one stream, task order 14.0 ms; profiles/r05/nw_rate.log.
-  int64_t cls_grid[kClasses] = {0}, cls_stride[kClasses] = {0}, cls_off[kClasses] = {0}, trace_bytes = 256;
-  std::vector<int32_t> index;
-  int64_t cls_first[kClasses + 1] = {0};
-  constexpr int64_t kTraceCap = (int64_t)16 << 30;              // of the context's trace block, all classes together
-  // longest first inside a class: rows of the alternate, then the reference's length, ties in task order (the classes side by side
-  // on the host cores, plain keys: a comparator that looks the tasks up was 1.1 ms for 21 k haplotypes)
-  ltr::parallel_for(kClasses, 1, [&](int64_t c) {
-    struct Key { int32_t l2, l1, task; };
-    std::vector<Key> keys; keys.reserve(cls_tasks[c].size());
-    for (const int32_t t : cls_tasks[c]) keys.push_back({tasks[(size_t)t].L2, tasks[(size_t)t].L1, t});
-    std::sort(keys.begin(), keys.end(), [](const Key& x, const Key& y) { return x.l2 != y.l2 ? x.l2 > y.l2 : (x.l1 != y.l1 ? x.l1 > y.l1 : x.task < y.task); });
-    for (size_t i = 0; i < keys.size(); ++i) cls_tasks[c][i] = keys[i].task;
-  }, 1);
-  for (int pass = 0; pass < 2; ++pass) {
-    // (pass 1, only when the regions of pass 0 add up to more than the cap: every class with its share of the wavefronts)
-    const double shrink = pass == 0 ? 1.0 : (double)kTraceCap / (double)trace_bytes * 0.98;
-    if (pass == 1 && trace_bytes <= kTraceCap) break;
-    trace_bytes = 256;
-    for (int c = 0; c < kClasses; ++c) {
-      if (pass == 0) {
-        cls_first[c + 1] = cls_first[c] + (int64_t)cls_tasks[c].size();
-        index.insert(index.end(), cls_tasks[c].begin(), cls_tasks[c].end());
-      }
-      if (cls_tasks[c].empty()) continue;
-      cls_off[c] = trace_bytes;
-      if (c < kClasses - 1) {
-        const int W = 4 * (c + 1);
-        cls_stride[c] = (((int64_t)(cls_max_l2[c] + 64) * 64 * W) + 255) / 256 * 256;       // per wavefront
-        int64_t waves = std::min<int64_t>((int64_t)cls_tasks[c].size(), (int64_t)n_cu * 12);
-        waves = std::max<int64_t>(1, std::min<int64_t>((int64_t)((double)waves * shrink), ((int64_t)6 << 30) / cls_stride[c]));
-        cls_grid[c] = (waves + kNwWaveBlock - 1) / kNwWaveBlock;
-        trace_bytes += cls_grid[c] * kNwWaveBlock * cls_stride[c];
-      } else {
-        cls_stride[c] = (((int64_t)(wg_max_l1 + 1) * (wg_max_l2 + 1)) + 255) / 256 * 256;   // per workgroup
-        int64_t g = std::min<int64_t>((int64_t)cls_tasks[c].size(), (int64_t)n_cu * 2);    // LDS (54 KB) admits two workgroups per CU
-        cls_grid[c] = std::max<int64_t>(1, std::min<int64_t>((int64_t)std::max(1.0, (double)g * shrink), ((int64_t)6 << 30) / cls_stride[c]));
-        trace_bytes += cls_grid[c] * cls_stride[c];
-      }
-    }
-  }
-  NW_TRACE("classes sorted");
-  const int64_t diag_stride = (wg_max_l2 > kNwLdsRows && !cls_tasks[kClasses - 1].empty()) ? (int64_t)9 * (wg_max_l2 + 1) : 0;
-  uint8_t *d_seqs = nullptr, *d_masks = nullptr, *d_trace = nullptr, *d_out = nullptr;
-  NwTask* d_tasks = nullptr; float* d_diag = nullptr; int32_t* d_len = nullptr; int32_t* d_index = nullptr; uint32_t* d_queue = nullptr;
-  int rc = LTR_OK;
-  std::unique_lock<std::mutex> big_lock;                        // (taken where the context's trace block is borrowed)
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;                      // device time of the kernels (ltr_timers.nw_kernel_ms)
-  hipEvent_t ev_join[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  hipStream_t st = (hipStream_t)ltr::ctx_stream(ctx);
-  uint8_t* h_out = nullptr;                                    // (pinned staging of the context: the download goes over the DMA engines)
-  std::vector<int32_t> h_len((size_t)nt);
-  std::vector<void*> blocks;
-#define NW_TRY(call) do { hipError_t e_ = (hipError_t)(call); if (e_ != hipSuccess) { ltr::set_error(ctx, std::string(#call) + ": " + hipGetErrorString(e_)); rc = LTR_ERR_HIP; goto done; } } while (0)
-#define NW_ALLOC(ptr, bytes) do { void* p_ = nullptr; NW_TRY(ltr::ctx_pool_alloc(ctx, &p_, (size_t)(bytes))); blocks.push_back(p_); ptr = (decltype(ptr))p_; } while (0)
-  NW_ALLOC(d_seqs, seqs.size());
-  NW_ALLOC(d_masks, seqs.size());
-  NW_ALLOC(d_tasks, (size_t)nt * sizeof(NwTask));
-  NW_ALLOC(d_index, (size_t)nt * sizeof(int32_t));
-  big_lock = ltr::ctx_call_lock(ctx);                           // one borrower of the context's big block at a time (a second host thread waits here)
-  d_trace = (uint8_t*)ltr::ctx_big_scratch(ctx, (size_t)trace_bytes);     // (kept by the context between calls: gigabytes)
-  if (!d_trace) { ltr::set_error(ctx, "out of device memory (NW trace)"); rc = LTR_ERR_NOMEM; goto done; }
-  if (diag_stride) NW_ALLOC(d_diag, (size_t)(cls_grid[kClasses - 1] * diag_stride) * sizeof(float));
-  NW_ALLOC(d_out, std::max<int64_t>(out_bytes, 1));
-  NW_ALLOC(d_len, (size_t)nt * sizeof(int32_t));
-  NW_ALLOC(d_queue, kClasses * sizeof(uint32_t));
-  NW_TRACE("device blocks");
-  NW_TRY(hipMemcpyAsync(d_seqs, seqs.data(), seqs.size(), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(ltr_nw_mask_kernel, dim3((unsigned)std::min<size_t>((seqs.size() + 255) / 256, (size_t)n_cu * 8)), dim3(256), 0, st, d_seqs, d_masks, (int64_t)seqs.size());
-  NW_TRY(hipGetLastError());
-  NW_TRY(hipMemcpyAsync(d_tasks, tasks.data(), (size_t)nt * sizeof(NwTask), hipMemcpyHostToDevice, st));
-  NW_TRY(hipMemcpyAsync(d_index, index.data(), (size_t)nt * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  NW_TRY(hipMemsetAsync(d_queue, 0, kClasses * sizeof(uint32_t), st));
-  NW_TRY(hipEventCreate(&ev0)); NW_TRY(hipEventCreate(&ev1));
-  NW_TRY(hipEventRecord(ev0, st));
-  for (int q = 0; q < kClasses; ++q) {
-    const int c = (q < kClasses - 1) ? kClasses - 2 - q : kClasses - 1;       // strip widths 20, 16, .., 4, then the workgroup kernel
-    const int n_c = (int)cls_tasks[c].size();
-    if (n_c == 0) continue;
-    hipStream_t sc = (hipStream_t)ltr::ctx_side_stream(ctx, q);            // (q = 0: the context's stream itself)
-    if (sc != st) NW_TRY(hipStreamWaitEvent(sc, ev0, 0));
-    const int32_t* idx = d_index + cls_first[c];
-    uint8_t* tr = d_trace + cls_off[c];
-    const dim3 g((unsigned)cls_grid[c]), wb(64 * kNwWaveBlock);
-    switch (c) {
-      case 0: hipLaunchKernelGGL((ltr_nw_wave_kernel<4>), g, wb, 0, sc, d_tasks, idx, n_c, d_queue + c, d_seqs, d_masks, tr, cls_stride[c], d_out, d_len); break;
-      case 1: hipLaunchKernelGGL((ltr_nw_wave_kernel<8>), g, wb, 0, sc, d_tasks, idx, n_c, d_queue + c, d_seqs, d_masks, tr, cls_stride[c], d_out, d_len); break;
-      case 2: hipLaunchKernelGGL((ltr_nw_wave_kernel<12>), g, wb, 0, sc, d_tasks, idx, n_c, d_queue + c, d_seqs, d_masks, tr, cls_stride[c], d_out, d_len); break;
-      case 3: hipLaunchKernelGGL((ltr_nw_wave_kernel<16>), g, wb, 0, sc, d_tasks, idx, n_c, d_queue + c, d_seqs, d_masks, tr, cls_stride[c], d_out, d_len); break;
-      case 4: hipLaunchKernelGGL((ltr_nw_wave_kernel<20>), g, wb, 0, sc, d_tasks, idx, n_c, d_queue + c, d_seqs, d_masks, tr, cls_stride[c], d_out, d_len); break;
-      default:
-        hipLaunchKernelGGL(ltr_nw_kernel, g, dim3(kNwThreads), 0, sc, d_tasks, idx, n_c, d_queue + c, d_seqs, tr, cls_stride[c],
-                           d_diag, diag_stride, d_out, d_len);
-    }
-    NW_TRY(hipGetLastError());
-    if (sc != st) {
-      if (!ev_join[q]) NW_TRY(hipEventCreateWithFlags(&ev_join[q], hipEventDisableTiming));
-      NW_TRY(hipEventRecord(ev_join[q], sc));
-      NW_TRY(hipStreamWaitEvent(st, ev_join[q], 0));
-    }
-  }
-  NW_TRY(hipEventRecord(ev1, st));
-  NW_TRACE("launches queued");
-  h_out = ltr::ctx_host_bytes(ctx, 0, (size_t)std::max<int64_t>(out_bytes, 1));       // (under the context's call lock, taken above)
-  NW_TRY(hipMemcpyAsync(h_out, d_out, (size_t)out_bytes, hipMemcpyDeviceToHost, st));
-  NW_TRY(hipMemcpyAsync(h_len.data(), d_len, (size_t)nt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  NW_TRY(hipStreamSynchronize(st));
-  NW_TRACE("codes downloaded");
-  { float ms = 0.f; if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) ltr::add_time(ctx, ltr::kTimerNwKernel, 0.0, (double)ms); }
-  {
-    // ---- host, all cores: reverse, adjust_indels, M / I / D (Haplotype.cpp:66-82) ----
-    for (int64_t k = 0; k < nt; ++k) info_off[k + 1] = info_off[k] + h_len[(size_t)k];       // (adjust_indels keeps the length)
-    if (info_off[nt] > cap) { ltr::set_error(ctx, "ltr_haplotype_align_to_ref: output buffer too small (ltr_haplotype_aln_info_capacity)"); rc = LTR_ERR_INVALID; goto done; }
-    ltr::parallel_for(nt, 64, [&](int64_t k) {
-      const int n = h_len[(size_t)k];
-      // the two aligned strings (traceAlignment's stringstreams, reversed, :247-312) from the device's column codes, front to back
-      const uint8_t* ops = h_out + tasks[(size_t)k].out_off;
-      char* dst = aln_info + info_off[k];
-      {
-        // adjust_indels only ever touches a gap that starts while the reference position is still left of the repeat block
-        // (`ref_pos < str_pos` in both of its branches): when the first str_pos - ref_pos0 columns are all matches it changes
-        // nothing, and the M / I / D string is the column codes read backwards -- no strings built (most haplotypes differ from
-        // the reference allele inside the repeat only; the strings + adjust_indels pass was 2.4 - 4.8 of the call's 15.4 ms).
-        const int flank = std::min(n, std::max(0, str_pos[(size_t)k] - ref_pos0[(size_t)k]));
-        bool plain = true;
-        for (int i = 0; i < flank; ++i) if (ops[n - 1 - i] != 0) { plain = false; break; }
-        if (plain) {
-          for (int i = 0; i < n; ++i) { const uint8_t op = ops[n - 1 - i]; dst[i] = op == 0 ? 'M' : (op == 1 ? 'D' : 'I'); }
-          return;
-        }
-      }
-      const uint8_t* rs = seqs.data() + tasks[(size_t)k].ref_off;
-      const uint8_t* as = seqs.data() + tasks[(size_t)k].alt_off;
-      std::string ref_al((size_t)n, '-'), alt_al((size_t)n, '-');
-      for (int i = 0, ri = 0, ai = 0; i < n; ++i) {
-        const uint8_t op = ops[n - 1 - i];
-        if (op != 2) ref_al[(size_t)i] = (char)rs[ri++];
-        if (op != 1) alt_al[(size_t)i] = (char)as[ai++];
-      }
-      adjust_indels(ref_al, alt_al, ref_pos0[(size_t)k], str_pos[(size_t)k]);
-      for (int i = 0; i < n; ++i) dst[i] = (ref_al[(size_t)i] == '-') ? 'I' : ((alt_al[(size_t)i] == '-') ? 'D' : 'M');
-    }, 16);
-  }
-  NW_TRACE("strings rebuilt");
-done:
-#undef NW_TRACE
-#undef NW_TRY
-#undef NW_ALLOC
-  if (rc != LTR_OK) for (int q = 0; q < 6; ++q) (void)hipStreamSynchronize((hipStream_t)ltr::ctx_side_stream(ctx, q));   // (nothing in flight may still use the blocks)
-  for (void* p_ : blocks) ltr::ctx_pool_release(ctx, p_);
-  for (hipEvent_t e : ev_join) if (e) (void)hipEventDestroy(e);
-  if (ev0) (void)hipEventDestroy(ev0);
-  if (ev1) (void)hipEventDestroy(ev1);
+  nw_classes(c, n_cu);
+  rc = nw_device(ctx, c, n_cu);
+  if (rc == LTR_OK) rc = nw_download(ctx, c);
+  if (rc == LTR_OK) rc = nw_strings(ctx, c, aln_info, cap, info_off);
   return rc;
   LTR_GUARD_END(ctx)
 }

@@ -237,7 +237,7 @@ struct GtCall {
   DevReads rd; int32_t* d_map = nullptr; DevPass pass[2];
   DevLease lease;
   GtCall(ltr_plan* p, const ltr_genotype_batch* g, const ltr_fields_request* f)
-      : plan(p), ctx(p->ctx), gb(g), pb(g->pb), fr(f), res(new ltr_genotype_result()), lease(p->ctx->pool, p->last_stream) {}
+      : plan(p), ctx(p->ctx), gb(g), pb(g->pb), fr(f), res(new ltr_genotype_result()), lease(p->ctx, p->last_stream) {}
 };
 
 // ---- host, all loci at once: the result laid out, labels checked, every sample's reads listed in read order, aligned_read (:262-266) ----

@@ -123,7 +123,7 @@ int ltr_posteriors(ltr_ctx* ctx, int32_t S, int32_t R, int32_t H,
   double *d_ll = nullptr, *d_p1 = nullptr, *d_p2 = nullptr, *d_post = nullptr, *d_stl = nullptr;
   int *d_lab = nullptr, *d_gts = nullptr;
   hipStream_t st = ctx->stream;
-  DevLease lease(ctx->pool, st);                               // (every host buffer the copies touch is the caller's or the lease's)
+  DevLease lease(ctx, st);                               // (every host buffer the copies touch is the caller's or the lease's)
   DEV_TRY(ctx, lease.alloc(&d_ll, std::max<size_t>(nll, 1) * 8));
   DEV_TRY(ctx, lease.alloc(&d_p1, std::max<size_t>(R, 1) * 8));
   DEV_TRY(ctx, lease.alloc(&d_p2, std::max<size_t>(R, 1) * 8));
@@ -189,7 +189,7 @@ int ltr_plan_posteriors(ltr_plan* plan, const ltr_posterior_batch* pb, double* p
   double *d_post = nullptr, *d_stl = nullptr;
   DevReads rd;
   hipStream_t st = plan->last_stream;
-  DevLease lease(ctx->pool, st);
+  DevLease lease(ctx, st);
   DEV_TRY(ctx, lease.alloc(&d_units, nu * sizeof(PostUnit)));
   DEV_TRY(ctx, hipMemcpyAsync(d_units, units.data(), nu * sizeof(PostUnit), hipMemcpyHostToDevice, st));
   if (int rc = upload_reads(ctx, lease, pb, &rd)) return rc;

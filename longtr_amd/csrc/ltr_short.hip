@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "ltr_internal.h"
+#include "ltr_lease.h"
 
 namespace {
 
@@ -750,8 +751,6 @@ double stutter_pmf(const StutterLogs& s, int motif_len, int sample_bps, int read
 
 namespace ltr {
 
-#define S_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_error(ctx, std::string(#call) + ": " + hipGetErrorString(e_)); rc = LTR_ERR_HIP; goto done; } } while (0)
-
 // Host-side accumulator of the seeded path: loci are prepared one by one (short_batch_add) and
 // scored together in ONE launch (short_batch_run) -- a pair is one lane running a sequential
 // recurrence, so the only parallelism is across pairs, and one locus has ~100 of them.
@@ -794,6 +793,55 @@ int short_batch_merge(ltr_ctx* ctx, ShortBatch* dst, ShortBatch* src) {
 }
 void short_batch_free(ShortBatch* b) { delete b; }
 
+// ... its haplotype combinations, both directions: bytes, upstream-match tables, artifact terms; the first of them is B->fw[hap0]
+static int short_add_haps(ltr_ctx* ctx, ShortBatch* B, const ltr_haplotype_blocks* hap, const std::vector<int32_t>& counts, int64_t H, size_t hap0) {
+  const ltr_stutter_params sp = ctx_stutter_params(ctx);
+  const int period = hap->period[1];
+  StutterLogs sl;
+  sl.in_step = std::log(1 - sp.in_geom); sl.in_nostep = std::log(sp.in_geom); sl.in_up = std::log(sp.in_up); sl.in_down = std::log(sp.in_down);
+  sl.out_step = std::log(1 - sp.out_geom); sl.out_nostep = std::log(sp.out_geom); sl.out_up = std::log(sp.out_up); sl.out_down = std::log(sp.out_down);
+  sl.equal = std::log(1 - sp.in_up - sp.in_down - sp.out_up - sp.out_down);
+  B->fw.resize(hap0 + (size_t)H); B->rv.resize(hap0 + (size_t)H); B->art.resize((hap0 + (size_t)H) * kNumArt);
+  std::vector<int32_t>& upstream = B->upstream;
+  auto slot = [&](int b, int al) { int64_t k = 0; for (int q = 0; q < b; q++) k += hap->n_alleles[q]; return k + al; };
+  auto add_upstream = [&](const std::vector<uint8_t>& blk, ShortHap* h) {      // StutterAlignerClass ctor, .h:45-79
+    const int len = (int)blk.size();
+    int nd = kMaxDel;
+    while (nd * period > len) nd--;
+    h->num_deletions = nd; h->up_off = (int32_t)upstream.size();
+    auto one = [&](int per) {                                                    // num_upstream_matches, .h:34-41
+      const size_t base = upstream.size();
+      upstream.resize(base + (size_t)std::max(len, 1), 0);
+      for (int i = per; i < len; i++) upstream[base + i] = (blk[i - per] != blk[i]) ? 0 : 1 + upstream[base + i - 1];
+    };
+    for (int i = 1; i <= nd; i++) one(i * period);
+    if (nd == 0) one(period);
+  };
+  for (int64_t k = 0; k < H; k++) {
+    std::vector<uint8_t> blk[3];
+    for (int b = 0; b < 3; b++) {
+      const int64_t s = slot(b, counts[(size_t)(k * 3 + b)]);
+      blk[b].assign(hap->allele_bytes + hap->allele_off[s], hap->allele_bytes + hap->allele_off[s + 1]);
+    }
+    if (blk[0].empty() || blk[2].empty()) { set_error(ctx, "short path: empty flank block"); return LTR_ERR_INVALID; }
+    ShortHap& f = B->fw[hap0 + (size_t)k]; ShortHap& r = B->rv[hap0 + (size_t)k];
+    f.seq_off = (int64_t)B->hbytes.size(); f.pad = 0;
+    for (int b = 0; b < 3; b++) { f.len[b] = (int32_t)blk[b].size(); B->hbytes.insert(B->hbytes.end(), blk[b].begin(), blk[b].end()); }
+    add_upstream(blk[1], &f);
+    r.seq_off = (int64_t)B->hbytes.size(); r.pad = 0;                           // Haplotype::reverse: blocks and bases reversed
+    for (int b = 0; b < 3; b++) { std::vector<uint8_t> t(blk[2 - b].rbegin(), blk[2 - b].rend()); r.len[b] = (int32_t)t.size(); B->hbytes.insert(B->hbytes.end(), t.begin(), t.end()); if (b == 1) add_upstream(t, &r); }
+    const int bl = (int)blk[1].size();
+    for (int q = 0; q < kNumArt; q++) {                                          // log_prob_pcr_artifact, RepeatStutterInfo.h:53-61
+      const int asz = (q - kMaxDel) * period, read_size = bl + asz;
+      B->art[(hap0 + (size_t)k) * kNumArt + q] = (asz < 0 && read_size < 0) ? -10e6 : stutter_pmf(sl, period, bl, read_size);   // (asz <= max_ins always)
+    }
+    B->maxHS = std::max(B->maxHS, (int)(blk[0].size() + blk[1].size() + blk[2].size()));
+    B->maxB = std::max(B->maxB, bl);
+  }
+  if (upstream.size() > 0x7fffff00u) { set_error(ctx, "short path: batch too large"); return LTR_ERR_INVALID; }
+  return LTR_OK;
+}
+
 // HapAligner::process_reads with short_ == 1 (HapAligner.cpp:545-581), host half, for one locus:
 // seeds and the all-zero rows of seedless reads are written at once, the pairs are queued.
 // aln_probs must stay valid until short_batch_run.
@@ -804,7 +852,6 @@ int short_batch_add(ltr_ctx* ctx, ShortBatch* B, const ltr_haplotype_blocks* hap
     set_error(ctx, "short path: expected [flank][repeat][flank] blocks (Haplotype.cpp:8 asserts the same)");
     return LTR_ERR_UNSUPPORTED;
   }
-  const ltr_stutter_params sp = ctx_stutter_params(ctx);
   const int period = hap->period[1];
   if (B->period == 0) B->period = period;
   if (B->period != period) { set_error(ctx, "short path: loci of one batch must share the repeat period"); return LTR_ERR_UNSUPPORTED; }
@@ -846,56 +893,8 @@ int short_batch_add(ltr_ctx* ctx, ShortBatch* B, const ltr_haplotype_blocks* hap
     B->maxS = std::max(B->maxS, std::max(seed, a.seq_len - seed - 1));
   }
   if (B->reads.size() == reads0) return LTR_OK;
-
-  // ---- haplotype combinations, both directions -------------------------------------------
-  StutterLogs sl;
-  sl.in_step = std::log(1 - sp.in_geom); sl.in_nostep = std::log(sp.in_geom); sl.in_up = std::log(sp.in_up); sl.in_down = std::log(sp.in_down);
-  sl.out_step = std::log(1 - sp.out_geom); sl.out_nostep = std::log(sp.out_geom); sl.out_up = std::log(sp.out_up); sl.out_down = std::log(sp.out_down);
-  sl.equal = std::log(1 - sp.in_up - sp.in_down - sp.out_up - sp.out_down);
   const size_t hap0 = B->fw.size();
-  B->fw.resize(hap0 + (size_t)H); B->rv.resize(hap0 + (size_t)H); B->art.resize((hap0 + (size_t)H) * kNumArt);
-  std::vector<int32_t>& upstream = B->upstream;
-  auto slot = [&](int b, int al) { int64_t k = 0; for (int q = 0; q < b; q++) k += hap->n_alleles[q]; return k + al; };
-  auto add_upstream = [&](const std::vector<uint8_t>& blk, ShortHap* h) {      // StutterAlignerClass ctor, .h:45-79
-    const int len = (int)blk.size();
-    int nd = kMaxDel;
-    while (nd * period > len) nd--;
-    h->num_deletions = nd; h->up_off = (int32_t)upstream.size();
-    auto one = [&](int per) {                                                    // num_upstream_matches, .h:34-41
-      const size_t base = upstream.size();
-      upstream.resize(base + (size_t)std::max(len, 1), 0);
-      for (int i = per; i < len; i++) upstream[base + i] = (blk[i - per] != blk[i]) ? 0 : 1 + upstream[base + i - 1];
-    };
-    for (int i = 1; i <= nd; i++) one(i * period);
-    if (nd == 0) one(period);
-  };
-  for (int64_t k = 0; k < H; k++) {
-    std::vector<uint8_t> blk[3];
-    for (int b = 0; b < 3; b++) {
-      const int64_t s = slot(b, counts[(size_t)(k * 3 + b)]);
-      blk[b].assign(hap->allele_bytes + hap->allele_off[s], hap->allele_bytes + hap->allele_off[s + 1]);
-    }
-    if (blk[0].empty() || blk[2].empty()) { set_error(ctx, "short path: empty flank block"); return LTR_ERR_INVALID; }
-    ShortHap& f = B->fw[hap0 + (size_t)k]; ShortHap& r = B->rv[hap0 + (size_t)k];
-    f.seq_off = (int64_t)B->hbytes.size(); f.pad = 0;
-    for (int b = 0; b < 3; b++) { f.len[b] = (int32_t)blk[b].size(); B->hbytes.insert(B->hbytes.end(), blk[b].begin(), blk[b].end()); }
-    add_upstream(blk[1], &f);
-    r.seq_off = (int64_t)B->hbytes.size(); r.pad = 0;                           // Haplotype::reverse: blocks and bases reversed
-    for (int b = 0; b < 3; b++) { std::vector<uint8_t> t(blk[2 - b].rbegin(), blk[2 - b].rend()); r.len[b] = (int32_t)t.size(); B->hbytes.insert(B->hbytes.end(), t.begin(), t.end()); if (b == 1) add_upstream(t, &r); }
-    const int bl = (int)blk[1].size();
-    for (int q = 0; q < kNumArt; q++) {                                          // log_prob_pcr_artifact, RepeatStutterInfo.h:53-61
-      const int asz = (q - kMaxDel) * period, read_size = bl + asz;
-      double v;
-      if (asz == 0) v = stutter_pmf(sl, period, bl, read_size);
-      else if (asz > 0) v = stutter_pmf(sl, period, bl, read_size);              // asz <= max_ins always
-      else v = (read_size < 0) ? -10e6 : stutter_pmf(sl, period, bl, read_size);
-      B->art[(hap0 + (size_t)k) * kNumArt + q] = v;
-    }
-    B->maxHS = std::max(B->maxHS, (int)(blk[0].size() + blk[1].size() + blk[2].size()));
-    B->maxB = std::max(B->maxB, bl);
-  }
-  if (upstream.size() > 0x7fffff00u) { set_error(ctx, "short path: batch too large"); return LTR_ERR_INVALID; }
-
+  if ((rc = short_add_haps(ctx, B, hap, counts, H, hap0)) != LTR_OK) return rc;
   // ---- pairs -----------------------------------------------------------------------------
   for (int32_t r = 0; r < n_alns; r++) {
     if (read_of_aln[(size_t)r] < 0) continue;
@@ -908,144 +907,175 @@ int short_batch_add(ltr_ctx* ctx, ShortBatch* B, const ltr_haplotype_blocks* hap
   return LTR_OK;
 }
 
-// One launch for everything queued; results go to the queued host destinations.
+namespace {   // ---- short_batch_run: one set of launches for everything queued, in stages over one per-call struct ----
+// S, HS, LP: ShortArgs.  A pure function of the batch and the knobs.
+struct ShortGeom { int S, HS, LP, grid, chunk_cap; int64_t per_block; size_t lds_bytes; bool wave_kernel; };
+ShortGeom short_geometry(const ShortBatch& B, int n_pairs, size_t n_ilog, bool lane_knob) {
+  ShortGeom g;
+  g.S = std::max(B.maxS, std::max(B.maxB + 2, kNumArt)) + 2; g.HS = B.maxHS + 4;
+  g.LP = std::max(g.S, g.HS) + 8;
+  g.per_block = (int64_t)(19 * g.S + g.LP + 2 * (g.HS + 2)) * 64;
+  // one wave per block; enough blocks to keep a few waves per SIMD busy with other pairs while a
+  // lane waits for its work arrays (scratch capped at 8 GB)
+  const int64_t cap_blocks = std::max<int64_t>(1, ((int64_t)8 << 30) / (g.per_block * (int64_t)sizeof(double)));
+  g.grid = (int)std::min<int64_t>(std::min<int64_t>((n_pairs + 63) / 64, 4096), cap_blocks);
+  // The four-launch path whenever a side fits 64 lanes x 8 read positions and the block kernel's tables fit 64 KB of LDS;
+  // beyond that (reads cut wider than the reference's +-200 bp) the lane-per-pair kernel with its global work arrays.
+  g.lds_bytes = ((size_t)4 * g.S + n_ilog) * sizeof(double) + ((size_t)kMaxDel * B.maxB + 8) * sizeof(int32_t) +
+                (size_t)((g.S + 7) & ~7) + (size_t)g.HS + 64;
+  g.wave_kernel = std::max(B.maxS, 1) <= 64 * 8 && g.lds_bytes <= 64 * 1024 && !lane_knob;
+  // pairs per set of launches: the block row's terms (13 x S doubles per side) fit ONE GB -- a block the context's pool keeps
+  // between calls (beyond 2 GB a block is a hipMalloc / hipFree per call: 15-20 ms each on MI355X, and a device-wide wait)
+  const size_t terms_side_bytes = (size_t)kNumArt * g.S * sizeof(double);
+  g.chunk_cap = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_pairs, (((size_t)1 << 30) - 64) / (2 * terms_side_bytes)));
+  return g;
+}
+
+// One call.  The ORDER of the members carries the invariant of DevLease (ltr_lease.h): the host memory queued copies read or write
+// comes first (the batch's arrays are the caller's and outlive the call) and the lease last.
+struct ShortCall {
+  ShortBatch* B; const int n_pairs;
+  std::vector<double> int_log, out; std::vector<int64_t> pout; double qtab[128];
+  ShortGeom g; ShortArgs A;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  const bool trace; const std::chrono::steady_clock::time_point t_start = std::chrono::steady_clock::now();
+  DevLease lease;
+  ShortCall(ltr_ctx* ctx, ShortBatch* b) : B(b), n_pairs((int)b->pread.size()), trace(ctx_debug(ctx).trace != 0), lease(ctx, (hipStream_t)ctx_stream(ctx)) {}
+  void mark(const char* what) const {
+    if (trace) std::fprintf(stderr, "[ltr] short_batch_run %8.2f ms: %s\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count(), what);
+  }
+};
+
+void short_host_tables(ShortCall& c) {
+  c.int_log.resize((size_t)c.B->maxHS + c.B->maxB + 16);
+  c.int_log[0] = -1000;                                                          // mathops.cpp:17
+  for (size_t i = 1; i < c.int_log.size(); i++) c.int_log[i] = std::log((double)i);
+  const int MAXQ = 'J' - '!';                                                    // BaseQuality's tables, base_quality.h:29-43
+  std::memset(c.qtab, 0, sizeof(c.qtab));
+  c.qtab[64] = -100; c.qtab[0] = 0;
+  for (int i = 1; i <= MAXQ; ++i) { c.qtab[64 + i] = std::log(1.0 - std::pow(10.0, i / (-10.0))); c.qtab[i] = std::log(std::pow(10.0, i / (-10.0) / 5.0)); }
+  c.pout.resize((size_t)c.n_pairs);
+  for (int q = 0; q < c.n_pairs; q++) c.pout[(size_t)q] = q;
+  c.out.assign((size_t)c.n_pairs, 0.0);
+}
+
+// n objects in a block of the context's pool (no hipMalloc / hipFree per call), the copy queued
+template <class T> hipError_t short_up(DevLease& lease, const T* src, size_t n, const T** dst) {
+  T* d = nullptr;
+  const hipError_t e = lease.alloc(&d, std::max<size_t>(n * sizeof(T), 8) + 64);
+  *dst = d;
+  if (e != hipSuccess) return e;
+  return n ? hipMemcpyAsync(d, src, n * sizeof(T), hipMemcpyHostToDevice, lease.st) : hipSuccess;
+}
+
+// uploads queued, work arrays allocated, every field of ShortArgs but the chunk's
+int short_upload(ltr_ctx* ctx, ShortCall& c) {
+  const ShortBatch* B = c.B; ShortArgs& A = c.A; DevLease& lease = c.lease; const ShortGeom& g = c.g;
+  std::memset(&A, 0, sizeof(A));
+  DEV_TRY(ctx, short_up(lease, B->reads.data(), B->reads.size(), &A.reads));
+  DEV_TRY(ctx, short_up(lease, B->fw.data(), B->fw.size(), &A.fw));
+  DEV_TRY(ctx, short_up(lease, B->rv.data(), B->rv.size(), &A.rv));
+  DEV_TRY(ctx, short_up(lease, B->rbytes.data(), B->rbytes.size(), &A.read_bytes));
+  DEV_TRY(ctx, short_up(lease, B->hbytes.data(), B->hbytes.size(), &A.hap_bytes));
+  DEV_TRY(ctx, short_up(lease, B->upstream.data(), B->upstream.size(), &A.upstream));
+  c.mark("tables and pairs uploaded");
+  DEV_TRY(ctx, short_up(lease, B->qidx.data(), B->qidx.size(), &A.qidx));
+  DEV_TRY(ctx, short_up(lease, (const double*)c.qtab, (size_t)128, &A.qtab));
+  DEV_TRY(ctx, lease.alloc(&A.wrong_w, B->qidx.size() * sizeof(double) + 64));
+  DEV_TRY(ctx, lease.alloc(&A.correct_w, B->qidx.size() * sizeof(double) + 64));
+  DEV_TRY(ctx, lease.alloc(&A.cum_w, (size_t)B->n_cum * sizeof(double) + 64));
+  DEV_TRY(ctx, short_up(lease, B->art.data(), B->art.size(), &A.art));
+  DEV_TRY(ctx, short_up(lease, c.int_log.data(), c.int_log.size(), &A.int_log));
+  DEV_TRY(ctx, short_up(lease, B->pread.data(), B->pread.size(), &A.pair_read));
+  DEV_TRY(ctx, short_up(lease, B->phap.data(), B->phap.size(), &A.pair_hap));
+  DEV_TRY(ctx, short_up(lease, c.pout.data(), c.pout.size(), &A.pair_out));
+  DEV_TRY(ctx, lease.alloc(&A.out, c.out.size() * sizeof(double) + 64));
+  if (!g.wave_kernel) DEV_TRY(ctx, lease.alloc(&A.scratch, (size_t)g.grid * g.per_block * sizeof(double)));
+  c.mark("uploads queued (+ work arrays allocated)");
+  const ltr_align_params prm = ctx_params(ctx);
+  A.wrong = A.wrong_w; A.correct = A.correct_w; A.cum = A.cum_w;
+  A.n_pairs = c.n_pairs; A.period = B->period; A.scratch_per_block = g.per_block;
+  A.S = g.S; A.HS = g.HS; A.LP = g.LP; A.n_ilog = (int32_t)c.int_log.size(); A.maxB = B->maxB;
+  A.a = prm.log_ins_to_ins; A.b = prm.log_ins_to_match; A.c = prm.log_del_to_del; A.d = prm.log_del_to_match;
+  A.e = prm.log_match_to_match; A.f = prm.log_match_to_ins; A.g = prm.log_match_to_del;
+  A.log_thresh = std::log(0.001);
+  A.n_reads = (int32_t)B->reads.size();
+  return LTR_OK;
+}
+
+// the four launches of every chunk of pairs (wavefront per (pair, side)); ltr_ctx_set_debug "short_split": events between the
+// launches -- the seeded path's time kernel by kernel, ltr_ctx_short_kernel_split
+int short_launch_chunks(ltr_ctx* ctx, ShortCall& c) {
+  ShortArgs& A = c.A; const ShortGeom& g = c.g; const hipStream_t st = c.lease.st; const int n_pairs = c.n_pairs;
+  DEV_TRY(ctx, c.lease.alloc(&A.g_row, (size_t)g.chunk_cap * 2 * g.S * sizeof(double) + 64));
+  DEV_TRY(ctx, c.lease.alloc(&A.g_last, (size_t)g.chunk_cap * 2 * (g.HS + 2) * sizeof(double) + 64));
+  DEV_TRY(ctx, c.lease.alloc(&A.g_terms, (size_t)g.chunk_cap * 2 * kNumArt * g.S * sizeof(double) + 64));
+  const bool split = ctx_debug(ctx).short_split != 0;
+  hipEvent_t evs[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (split) { for (hipEvent_t& e : evs) DEV_TRY(ctx, c.lease.event(&e, true)); DEV_TRY(ctx, hipEventRecord(evs[0], st)); }
+  for (int first = 0; first < n_pairs; first += g.chunk_cap) {
+    A.chunk_first = first; A.chunk_pairs = std::min(g.chunk_cap, n_pairs - first);
+    const unsigned side_blocks = (unsigned)((2 * (int64_t)A.chunk_pairs + kShortThreads / 64 - 1) / (kShortThreads / 64));
+    const unsigned pair_blocks = (unsigned)(((int64_t)A.chunk_pairs + kShortThreads / 64 - 1) / (kShortThreads / 64));
+    const unsigned block_grid = (unsigned)(2 * (int64_t)A.chunk_pairs);      // (one workgroup per (pair, side): the sides differ tenfold in length; the dispatcher balances them)
+    const bool sp = split && first == 0;                         // (the first chunk: every bounded workload is one chunk)
+    hipLaunchKernelGGL((ltr_short_flank_kernel<false>), dim3(side_blocks), dim3(kShortThreads), 0, st, A);
+    if (sp) DEV_TRY(ctx, hipEventRecord(evs[1], st));
+    hipLaunchKernelGGL(ltr_short_block_kernel, dim3(block_grid), dim3(kShortThreads), g.lds_bytes, st, A);
+    if (sp) DEV_TRY(ctx, hipEventRecord(evs[2], st));
+    hipLaunchKernelGGL((ltr_short_flank_kernel<true>), dim3(side_blocks), dim3(kShortThreads), 0, st, A);
+    if (sp) DEV_TRY(ctx, hipEventRecord(evs[3], st));
+    hipLaunchKernelGGL(ltr_short_final_kernel, dim3(pair_blocks), dim3(kShortThreads), 0, st, A);
+    if (sp) DEV_TRY(ctx, hipEventRecord(evs[4], st));
+  }
+  if (split) {
+    DEV_TRY(ctx, hipStreamSynchronize(st));
+    double ms4[4] = {0, 0, 0, 0};
+    for (int k = 0; k < 4; ++k) { float ms = 0.f; if (hipEventElapsedTime(&ms, evs[k], evs[k + 1]) == hipSuccess) ms4[k] = (double)ms; }
+    ctx_note_short_split(ctx, ms4);                              // [prep + flank rows before the block, block row, flank rows after, seed log-sum]
+  }
+  return LTR_OK;
+}
+
+// the per-read tables on the device, then the chunk launches or the lane-per-pair launch
+int short_launch(ltr_ctx* ctx, ShortCall& c) {
+  const hipStream_t st = c.lease.st;
+  DEV_TRY(ctx, c.lease.event(&c.ev0, true)); DEV_TRY(ctx, c.lease.event(&c.ev1, true));
+  DEV_TRY(ctx, hipEventRecord(c.ev0, st));
+  hipLaunchKernelGGL(ltr_short_prep_kernel, dim3((unsigned)((c.B->reads.size() + kShortThreads / 64 - 1) / (kShortThreads / 64))), dim3(kShortThreads), 0, st, c.A);
+  if (c.g.wave_kernel) { const int rc = short_launch_chunks(ctx, c); if (rc != LTR_OK) return rc; }
+  else hipLaunchKernelGGL(ltr_short_kernel, dim3((unsigned)c.g.grid), dim3(64), 0, st, c.A);
+  DEV_TRY(ctx, hipGetLastError());
+  DEV_TRY(ctx, hipEventRecord(c.ev1, st));
+  c.mark("launches queued");
+  return LTR_OK;
+}
+
+// scores back (the call's one wait), device time to the timers, every score to its queued host destination
+int short_fetch(ltr_ctx* ctx, ShortCall& c) {
+  DEV_TRY(ctx, hipMemcpyAsync(c.out.data(), c.A.out, c.out.size() * sizeof(double), hipMemcpyDeviceToHost, c.lease.st));
+  DEV_TRY(ctx, c.lease.drain());
+  c.mark("scores back");
+  { float ms = 0.f; if (hipEventElapsedTime(&ms, c.ev0, c.ev1) == hipSuccess) add_time(ctx, kTimerShortKernel, 0.0, (double)ms); }
+  for (int q = 0; q < c.n_pairs; q++) *c.B->pdst[(size_t)q] = c.out[(size_t)q];
+  return LTR_OK;
+}
+}  // namespace
+
+// One set of launches for everything queued; results go to the queued host destinations.  (Both ways here -- ltr_process_reads
+// through process_reads_short, ltr_calc_hap_aln_probs -- are inside LTR_GUARD: an exception unwinds through the lease.)
 int short_batch_run(ltr_ctx* ctx, ShortBatch* B) {
   const int64_t n_pairs64 = (int64_t)B->pread.size();
   if (n_pairs64 == 0) return LTR_OK;
   if (n_pairs64 > 0x7fffffff) { set_error(ctx, "short path: too many pairs in one batch"); return LTR_ERR_INVALID; }
-  const int n_pairs = (int)n_pairs64;
-  const ltr_align_params prm = ctx_params(ctx);
-  int rc = LTR_OK;
-  std::vector<double> int_log((size_t)B->maxHS + B->maxB + 16);
-  int_log[0] = -1000;                                                            // mathops.cpp:17
-  for (size_t i = 1; i < int_log.size(); i++) int_log[i] = std::log((double)i);
-  double qtab[128];                                                               // BaseQuality's tables, base_quality.h:29-43
-  {
-    const int MAXQ = 'J' - '!';
-    std::memset(qtab, 0, sizeof(qtab));
-    qtab[64] = -100; qtab[0] = 0;
-    for (int i = 1; i <= MAXQ; ++i) { qtab[64 + i] = std::log(1.0 - std::pow(10.0, i / (-10.0))); qtab[i] = std::log(std::pow(10.0, i / (-10.0) / 5.0)); }
-  }
-  std::vector<int64_t> pout((size_t)n_pairs);
-  for (int q = 0; q < n_pairs; q++) pout[(size_t)q] = q;
-
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  const bool trace = ctx_debug(ctx).trace != 0;
-  const auto t_start = std::chrono::steady_clock::now();
-  auto mark = [&](const char* what) {
-    if (trace) std::fprintf(stderr, "[ltr] short_batch_run %8.2f ms: %s\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count(), what);
-  };
-  ShortArgs A; std::memset(&A, 0, sizeof(A));
-  void* d[24] = {nullptr}; int nd_alloc = 0;
-  std::vector<double> out((size_t)n_pairs, 0.0);
-  hipStream_t st = (hipStream_t)ctx_stream(ctx);
-  const int S = std::max(B->maxS, std::max(B->maxB + 2, kNumArt)) + 2, HS = B->maxHS + 4;
-  const int LP = std::max(S, HS) + 8;
-  const int64_t per_block = (int64_t)(19 * S + LP + 2 * (HS + 2)) * 64;
-  // one wave per block; enough blocks to keep a few waves per SIMD busy with other pairs while a
-  // lane waits for its work arrays (scratch capped at 8 GB)
-  const int64_t cap_blocks = std::max<int64_t>(1, ((int64_t)8 << 30) / (per_block * (int64_t)sizeof(double)));
-  const int grid = (int)std::min<int64_t>(std::min<int64_t>((n_pairs + 63) / 64, 4096), cap_blocks);
+  ShortCall c(ctx, B);
+  short_host_tables(c);
+  c.g = short_geometry(*B, c.n_pairs, c.int_log.size(), ctx_debug(ctx).short_lane_kernel != 0);
   (void)hipSetDevice(ctx_device(ctx));
-  auto up = [&](const void* src, size_t bytes, void** dst) -> hipError_t {
-    hipError_t e = (hipError_t)ctx_pool_alloc(ctx, dst, std::max<size_t>(bytes, 8) + 64);      // (the context's pool: no hipMalloc / hipFree per call)
-    if (e != hipSuccess) return e;
-    d[nd_alloc++] = *dst;
-    return bytes ? hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
-  };
-  void *p_reads, *p_fw, *p_rv, *p_rb, *p_hb, *p_up, *p_w, *p_c, *p_art, *p_il, *p_pr, *p_ph, *p_po, *p_out, *p_scr = nullptr, *p_cum, *p_qi, *p_qt;
-  // The four-launch path whenever a side fits 64 lanes x 8 read positions and the block kernel's tables fit 64 KB of LDS;
-  // beyond that (reads cut wider than the reference's +-200 bp) the lane-per-pair kernel with its global work arrays.
-  const int maxS = std::max(B->maxS, 1);
-  const size_t lds_bytes = ((size_t)4 * S + int_log.size()) * sizeof(double) + ((size_t)kMaxDel * B->maxB + 8) * sizeof(int32_t) +
-                           (size_t)((S + 7) & ~7) + (size_t)HS + 64;
-  const bool wave_kernel = maxS <= 64 * 8 && lds_bytes <= 64 * 1024 && !ctx_debug(ctx).short_lane_kernel;
-  // pairs per set of launches: the block row's terms (13 x S doubles per side) fit ONE GB -- a block the context's pool keeps
-  // between calls (beyond 2 GB a block is a hipMalloc / hipFree per call: 15-20 ms each on MI355X, and a device-wide wait)
-  const size_t terms_side_bytes = (size_t)kNumArt * S * sizeof(double);
-  const int chunk_cap = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_pairs, (((size_t)1 << 30) - 64) / (2 * terms_side_bytes)));
-  void *p_row = nullptr, *p_last = nullptr, *p_terms = nullptr;
-  mark("start");
-  S_TRY(up(B->reads.data(), B->reads.size() * sizeof(ShortRead), &p_reads));
-  S_TRY(up(B->fw.data(), B->fw.size() * sizeof(ShortHap), &p_fw));
-  S_TRY(up(B->rv.data(), B->rv.size() * sizeof(ShortHap), &p_rv));
-  S_TRY(up(B->rbytes.data(), B->rbytes.size(), &p_rb));
-  S_TRY(up(B->hbytes.data(), B->hbytes.size(), &p_hb));
-  S_TRY(up(B->upstream.data(), B->upstream.size() * sizeof(int32_t), &p_up));
-  mark("tables and pairs uploaded");
-  S_TRY(up(B->qidx.data(), B->qidx.size(), &p_qi));
-  S_TRY(up(qtab, sizeof(qtab), &p_qt));
-  S_TRY((hipError_t)ctx_pool_alloc(ctx, &p_w, B->qidx.size() * sizeof(double) + 64)); d[nd_alloc++] = p_w;
-  S_TRY((hipError_t)ctx_pool_alloc(ctx, &p_c, B->qidx.size() * sizeof(double) + 64)); d[nd_alloc++] = p_c;
-  S_TRY((hipError_t)ctx_pool_alloc(ctx, &p_cum, (size_t)B->n_cum * sizeof(double) + 64)); d[nd_alloc++] = p_cum;
-  S_TRY(up(B->art.data(), B->art.size() * sizeof(double), &p_art));
-  S_TRY(up(int_log.data(), int_log.size() * sizeof(double), &p_il));
-  S_TRY(up(B->pread.data(), B->pread.size() * sizeof(int32_t), &p_pr));
-  S_TRY(up(B->phap.data(), B->phap.size() * sizeof(int32_t), &p_ph));
-  S_TRY(up(pout.data(), pout.size() * sizeof(int64_t), &p_po));
-  S_TRY((hipError_t)ctx_pool_alloc(ctx, &p_out, out.size() * sizeof(double) + 64)); d[nd_alloc++] = p_out;
-  if (!wave_kernel) { S_TRY((hipError_t)ctx_pool_alloc(ctx, &p_scr, (size_t)grid * per_block * sizeof(double))); d[nd_alloc++] = p_scr; }
-  mark("uploads queued (+ work arrays allocated)");
-  A.reads = (const ShortRead*)p_reads; A.fw = (const ShortHap*)p_fw; A.rv = (const ShortHap*)p_rv;
-  A.read_bytes = (const uint8_t*)p_rb; A.hap_bytes = (const uint8_t*)p_hb; A.upstream = (const int32_t*)p_up;
-  A.wrong = (const double*)p_w; A.correct = (const double*)p_c; A.cum = (const double*)p_cum; A.art = (const double*)p_art; A.int_log = (const double*)p_il;
-  A.pair_read = (const int32_t*)p_pr; A.pair_hap = (const int32_t*)p_ph; A.pair_out = (const int64_t*)p_po;
-  A.n_pairs = n_pairs; A.period = B->period; A.out = (double*)p_out; A.scratch = (double*)p_scr; A.scratch_per_block = per_block;
-  A.S = S; A.HS = HS; A.LP = LP; A.n_ilog = (int32_t)int_log.size(); A.maxB = B->maxB;
-  A.a = prm.log_ins_to_ins; A.b = prm.log_ins_to_match; A.c = prm.log_del_to_del; A.d = prm.log_del_to_match;
-  A.e = prm.log_match_to_match; A.f = prm.log_match_to_ins; A.g = prm.log_match_to_del;
-  A.log_thresh = std::log(0.001);
-  A.qidx = (const uint8_t*)p_qi; A.qtab = (const double*)p_qt; A.wrong_w = (double*)p_w; A.correct_w = (double*)p_c; A.cum_w = (double*)p_cum;
-  A.n_reads = (int32_t)B->reads.size();
-  S_TRY(hipEventCreate(&ev0)); S_TRY(hipEventCreate(&ev1));
-  S_TRY(hipEventRecord(ev0, st));
-  hipLaunchKernelGGL(ltr_short_prep_kernel, dim3((unsigned)((B->reads.size() + kShortThreads / 64 - 1) / (kShortThreads / 64))), dim3(kShortThreads), 0, st, A);
-  if (wave_kernel) {
-    S_TRY((hipError_t)ctx_pool_alloc(ctx, &p_row, (size_t)chunk_cap * 2 * S * sizeof(double) + 64)); d[nd_alloc++] = p_row;
-    S_TRY((hipError_t)ctx_pool_alloc(ctx, &p_last, (size_t)chunk_cap * 2 * (HS + 2) * sizeof(double) + 64)); d[nd_alloc++] = p_last;
-    S_TRY((hipError_t)ctx_pool_alloc(ctx, &p_terms, (size_t)chunk_cap * 2 * kNumArt * S * sizeof(double) + 64)); d[nd_alloc++] = p_terms;
-    A.g_row = (double*)p_row; A.g_last = (double*)p_last; A.g_terms = (double*)p_terms;
-    // (ltr_ctx_set_debug "short_split": events between the five launches -- the seeded path's time kernel by kernel, ltr_ctx_short_kernel_split)
-    const bool split = ctx_debug(ctx).short_split != 0;
-    hipEvent_t evs[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (split) { for (hipEvent_t& e : evs) S_TRY(hipEventCreate(&e)); S_TRY(hipEventRecord(evs[0], st)); }
-    for (int first = 0; first < n_pairs; first += chunk_cap) {
-      A.chunk_first = first; A.chunk_pairs = std::min(chunk_cap, n_pairs - first);
-      const unsigned side_blocks = (unsigned)((2 * (int64_t)A.chunk_pairs + kShortThreads / 64 - 1) / (kShortThreads / 64));
-      const unsigned pair_blocks = (unsigned)(((int64_t)A.chunk_pairs + kShortThreads / 64 - 1) / (kShortThreads / 64));
-      const unsigned block_grid = (unsigned)(2 * (int64_t)A.chunk_pairs);      // (one workgroup per (pair, side): the sides differ tenfold in length; the dispatcher balances them)
-      const bool sp = split && first == 0;                         // (the first chunk: every bounded workload is one chunk)
-      hipLaunchKernelGGL((ltr_short_flank_kernel<false>), dim3(side_blocks), dim3(kShortThreads), 0, st, A);
-      if (sp) S_TRY(hipEventRecord(evs[1], st));
-      hipLaunchKernelGGL(ltr_short_block_kernel, dim3(block_grid), dim3(kShortThreads), lds_bytes, st, A);
-      if (sp) S_TRY(hipEventRecord(evs[2], st));
-      hipLaunchKernelGGL((ltr_short_flank_kernel<true>), dim3(side_blocks), dim3(kShortThreads), 0, st, A);
-      if (sp) S_TRY(hipEventRecord(evs[3], st));
-      hipLaunchKernelGGL(ltr_short_final_kernel, dim3(pair_blocks), dim3(kShortThreads), 0, st, A);
-      if (sp) S_TRY(hipEventRecord(evs[4], st));
-    }
-    if (split) {
-      S_TRY(hipStreamSynchronize(st));
-      double ms4[4] = {0, 0, 0, 0};
-      for (int k = 0; k < 4; ++k) { float ms = 0.f; if (hipEventElapsedTime(&ms, evs[k], evs[k + 1]) == hipSuccess) ms4[k] = (double)ms; }
-      ctx_note_short_split(ctx, ms4);                              // [prep + flank rows before the block, block row, flank rows after, seed log-sum]
-      for (hipEvent_t& e : evs) if (e) (void)hipEventDestroy(e);
-    }
-  } else
-  hipLaunchKernelGGL(ltr_short_kernel, dim3((unsigned)grid), dim3(64), 0, st, A);
-  S_TRY(hipGetLastError());
-  S_TRY(hipEventRecord(ev1, st));
-  mark("launches queued");
-  S_TRY(hipMemcpyAsync(out.data(), p_out, out.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-  S_TRY(hipStreamSynchronize(st));
-  mark("scores back");
-  { float ms = 0.f; if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) add_time(ctx, kTimerShortKernel, 0.0, (double)ms); }
-  for (int q = 0; q < n_pairs; q++) *B->pdst[(size_t)q] = out[(size_t)q];
-done:
-  if (rc != LTR_OK) (void)hipStreamSynchronize(st);                              // (nothing in flight may still use the blocks)
-  for (int i = 0; i < nd_alloc; i++) ctx_pool_release(ctx, d[i]);
-  if (ev0) (void)hipEventDestroy(ev0);
-  if (ev1) (void)hipEventDestroy(ev1);
+  c.mark("start");
+  int rc = short_upload(ctx, c);
+  if (rc == LTR_OK) rc = short_launch(ctx, c);
+  if (rc == LTR_OK) rc = short_fetch(ctx, c);
   return rc;
 }
 

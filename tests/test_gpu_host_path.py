@@ -117,6 +117,54 @@ def test_short_path_matches_oracle_bit_for_bit(gpu_ctx, seed):
         gpu_ctx.set_params(_abi.default_params())
 
 
+@pytest.mark.parametrize("shape", [(8, 2, 4), (25, 4, 6)])
+def test_short_path_lane_per_pair_kernel(gpu_ctx, shape):
+    """ltr_ctx_set_debug "short_lane_kernel": the lane-per-pair kernel with its scratch strips in global memory (the path reads cut
+    wider than 512 bases a side take) gives the bits of the restatement and of the four-launch path."""
+    import short_util as su
+    tr, H, R = shape
+    blocks, alns = su.homopolymer_locus(np.random.default_rng(36), tr, H, R)
+    gpu_ctx.set_params(_short_params())
+    try:
+        wave, _ = gpu_ctx.process_reads(blocks, alns)
+        gpu_ctx.set_debug("short_lane_kernel", 1)
+        try:
+            lane, seeds = gpu_ctx.process_reads(blocks, alns)
+        finally:
+            gpu_ctx.set_debug("short_lane_kernel", 0)
+    finally:
+        gpu_ctx.set_params(_abi.default_params())
+    rc, want, ws = ol.oracle_process_reads_short(_short_params(), _abi.default_stutter_params(), blocks, alns)
+    assert rc == 0 and np.isfinite(want).all()
+    assert np.array_equal(bits(lane), bits(want)) and np.array_equal(seeds, ws)
+    assert np.array_equal(bits(lane), bits(wave))
+
+
+def test_short_path_split_events(gpu_ctx):
+    """ltr_ctx_set_debug "short_split": events between the launches change no bit, ltr_ctx_short_kernel_split hands their four
+    device times out once, and the call's own timer still runs."""
+    import short_util as su
+    blocks, alns = su.homopolymer_locus(np.random.default_rng(37), 14, 3, 6)
+    gpu_ctx.set_params(_short_params())
+    try:
+        off, _ = gpu_ctx.process_reads(blocks, alns)
+        gpu_ctx.short_kernel_split(reset=True)
+        gpu_ctx.timers(reset=True)
+        gpu_ctx.set_debug("short_split", 1)
+        try:
+            on, _ = gpu_ctx.process_reads(blocks, alns)
+        finally:
+            gpu_ctx.set_debug("short_split", 0)
+        split, again = gpu_ctx.short_kernel_split(reset=True), gpu_ctx.short_kernel_split(reset=True)
+        tm = gpu_ctx.timers(reset=True)
+    finally:
+        gpu_ctx.set_params(_abi.default_params())
+    assert np.isfinite(off).all() and np.array_equal(bits(on), bits(off))
+    assert len(split) == 4 and all(ms > 0 for ms in split), split
+    assert again == [0.0, 0.0, 0.0, 0.0]
+    assert tm["short_kernel_ms"] > 0
+
+
 def test_short_path_only_for_period_one(gpu_ctx):
     # --stutter-align-len set but period 3: the reference takes the LONG path (HapAligner.cpp:552)
     rng = np.random.default_rng(24)

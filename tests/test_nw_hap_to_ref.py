@@ -94,3 +94,22 @@ def test_gpu_kernel_equals_restatement(gpu_ctx):
     tm = gpu_ctx.timers(reset=True)
     assert tm["hap_build_calls"] >= 1 and tm["hap_build_s"] > 0
     assert tm["nw_kernel_ms"] > 0 and tm["nw_kernel_ms"] < tm["hap_build_s"] * 1e3     # device time of the NW kernels, inside the call's wall time
+
+
+@pytest.mark.gpu
+def test_gpu_output_buffer_too_small_then_reuse(gpu_ctx):
+    """A status return AFTER the launches (the capacity check follows the download; nothing faults): every class has run -- strip
+    widths 4 and 8, the workgroup kernel -- the error is the library's, and the same context then gives the right strings."""
+    from longtr_amd import _abi, _lib
+    rng = np.random.default_rng(83)
+    loci = [synth.synth_locus(rng, tr, period, 3, 1) for tr, period in ((40, 3), (300, 7), (1400, 17))]
+    packed = gpu_ctx.pack_haplotypes([L.blocks() for L in loci])
+    with pytest.raises(_lib.LtrError) as e:
+        gpu_ctx.haplotype_align_to_ref_packed(dict(packed, cap=1))
+    assert e.value.code == _abi.LTR_ERR_INVALID and "output buffer too small" in str(e.value)
+    got = gpu_ctx.haplotype_align_to_ref_packed(packed)
+    for L, infos in zip(loci, got):
+        haps = L.haplotypes
+        assert len(infos) == len(haps)
+        for h, info in zip(haps, infos):
+            assert info == ol.oracle_nw_aln_info(haps[0], h, L.start, L.start + len(L.lflank)), (len(haps[0]), len(h))
