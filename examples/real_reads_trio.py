@@ -113,7 +113,20 @@ def plan_genotype(ctx, todo, device_fields=False):
     return out
 
 
-def run(ctx, vcf_path=None, max_loci=None, tmp_dir="/tmp", ref_vcf=None, prune=False, device_fields=False):
+def ll_genotype(ctx, todo):
+    """No plan: the per-read matrices and seed positions ltr_calc_hap_aln_probs returns go straight into ltr_ll_genotype (pruning
+    and the fields of every record on the device) -- the GenotypeResult itself (the caller closes it)."""
+    res = ctx.calc_hap_aln_probs([(l["blocks"], l["alns"], None) for l in todo])
+    lro, p1s, p2s, labs = [0], [], [], []
+    for l in todo:
+        p1, p2 = phasing_priors(l["sample"], l["hp"])
+        p1s += list(p1); p2s += list(p2); labs += list(l["sample"])
+        lro.append(lro[-1] + len(l["alns"]))
+    return ctx.genotype_ll([m for m, _ in res], [s for _, s in res], [l["blocks"] for l in todo], lro, p1s, p2s, labs,
+                           [len(SAMPLES)] * len(todo), prune=True, fields={})
+
+
+def run(ctx, vcf_path=None, max_loci=None, tmp_dir="/tmp", ref_vcf=None, prune=False, device_fields=False, from_ll=False):
     """ref_vcf: a bgzipped, tabix-indexed VCF whose records give the candidate alleles (--ref-vcf: read_vcf_alleles,
     add_vcf_haplotype_block); a locus without a record gets the status "no panel record".
     prune: discovery mode as the reference runs it (seq_stutter_genotyper.cpp:636-645) -- alleles no sample carries in its best
@@ -121,7 +134,9 @@ def run(ctx, vcf_path=None, max_loci=None, tmp_dir="/tmp", ref_vcf=None, prune=F
     record lists only called ALT alleles and Q is normalised over the diplotypes LongTR keeps.  With ref_vcf nothing is
     pruned, as in the reference (:636).  Default off: every candidate allele stays in the record.
     device_fields (with prune): the numbers of every record (GT, Q, PQ, GLDIFF, DP, DSNP, PSNP, MALLREADS) are computed on the
-    device by ltr_plan_genotype_fields and all records formatted by one ltr_genotype_result_vcf_records call."""
+    device by ltr_plan_genotype_fields and all records formatted by one ltr_genotype_result_vcf_records call.
+    from_ll (with prune and device_fields): no resident plan -- ltr_calc_hap_aln_probs scores the reads as in the default run and its
+    matrices and seed positions are handed to ltr_ll_genotype, which does the rest of device_fields on them."""
     bed = os.path.join(tmp_dir, f"ltr_regions_{os.getpid()}.bed")
     convert_bed(os.path.join(DATA, "test_regions_hg38.bed"), bed)
     regions, _ = _lib.read_regions(bed, order=True)
@@ -167,8 +182,10 @@ def run(ctx, vcf_path=None, max_loci=None, tmp_dir="/tmp", ref_vcf=None, prune=F
     # one GPU pass for every locus: ltr_calc_hap_aln_probs, or -- pruning -- a resident plan and ltr_plan_genotype on it
     if device_fields and (not prune or panel is not None):
         raise ValueError("device_fields needs prune=True and no ref_vcf: it is the plan path (ltr_plan_genotype_fields)")
+    if from_ll and not device_fields:
+        raise ValueError("from_ll is a form of device_fields: ltr_ll_genotype on the output of ltr_calc_hap_aln_probs")
     if device_fields and todo:
-        return _run_device_fields(ctx, loci, todo, vcf_path)
+        return _run_device_fields(ctx, loci, todo, vcf_path, from_ll)
     final = plan_genotype(ctx, todo) if prune and panel is None and todo else None
     res = ctx.calc_hap_aln_probs([(l["blocks"], l["alns"], None) for l in todo]) if final is None else [(g["read_ll"], None) for g in final]
     writer = _lib.VcfWriter(vcf_path) if vcf_path else None
@@ -204,10 +221,10 @@ def run(ctx, vcf_path=None, max_loci=None, tmp_dir="/tmp", ref_vcf=None, prune=F
     return loci
 
 
-def _run_device_fields(ctx, loci, todo, vcf_path):
+def _run_device_fields(ctx, loci, todo, vcf_path, from_ll=False):
     """The pruned run with the fields of every record from the device and one formatting call for all records."""
     none = np.zeros(0)
-    with plan_genotype(ctx, todo, device_fields=True) as result:
+    with (ll_genotype(ctx, todo) if from_ll else plan_genotype(ctx, todo, device_fields=True)) as result:
         pvs = []
         for k, l in enumerate(todo):
             g = result.locus(k)
@@ -243,9 +260,10 @@ def main():
     ap.add_argument("--ref-vcf", default=None, metavar="PATH", help="bgzipped, tabix-indexed VCF of candidate alleles (LongTR's --ref-vcf)")
     ap.add_argument("--prune-alleles", action="store_true", help="remove the alleles no sample is called with and genotype again (the reference's discovery mode)")
     ap.add_argument("--device-fields", action="store_true", help="needs --prune-alleles, not with --ref-vcf: the records' numbers from the device, all records formatted in one call")
+    ap.add_argument("--from-ll", action="store_true", help="with --device-fields: no resident plan, the matrices of ltr_calc_hap_aln_probs go into ltr_ll_genotype")
     args = ap.parse_args()
     ctx = _lib.Context(0)
-    loci = run(ctx, args.out, ref_vcf=args.ref_vcf, prune=args.prune_alleles, device_fields=args.device_fields)
+    loci = run(ctx, args.out, ref_vcf=args.ref_vcf, prune=args.prune_alleles, device_fields=args.device_fields, from_ll=args.from_ll)
     for l in loci:
         if l["status"] != "ok":
             print(f"{l['region']['name']:>16} {l['region']['chrom']}:{l['region']['start']}-{l['region']['stop']}  skipped: {l['status']}")

@@ -646,6 +646,26 @@ typedef struct ltr_fields_request {
   int32_t want_posteriors;     /* 0: the S x H' x H' blocks are NOT downloaded (ltr_genotype_result_log_sample_posteriors returns NULL) */
 } ltr_fields_request;
 int ltr_plan_genotype_fields(ltr_plan* plan, const ltr_genotype_batch* gb, const ltr_fields_request* fr, ltr_genotype_result** out);
+/* The same consumer WITHOUT a plan: ltr_plan_genotype (fr == NULL) or ltr_plan_genotype_fields (fr given) on per-read matrices in
+ * caller memory -- what ltr_calc_hap_aln_probs returns, the state of SeqStutterGenotyper at seq_stutter_genotyper.cpp:634, also
+ * after the seeded stutter path, with mate rows summed (:546-559) or re-scored under realign_* masks.  Every read is its own row:
+ *   gb            as for ltr_plan_genotype[_fields], except that gb->pb->pool_index is not read (may be NULL); gb->haps[l] must
+ *                 enumerate n_haps[l] combinations (checked whenever the block lists are read: prune != 0 or fr given)
+ *   aligned_read  of get_unused_alleles (:262-266): seed_positions[l][read] >= 0
+ * The matrices are never written (ltr_posteriors clamps its input in place; here the clamp at -600 happens on the device copy).
+ * They are gathered into pinned staging by the worker pool under the host-thread budget and uploaded in chunks on the context's
+ * stream, chunk k + 1 being gathered while chunk k is copied; the block stays on the device for the whole call.
+ * The result is the same object: every accessor above and below works on it; new_to_old indexes the caller's columns, read_ll
+ * (want_read_ll) is the caller's matrix clamped and re-mapped; the same bits as the plan path on the same scores.
+ * Errors as ltr_plan_genotype: LTR_ERR_INVALID + ltr_last_error (the locus named), nothing launched, *out left NULL.
+ * The context must outlive the result. */
+typedef struct ltr_ll_batch {
+  const double*  const* log_aln_probs;   /* [n_loci] R_l x H_l per READ, host memory, never written (NULL allowed for a locus without reads) */
+  const int32_t* const* seed_positions;  /* [n_loci] R_l; NULL, or a NULL entry = every read aligned */
+  const int32_t*        n_haps;          /* [n_loci] H_l */
+} ltr_ll_batch;
+int ltr_ll_genotype(ltr_ctx* ctx, const ltr_ll_batch* lb, const ltr_genotype_batch* gb,
+                    const ltr_fields_request* fr /* NULL = as ltr_plan_genotype */, ltr_genotype_result** out);
 /* views into the result (LTR_ERR_INVALID for a result of ltr_plan_genotype, which has none) */
 int ltr_genotype_result_fields(const ltr_genotype_result* r, int64_t l, ltr_locus_fields* out);
 

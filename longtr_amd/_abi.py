@@ -169,6 +169,13 @@ class FieldsRequest(C.Structure):
                 ("want_posteriors", C.c_int32)]
 
 
+class LlBatch(C.Structure):
+    """struct ltr_ll_batch."""
+
+    _fields_ = [("log_aln_probs", C.POINTER(C.POINTER(C.c_double))), ("seed_positions", C.POINTER(C.POINTER(C.c_int32))),
+                ("n_haps", C.POINTER(C.c_int32))]
+
+
 class LocusFields(C.Structure):
     """struct ltr_locus_fields."""
 

@@ -46,7 +46,7 @@ EXPORTS = [
     "ltr_genotype_result_num_aff_alleles", "ltr_genotype_result_blocks", "ltr_genotype_result_log_sample_posteriors",
     "ltr_genotype_result_sample_total_ll", "ltr_genotype_result_gts", "ltr_genotype_result_read_ll",
     "ltr_plan_genotype_fields", "ltr_genotype_result_fields", "ltr_genotype_result_vcf_records", "ltr_vcf_text_free",
-    "ltr_vcf_fields", "ltr_vcf_field_set_view", "ltr_vcf_field_set_free", "ltr_vcf_record_from_fields",
+    "ltr_vcf_fields", "ltr_vcf_field_set_view", "ltr_vcf_field_set_free", "ltr_vcf_record_from_fields", "ltr_ll_genotype",
 ]
 
 
@@ -359,6 +359,73 @@ class Context:
                                          _p(post), _p(stl), _p(gts), C.byref(tot)))
         return dict(post=post.reshape(n_samples, H, H), sample_total_ll=stl, gts=gts.reshape(n_samples, 2),
                     total_ll=tot.value, clamped_ll=ll)
+
+    def pack_ll_genotype(self, ll_list, seed_list, loci_blocks, locus_read_off, log_p1, log_p2, sample_label, n_samples, haploid=False,
+                         prune=True, want_read_ll=False, sample_filtered=None):
+        """ctypes image of the ltr_ll_batch + ltr_genotype_batch of genotype_ll (for repeated calls).  ll_list: per locus the
+        [R_l x H_l] matrix (float64, C order: used where it lies, never written) or None for a locus without reads; seed_list:
+        None, or per locus the [R_l] seed positions or None (= every read aligned); loci_blocks: per locus the block list, or
+        None altogether (prune=False without fields)."""
+        n = len(n_samples)
+        lro = np.ascontiguousarray(locus_read_off, dtype=np.int64)
+        keep = [lro, None, np.ascontiguousarray(log_p1, dtype=np.float64), np.ascontiguousarray(log_p2, dtype=np.float64),
+                np.ascontiguousarray(sample_label, dtype=np.int32), np.ascontiguousarray(n_samples, dtype=np.int32)]
+        pb = _abi.PosteriorBatch()
+        pb.n_loci, pb.n_reads, pb.haploid = n, len(keep[4]), int(haploid)
+        pb.locus_read_off = lro.ctypes.data_as(C.POINTER(C.c_int64))
+        pb.log_p1, pb.log_p2 = keep[2].ctypes.data_as(C.POINTER(C.c_double)), keep[3].ctypes.data_as(C.POINTER(C.c_double))
+        pb.sample_label, pb.n_samples = keep[4].ctypes.data_as(C.POINTER(C.c_int32)), keep[5].ctypes.data_as(C.POINTER(C.c_int32))
+        if len(ll_list) != n or (seed_list is not None and len(seed_list) != n) or (loci_blocks is not None and len(loci_blocks) != n):
+            raise LtrError(_abi.LTR_ERR_INVALID, "genotype_ll: one matrix / seed array / block list per locus")
+        mats = [None if m is None else np.ascontiguousarray(m, dtype=np.float64) for m in ll_list]
+        for l, m in enumerate(mats):
+            if m is not None and (m.ndim != 2 or m.shape[0] != lro[l + 1] - lro[l]):
+                raise LtrError(_abi.LTR_ERR_INVALID, f"genotype_ll: matrix of locus {l} is not [reads x haplotypes]")
+        if loci_blocks is not None:
+            n_haps = np.asarray([int(np.prod([len(b["alleles"]) for b in bl], dtype=np.int64)) if m is None else m.shape[1]
+                                 for m, bl in zip(mats, loci_blocks)], dtype=np.int32)
+        else:
+            n_haps = np.asarray([1 if m is None else m.shape[1] for m in mats], dtype=np.int32)
+        seeds = None if seed_list is None else [None if s is None else np.ascontiguousarray(s, dtype=np.int32) for s in seed_list]
+        lb = _abi.LlBatch()
+        mp = (C.POINTER(C.c_double) * max(n, 1))(*[None if m is None else m.ctypes.data_as(C.POINTER(C.c_double)) for m in mats])
+        sp = None if seeds is None else (C.POINTER(C.c_int32) * max(n, 1))(*[None if s is None else s.ctypes.data_as(C.POINTER(C.c_int32)) for s in seeds])
+        lb.log_aln_probs, lb.seed_positions, lb.n_haps = mp, sp, n_haps.ctypes.data_as(C.POINTER(C.c_int32))
+        phs = [] if loci_blocks is None else [_abi.PackedHaplotype(b) for b in loci_blocks]
+        arr = None if loci_blocks is None else (C.POINTER(_abi.HaplotypeBlocks) * max(n, 1))(*[C.pointer(p.struct) for p in phs])
+        sf = None if sample_filtered is None else np.ascontiguousarray(sample_filtered, dtype=np.uint8)
+        gb = _abi.GenotypeBatch()
+        gb.pb, gb.haps = C.pointer(pb), arr
+        gb.sample_filtered = sf.ctypes.data_as(C.POINTER(C.c_uint8)) if sf is not None else None
+        gb.prune, gb.want_read_ll = int(bool(prune)), int(bool(want_read_ll))
+        return dict(gb=gb, lb=lb, keep=(pb, keep, mats, seeds, n_haps, mp, sp, phs, arr, sf), n_samples=keep[5], locus_read_off=lro,
+                    loci_blocks=loci_blocks if loci_blocks is not None else [[dict(alleles=[b""] * int(h))] for h in n_haps])
+
+    def genotype_ll(self, ll_list=None, seed_list=None, loci_blocks=None, locus_read_off=None, log_p1=None, log_p2=None, sample_label=None,
+                    n_samples=None, haploid=False, prune=True, want_read_ll=False, fields=None, sample_filtered=None, packed=None):
+        """ltr_ll_genotype: what Plan.genotype / Plan.genotype_fields do for a resident plan, on per-read matrices in host
+        memory -- the output of calc_hap_aln_probs (any path: plans, the seeded stutter path, mates summed, realign masks).
+        fields: None = no VCF fields (as Plan.genotype; posterior blocks are downloaded), or a dict with any of block,
+        want_gls, want_pls, want_phased_gls, want_posteriors (as Plan.genotype_fields).  packed: a pack_ll_genotype image.
+        Returns a GenotypeResult (close() it, or use it as a context manager)."""
+        if packed is None:
+            packed = self.pack_ll_genotype(ll_list, seed_list, loci_blocks, locus_read_off, log_p1, log_p2, sample_label, n_samples, haploid,
+                                           prune, want_read_ll, sample_filtered)
+        L = lib()
+        _bind_genotype(L)
+        fr, blk = None, None
+        if fields is not None:
+            fr = _abi.FieldsRequest()
+            if fields.get("block") is not None:
+                blk = np.ascontiguousarray(fields["block"], dtype=np.int32)
+                if len(blk) != len(packed["n_samples"]):
+                    raise LtrError(_abi.LTR_ERR_INVALID, "genotype_ll: one block index per locus")
+                fr.block = blk.ctypes.data_as(C.POINTER(C.c_int32))
+            for k in ("want_gls", "want_pls", "want_phased_gls", "want_posteriors"):
+                setattr(fr, k, int(bool(fields.get(k, False))))
+        h = C.c_void_p()
+        self._check(L.ltr_ll_genotype(self._h, C.byref(packed["lb"]), C.byref(packed["gb"]), None if fr is None else C.byref(fr), C.byref(h)))
+        return GenotypeResult(self, h, packed)
 
     def close(self):
         if self._h:
@@ -1121,7 +1188,7 @@ def vcf_record_from_fields(packed_vcf_locus, fields, options=None):
 
 
 class GenotypeResult:
-    """A ltr_genotype_result of Plan.genotype_fields, kept on the library's side until close()."""
+    """A ltr_genotype_result of Plan.genotype_fields / Context.genotype_ll, kept on the library's side until close()."""
 
     def __init__(self, ctx, handle, packed):
         self.ctx, self._h, self._packed = ctx, handle, packed
@@ -1210,6 +1277,7 @@ def _bind_genotype(L):
         fn.argtypes, fn.restype = [vp, i64], rt
     L.ltr_genotype_result_removed.argtypes, L.ltr_genotype_result_removed.restype = [vp, i64, i32, C.POINTER(C.POINTER(i32))], i32
     L.ltr_plan_genotype_fields.argtypes = [vp, C.POINTER(_abi.GenotypeBatch), C.POINTER(_abi.FieldsRequest), C.POINTER(vp)]
+    L.ltr_ll_genotype.argtypes = [vp, C.POINTER(_abi.LlBatch), C.POINTER(_abi.GenotypeBatch), C.POINTER(_abi.FieldsRequest), C.POINTER(vp)]
     L.ltr_genotype_result_fields.argtypes = [vp, i64, C.POINTER(_abi.LocusFields)]
     L.ltr_genotype_result_vcf_records.argtypes = [vp, C.POINTER(_abi.VcfLocus), C.POINTER(_abi.VcfOptions), C.POINTER(vp), vp, vp]
     L.ltr_vcf_text_free.argtypes, L.ltr_vcf_text_free.restype = [vp], None

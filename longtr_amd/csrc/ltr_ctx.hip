@@ -233,6 +233,7 @@ int ltr_ctx_set_debug(ltr_ctx* ctx, const char* key, double value) {
     if (k == "reset") ctx->dbg = ltr::DebugKnobs();
   }
   else if (k == "short_lane_kernel") ctx->dbg.short_lane_kernel = (int)value;
+  else if (k == "ll_chunk_loci") ctx->dbg.ll_chunk_loci = (int64_t)value;
   else { ltr::set_error(ctx, "ltr_ctx_set_debug: unknown key " + k); return LTR_ERR_INVALID; }
   return LTR_OK;
 }

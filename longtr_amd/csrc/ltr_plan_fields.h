@@ -44,8 +44,9 @@ struct DevPass { double* post = nullptr; double* stl = nullptr; int* gts = nullp
 
 #pragma GCC visibility push(hidden)
 // The fields stage of ltr_plan_genotype_fields (ltr_plan_fields.hip): layout, tables, the kernel on the passes' buffers where they
-// lie, copies into res.  pass[0] / pass[1]: the first / second pass; d_map: the column maps of the pruned loci (null: none).
-int ltr_plan_fields_stage(ltr_plan* plan, const ltr_genotype_batch* gb, const ltr_fields_request* fr, ltr_genotype_result* res,
+// lie, copies into res.  src: where the scores lie (the plan's buffer, or the per-read block of ltr_ll_genotype); pass[0] /
+// pass[1]: the first / second pass; d_map: the column maps of the pruned loci (null: none).
+int ltr_plan_fields_stage(ltr_ctx* ctx, const LlSource& src, const ltr_genotype_batch* gb, const ltr_fields_request* fr, ltr_genotype_result* res,
                           const DevReads& rd, const int32_t* d_map, const DevPass pass[2], DevLease& lease);
 // ... of a batch without a single sample: the per-locus sizes, nothing to compute
 void ltr_plan_fields_empty(const ltr_genotype_batch* gb, ltr_genotype_result* res);

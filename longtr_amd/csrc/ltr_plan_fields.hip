@@ -102,8 +102,9 @@ __device__ __forceinline__ double block_max(double v, double* s_red, int tid) {
 //  2. thread 0: best_gts, the haplotype and genotype posteriors of the best pair (:147-150, :174-198).
 //  3. thread per genotype: GL (:204-241), PHASEDGL; then the maximum and the runner-up (exact in any order), calc_gl_diff, calc_PLs.
 //  4. thread per read of the sample: the strand haplotype (:965-967) and its allele (:1038-1040); read counts (:1006-1012).
-template <int NT>
-__global__ __launch_bounds__(NT) void ltr_genotype_fields_kernel(const FieldArgs A, int unit0, double log_thresh) {
+// DIRECT: the row rule of the LL source (LlSource): false = a read's row is its pool's, true = its own (A.pool_index null).
+template <int NT, bool DIRECT>
+__device__ __forceinline__ void fields_unit(const FieldArgs& A, int unit0, double log_thresh) {
   extern __shared__ double s_cells[];
   __shared__ double s_red[NT];
   __shared__ int s_cnt[4];
@@ -194,7 +195,7 @@ __global__ __launch_bounds__(NT) void ltr_genotype_fields_kernel(const FieldArgs
     const double p1 = A.lp1[r], p2 = A.lp2[r];
     int strand = 0;
     if (!L.haploid && ha != hb) {
-      const double* row = A.ll + L.ll_off + (int64_t)A.pool_index[r] * L.H;
+      const double* row = A.ll + L.ll_off + (DIRECT ? (int64_t)(r - L.r0) : (int64_t)A.pool_index[r]) * L.H;
       strand = (p1 + ltr_clamped_ll(row, cmap, ha) > p2 + ltr_clamped_ll(row, cmap, hb)) ? 0 : 1;      // :965-967
     }
     A.read_allele[r] = strand == 0 ? ga : gb;
@@ -207,18 +208,27 @@ __global__ __launch_bounds__(NT) void ltr_genotype_fields_kernel(const FieldArgs
   __syncthreads();
   if (tid < 4) A.counts[(int64_t)tid * A.nu + u.out] = s_cnt[tid];
 }
+template <int NT>
+__global__ __launch_bounds__(NT) void ltr_genotype_fields_kernel(const FieldArgs A, int unit0, double log_thresh) {
+  fields_unit<NT, false>(A, unit0, log_thresh);
+}
+// ... on per-read matrices (ltr_ll_genotype)
+template <int NT>
+__global__ __launch_bounds__(NT) void ltr_ll_fields_kernel(const FieldArgs A, int unit0, double log_thresh) {
+  fields_unit<NT, true>(A, unit0, log_thresh);
+}
 
 // units [0, n_small) in workgroups of 64 threads, [n_small, n_small + n_large) of 256; cell_cap_*: doubles of LDS for the V x V table
-void launch_fields(hipStream_t st, const FieldArgs& a, size_t n_small, int cell_cap_small, size_t n_large, int cell_cap_large) {
+void launch_fields(hipStream_t st, const FieldArgs& a, bool direct, size_t n_small, int cell_cap_small, size_t n_large, int cell_cap_large) {
   const double log_thresh = std::log(0.001);                     // LOG_THRESH, mathops.h:36
   if (n_small)
-    hipLaunchKernelGGL(ltr_genotype_fields_kernel<64>, dim3((unsigned)n_small), dim3(64), (size_t)cell_cap_small * sizeof(double), st, a, 0, log_thresh);
+    hipLaunchKernelGGL(direct ? ltr_ll_fields_kernel<64> : ltr_genotype_fields_kernel<64>, dim3((unsigned)n_small), dim3(64), (size_t)cell_cap_small * sizeof(double), st, a, 0, log_thresh);
   if (n_large)
-    hipLaunchKernelGGL(ltr_genotype_fields_kernel<256>, dim3((unsigned)n_large), dim3(256), (size_t)cell_cap_large * sizeof(double), st, a, (int)n_small, log_thresh);
+    hipLaunchKernelGGL(direct ? ltr_ll_fields_kernel<256> : ltr_genotype_fields_kernel<256>, dim3((unsigned)n_large), dim3(256), (size_t)cell_cap_large * sizeof(double), st, a, (int)n_small, log_thresh);
 }
 
 // sizes and offsets of every locus (res->f_V, f_gl_off, f_pgl_off, f_read_off; floci when the kernel will run); the table entries needed
-int64_t layout_loci(const ltr_plan* plan, const ltr_genotype_batch* gb, ltr_genotype_result* res, FieldLocus* floci) {
+int64_t layout_loci(const LlSource* src, const ltr_genotype_batch* gb, ltr_genotype_result* res, FieldLocus* floci) {
   const ltr_posterior_batch* pb = gb->pb;
   const int64_t nl = res->n_loci;
   res->f_gl_off.assign((size_t)nl + 1, 0); res->f_pgl_off.assign((size_t)nl + 1, 0);
@@ -231,7 +241,7 @@ int64_t layout_loci(const ltr_plan* plan, const ltr_genotype_batch* gb, ltr_geno
     res->f_V[(size_t)l] = V;
     if (!floci) continue;
     FieldLocus& F = floci[(size_t)l];
-    F.ll_off = plan->locus_ll_off[(size_t)l]; F.map_off = p ? mo : -1; F.tab_off = tab;
+    F.ll_off = src->locus_off[l]; F.map_off = p ? mo : -1; F.tab_off = tab;
     F.gl_off = res->f_gl_off[(size_t)l]; F.pgl_off = res->f_pgl_off[(size_t)l];
     F.r0 = (int32_t)pb->locus_read_off[l]; F.r1 = (int32_t)pb->locus_read_off[l + 1]; F.H = H; F.Hn = Hn; F.V = V; F.haploid = pb->haploid ? 1 : 0;
     F.n_gl = pb->haploid ? V : V * (V + 1) / 2; F.n_pgl = pb->haploid ? V : V * V;
@@ -306,16 +316,15 @@ void ltr_plan_fields_empty(const ltr_genotype_batch* gb, ltr_genotype_result* re
   res->f_i32.reset(new int32_t[std::max<size_t>((size_t)gb->pb->n_reads, 1)]()); res->f_f64.reset(new double[1]());
 }
 
-int ltr_plan_fields_stage(ltr_plan* plan, const ltr_genotype_batch* gb, const ltr_fields_request* fr, ltr_genotype_result* res,
+int ltr_plan_fields_stage(ltr_ctx* ctx, const LlSource& src, const ltr_genotype_batch* gb, const ltr_fields_request* fr, ltr_genotype_result* res,
                           const DevReads& rd, const int32_t* d_map, const DevPass pass[2], DevLease& lease) {
-  ltr_ctx* ctx = plan->ctx;
   hipStream_t st = lease.st;
   const int64_t nl = res->n_loci;
   const size_t nu = (size_t)res->unit_off[(size_t)nl], nr = (size_t)gb->pb->n_reads;
   FieldLocus* floci = lease.host<FieldLocus>((size_t)nl);
-  const size_t ntab = (size_t)layout_loci(plan, gb, res, floci);
+  const size_t ntab = (size_t)layout_loci(&src, gb, res, floci);
   int32_t* ftab = lease.host<int32_t>(ntab);
-  if (!fill_tables(gb, res, floci, ftab)) { ltr::set_error(ctx, "ltr_plan_genotype_fields: malformed haplotype blocks"); return LTR_ERR_INVALID; }
+  if (!fill_tables(gb, res, floci, ftab)) { ltr::set_error(ctx, std::string(src.direct ? "ltr_ll_genotype" : "ltr_plan_genotype_fields") + ": malformed haplotype blocks"); return LTR_ERR_INVALID; }
   FieldUnit* funits = lease.host<FieldUnit>(nu);
   const UnitLayout ul = layout_field_units(res, floci, funits);
   const int64_t ngl = res->f_gl_off[(size_t)nl], npgl = res->f_pgl_off[(size_t)nl];
@@ -347,11 +356,11 @@ int ltr_plan_fields_stage(ltr_plan* plan, const ltr_genotype_batch* gb, const lt
   if (nr) DEV_TRY(ctx, hipMemsetAsync(d_fi32 + 6 * nu, 0xff, nr * 4, st));   // (a read whose label no unit claims cannot exist: the labels were checked; -1 would be refused by the formatter)
   FieldArgs a;
   a.units = d_funits; a.loci = d_floci; a.tab = d_ftab;
-  a.ll = plan->last_out; a.pool_index = rd.pool_index; a.lp1 = rd.lp1; a.lp2 = rd.lp2; a.label = rd.label; a.map = d_map;
+  a.ll = src.base; a.pool_index = rd.pool_index; a.lp1 = rd.lp1; a.lp2 = rd.lp2; a.label = rd.label; a.map = d_map;
   for (int k = 0; k < 2; ++k) { a.post[k] = pass[k].post; a.stl[k] = pass[k].stl; a.gts[k] = pass[k].gts; }
   a.best_gts = d_fi32; a.counts = d_fi32 + 2 * nu; a.scalars = d_ff64; a.nu = (int64_t)nu;
   a.gls = d_fgls; a.pls = d_fpls; a.pgls = d_fpgls; a.cells = d_fcells; a.read_allele = d_fi32 + 6 * nu;
-  launch_fields(st, a, ul.n_small, ul.cap_small, nu - ul.n_small, ul.cap_large);
+  launch_fields(st, a, src.direct, ul.n_small, ul.cap_small, nu - ul.n_small, ul.cap_large);
   DEV_TRY(ctx, hipGetLastError());
   DEV_TRY(ctx, hipMemcpyAsync(res->f_i32.get(), d_fi32, ni32 * 4, hipMemcpyDeviceToHost, st));
   DEV_TRY(ctx, hipMemcpyAsync(res->f_f64.get(), d_ff64, 5 * nu * 8, hipMemcpyDeviceToHost, st));

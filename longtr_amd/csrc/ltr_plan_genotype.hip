@@ -36,7 +36,8 @@ struct GtUnit {
 // mathops.cpp:47-53) and scanned for the first maximum of the NORMALISED values (:85-100); a larger one is accumulated in the
 // posterior buffer and finished by ltr_genotype_finish_kernel.  A row that does not fit a tile (H' > tile_doubles) is not
 // staged: its diplotype threads take the exponentials themselves.
-template <int NT>
+// DIRECT: the row rule of the LL source (LlSource): false = a read's row is its pool's (pool_index), true = its own (r - r0; pool_index null).
+template <int NT, bool DIRECT>
 __global__ __launch_bounds__(NT) void ltr_genotype_kernel(const GtUnit* __restrict__ units, const double* __restrict__ ll,
                                                           const int32_t* __restrict__ pool_index, const double* __restrict__ lp1,
                                                           const double* __restrict__ lp2, const int32_t* __restrict__ label,
@@ -68,7 +69,7 @@ __global__ __launch_bounds__(NT) void ltr_genotype_kernel(const GtUnit* __restri
         const bool mine = label[r] == u.sample;
         if (a == 0) sMine[j] = mine;
         if (!mine) continue;
-        const double v = ltr_clamped_ll(llb + (int64_t)pool_index[r] * u.H, cmap, a);   // the read's pool row (seq_stutter_genotyper.cpp:531-537)
+        const double v = ltr_clamped_ll(llb + (DIRECT ? (int64_t)(r - u.r0) : (int64_t)pool_index[r]) * u.H, cmap, a);   // the read's pool row (seq_stutter_genotyper.cpp:531-537), or its own
         sE1[k] = exp(v + lp1[r] + LOG_ONE_HALF);
         sE2[k] = exp(v + lp2[r] + LOG_ONE_HALF);
       }
@@ -86,7 +87,7 @@ __global__ __launch_bounds__(NT) void ltr_genotype_kernel(const GtUnit* __restri
       double acc = accp[idx];
       for (int r = u.r0; r < u.r1; ++r) {
         if (label[r] != u.sample) continue;
-        const double* row = llb + (int64_t)pool_index[r] * u.H;
+        const double* row = llb + (DIRECT ? (int64_t)(r - u.r0) : (int64_t)pool_index[r]) * u.H;
         acc += log(exp(ltr_clamped_ll(row, cmap, a1) + lp1[r] + LOG_ONE_HALF) + exp(ltr_clamped_ll(row, cmap, a2) + lp2[r] + LOG_ONE_HALF));
       }
       accp[idx] = acc;
@@ -141,6 +142,7 @@ struct GtLocus {
   int64_t ll_off, out_off, map_off;
   int32_t r0, r1, H, Hn;
 };
+template <bool DIRECT>
 __global__ void ltr_genotype_gather_kernel(const GtLocus* __restrict__ loci, const double* __restrict__ ll,
                                            const int32_t* __restrict__ pool_index, const int32_t* __restrict__ map,
                                            double* __restrict__ out) {
@@ -150,7 +152,7 @@ __global__ void ltr_genotype_gather_kernel(const GtLocus* __restrict__ loci, con
   for (int64_t k = threadIdx.x; k < n; k += blockDim.x) {
     const int64_t j = k / L.Hn;
     const int a = (int)(k - j * L.Hn);
-    out[L.out_off + k] = ltr_clamped_ll(ll + L.ll_off + (int64_t)pool_index[L.r0 + j] * L.H, cmap, a);
+    out[L.out_off + k] = ltr_clamped_ll(ll + L.ll_off + (DIRECT ? j : (int64_t)pool_index[L.r0 + j]) * L.H, cmap, a);
   }
 }
 
@@ -192,14 +194,16 @@ PassShape shape_of(const GtUnit* units, size_t n_units) {
 
 // The launches of a pass: one per shape with units (d_lists: the unit lists of shape 0 then shape 1, or null when there is one
 // shape), then the finish kernel over the units whose block did not fit LDS (d_unfused: shape 0's then shape 1's).
-void launch_pass(const PassShape& ps, hipStream_t st, const GtUnit* d_units, const double* d_ll, const DevReads& rd, const int32_t* d_map,
+void launch_pass(const PassShape& ps, hipStream_t st, const GtUnit* d_units, const LlSource& src, const DevReads& rd, const int32_t* d_map,
                  const int32_t* d_lists, const int32_t* d_unfused, const DevPass& out) {
   for (int g = 0; g < 2; ++g) {
     const LaunchShape& sh = ps.sh[g];
     if (sh.n == 0) continue;
     const int32_t* list = d_lists ? d_lists + (g == 0 ? 0 : ps.sh[0].n) : nullptr;
     // (sh.nt is the kernel's NT: shape_of sets 64 for shape 0, 256 for shape 1)
-    hipLaunchKernelGGL(g == 0 ? ltr_genotype_kernel<64> : ltr_genotype_kernel<256>, dim3((unsigned)sh.n), dim3(sh.nt), sh.lds, st, d_units, d_ll, rd.pool_index,
+    const auto kernel = src.direct ? (g == 0 ? ltr_genotype_kernel<64, true> : ltr_genotype_kernel<256, true>)
+                                   : (g == 0 ? ltr_genotype_kernel<64, false> : ltr_genotype_kernel<256, false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)sh.n), dim3(sh.nt), sh.lds, st, d_units, src.base, rd.pool_index,
                        rd.lp1, rd.lp2, rd.label, d_map, list, sh.tile, sh.post_cap, out.post, out.stl, out.gts);
   }
   const size_t nf = ps.sh[0].unfused.size() + ps.sh[1].unfused.size();
@@ -223,12 +227,24 @@ int upload_lists(ltr_ctx* ctx, DevLease& lease, const PassShape& ps, const int32
   return LTR_OK;
 }
 
-// One call of ltr_plan_genotype / ltr_plan_genotype_fields.  The ORDER of the members carries the invariant of DevLease: the host
-// memory that queued copies read or write (the result's arrays, the second pass's units and column maps) comes first and the
-// lease last, so on every way out -- return, error return, exception -- the lease drains the stream and gives the blocks back
-// before any of that memory is freed.  (The first pass's units live in the context; all other staging comes from lease.host().)
+// the two pinned staging blocks of ltr_ll_genotype's upload, from the context's cache and back to it
+struct PinnedPair {
+  ltr_ctx* ctx; double* p[2] = {nullptr, nullptr};
+  explicit PinnedPair(ltr_ctx* c) : ctx(c) {}
+  PinnedPair(const PinnedPair&) = delete;
+  ~PinnedPair() { ctx_give_pinned(ctx, p[0]); ctx_give_pinned(ctx, p[1]); }
+};
+
+// One call of ltr_plan_genotype / ltr_plan_genotype_fields / ltr_ll_genotype.  The ORDER of the members carries the invariant of
+// DevLease: the host memory that queued copies read or write (the result's arrays, the second pass's units and column maps, the
+// staging blocks of the LL upload) comes first and the lease last, so on every way out -- return, error return, exception -- the
+// lease drains the stream and gives the blocks back before any of that memory is freed or handed to another call.  (The first
+// pass's units live in the context; all other staging comes from lease.host().)
 struct GtCall {
-  ltr_plan* plan; ltr_ctx* ctx; const ltr_genotype_batch* gb; const ltr_posterior_batch* pb; const ltr_fields_request* fr;
+  ltr_ctx* ctx; const ltr_genotype_batch* gb; const ltr_posterior_batch* pb; const ltr_fields_request* fr;
+  LlSource src;                                     // where the scores lie and how a read finds its row: the plan's buffer, or the block upload_ll fills
+  std::vector<int64_t> ll_off;                      // ... the locus offsets of that block (src.locus_off)
+  PinnedPair stage;                                 // ... its staging
   std::unique_ptr<ltr_genotype_result> res;
   GtUnit* units = nullptr; size_t nu = 0;           // the first pass's units (ctx->gt_units)
   std::vector<uint8_t> aligned;                     // per unit: one of the sample's reads was aligned (:262-266)
@@ -236,32 +252,33 @@ struct GtCall {
   double* stl2 = nullptr; int32_t* gts2 = nullptr;  // ... its totals and best pairs (lease.host)
   DevReads rd; int32_t* d_map = nullptr; DevPass pass[2];
   DevLease lease;
-  GtCall(ltr_plan* p, const ltr_genotype_batch* g, const ltr_fields_request* f)
-      : plan(p), ctx(p->ctx), gb(g), pb(g->pb), fr(f), res(new ltr_genotype_result()), lease(p->ctx, p->last_stream) {}
+  GtCall(ltr_ctx* x, hipStream_t st, const LlSource& s, const ltr_genotype_batch* g, const ltr_fields_request* f)
+      : ctx(x), gb(g), pb(g->pb), fr(f), src(s), stage(x), res(new ltr_genotype_result()), lease(x, st) {}
 };
 
 // ---- host, all loci at once: the result laid out, labels checked, every sample's reads listed in read order, aligned_read (:262-266) ----
 int layout_units(GtCall& c) {
-  ltr_ctx* ctx = c.ctx; ltr_plan* plan = c.plan; ltr_genotype_result* res = c.res.get();
+  ltr_ctx* ctx = c.ctx; const LlSource& src = c.src; ltr_genotype_result* res = c.res.get();
   const ltr_genotype_batch* gb = c.gb; const ltr_posterior_batch* pb = c.pb; const ltr_fields_request* fr = c.fr;
   const int64_t nl = pb->n_loci;
   const bool need_haps = gb->prune || fr;
+  const std::string who(src.who);
   res->n_loci = nl;
   res->S.assign(pb->n_samples, pb->n_samples + nl);
-  res->H.assign(plan->locus_H.begin(), plan->locus_H.end());
+  res->H.assign(src.H, src.H + nl);
   if (gb->haps) res->haps.assign(gb->haps, gb->haps + nl); else res->haps.assign((size_t)nl, nullptr);
   res->unit_off.assign((size_t)nl + 1, 0); res->post1_off.assign((size_t)nl + 1, 0);
   res->pruned.resize((size_t)nl); res->n_blocks.assign((size_t)nl, 0);
-  std::vector<int64_t> pool_base((size_t)nl + 1, 0);          // first pool (= read of the plan) of every locus
+  std::vector<int64_t> pool_base(src.direct ? 0 : (size_t)nl + 1, 0);   // first pool (= read of the plan) of every locus
   int32_t max_H = 1;
   for (int64_t l = 0; l < nl; ++l) {
     const int64_t r0 = pb->locus_read_off[l], r1 = pb->locus_read_off[l + 1];
-    const int32_t S = pb->n_samples[l], H = plan->locus_H[(size_t)l];
+    const int32_t S = pb->n_samples[l], H = src.H[l];
     if (r0 < 0 || r1 < r0 || r1 > pb->n_reads || S < 0 || r1 > 0x7fffffff) { ltr::set_error(ctx, "bad posterior batch offsets"); return LTR_ERR_INVALID; }
-    if (H <= 0) { ltr::set_error(ctx, "ltr_plan_genotype: a locus without haplotypes"); return LTR_ERR_INVALID; }
+    if (H <= 0) { ltr::set_error(ctx, who + ": a locus without haplotypes"); return LTR_ERR_INVALID; }
     res->unit_off[(size_t)l + 1] = res->unit_off[(size_t)l] + S;
     res->post1_off[(size_t)l + 1] = res->post1_off[(size_t)l] + (int64_t)S * H * H;
-    pool_base[(size_t)l + 1] = pool_base[(size_t)l] + plan->locus_P[(size_t)l];
+    if (!src.direct) pool_base[(size_t)l + 1] = pool_base[(size_t)l] + src.P[l];
     max_H = std::max(max_H, H);
   }
   const size_t nu = c.nu = (size_t)res->unit_off[(size_t)nl];
@@ -277,7 +294,7 @@ int layout_units(GtCall& c) {
   if (fr) { res->has_fields = true; res->ctx = ctx; res->haploid = pb->haploid ? 1 : 0; res->f_block.assign((size_t)nl, 0); res->f_V.assign((size_t)nl, 0); }
   ltr::parallel_for(nl, 64, [&](int64_t l) {
     const int64_t r0 = pb->locus_read_off[l], r1 = pb->locus_read_off[l + 1], u0 = res->unit_off[(size_t)l];
-    const int32_t S = pb->n_samples[l], H = plan->locus_H[(size_t)l], P = plan->locus_P[(size_t)l];
+    const int32_t S = pb->n_samples[l], H = src.H[l];
     if (need_haps) {     // (prune == 0 never reads the block lists: 100 000 of them scattered over the caller's heap cost 2 ms of cache misses)
       if (!gb->haps[l] || ltr_haplotype_num_combs(gb->haps[l]) != H) { bad_haps.store(l); return; }
       res->n_blocks[(size_t)l] = gb->haps[l]->n_blocks;
@@ -289,14 +306,24 @@ int layout_units(GtCall& c) {
       if (b < 0 || b >= hb->n_blocks) { bad_block.store(l); return; }
       res->f_block[(size_t)l] = b;
     }
-    for (int64_t r = r0; r < r1; ++r) {
-      const int32_t q = pb->pool_index[r], s = pb->sample_label[r];
-      if (q < 0 || q >= P || s < 0 || s >= S) { bad.store(1); return; }
-      if (plan->seed[(size_t)(pool_base[(size_t)l] + q)] >= 0) c.aligned[(size_t)(u0 + s)] = 1;     // seed_positions_[read] >= 0, :265
+    if (src.direct) {                                          // a row and a seed per read (null: every read aligned)
+      const int32_t* seed = src.read_seed ? src.read_seed[l] : nullptr;
+      for (int64_t r = r0; r < r1; ++r) {
+        const int32_t s = pb->sample_label[r];
+        if (s < 0 || s >= S) { bad.store(1); return; }
+        if (!seed || seed[r - r0] >= 0) c.aligned[(size_t)(u0 + s)] = 1;
+      }
+    } else {
+      const int32_t P = src.P[l];
+      for (int64_t r = r0; r < r1; ++r) {
+        const int32_t q = pb->pool_index[r], s = pb->sample_label[r];
+        if (q < 0 || q >= P || s < 0 || s >= S) { bad.store(1); return; }
+        if (src.pool_seed[pool_base[(size_t)l] + q] >= 0) c.aligned[(size_t)(u0 + s)] = 1;     // seed_positions_[read] >= 0, :265
+      }
     }
     for (int32_t s = 0; s < S; ++s) {
       GtUnit& u = units[(size_t)(u0 + s)];
-      u.ll_off = plan->locus_ll_off[(size_t)l]; u.post_off = res->post1_off[(size_t)l] + (int64_t)s * H * H; u.map_off = -1;
+      u.ll_off = src.locus_off[l]; u.post_off = res->post1_off[(size_t)l] + (int64_t)s * H * H; u.map_off = -1;
       u.r0 = (int32_t)r0; u.r1 = (int32_t)r1;
       u.H = H; u.Hn = H; u.out = (int32_t)(u0 + s); u.sample = s;
       ltr_log_priors(H, pb->haploid, &u.homoz, &u.hetz);
@@ -304,14 +331,14 @@ int layout_units(GtCall& c) {
   });
   if (bad_haps.load() >= 0) {
     const int64_t l = bad_haps.load();
-    ltr::set_error(ctx, "haplotype blocks of locus " + std::to_string(l) + " do not enumerate the plan's " + std::to_string(plan->locus_H[(size_t)l]) + " haplotypes");
+    ltr::set_error(ctx, "haplotype blocks of locus " + std::to_string(l) + " do not enumerate the " + (src.direct ? "batch's " : "plan's ") + std::to_string(src.H[l]) + " haplotypes");
     return LTR_ERR_INVALID;
   }
   if (bad_block.load() >= 0) {
-    ltr::set_error(ctx, "ltr_plan_genotype_fields: locus " + std::to_string(bad_block.load()) + (fr->block ? ": block out of range" : ": no repeat block"));
+    ltr::set_error(ctx, (src.direct ? who : who + "_fields") + ": locus " + std::to_string(bad_block.load()) + (fr->block ? ": block out of range" : ": no repeat block"));
     return LTR_ERR_INVALID;
   }
-  if (bad.load()) { ltr::set_error(ctx, "pool index / sample label out of range"); return LTR_ERR_INVALID; }
+  if (bad.load()) { ltr::set_error(ctx, src.direct ? "sample label out of range" : "pool index / sample label out of range"); return LTR_ERR_INVALID; }
   return LTR_OK;
 }
 
@@ -330,7 +357,7 @@ int run_pass(GtCall& c, DevPass* dp, const GtUnit* units, size_t nu, int64_t npo
   DEV_TRY(ctx, c.lease.alloc(&dp->gts, nu * 8));
   DEV_TRY(ctx, hipMemcpyAsync(d_units, units, nu * sizeof(GtUnit), hipMemcpyHostToDevice, st));
   if (int rc = upload_lists(ctx, c.lease, ps, &d_lists, &d_unf)) return rc;
-  launch_pass(ps, st, d_units, c.plan->last_out, c.rd, d_map, d_lists, d_unf, *dp);
+  launch_pass(ps, st, d_units, c.src, c.rd, d_map, d_lists, d_unf, *dp);
   DEV_TRY(ctx, hipGetLastError());
   DEV_TRY(ctx, hipMemcpyAsync(gts, dp->gts, nu * 8, hipMemcpyDeviceToHost, st));
   DEV_TRY(ctx, hipMemcpyAsync(stl, dp->stl, nu * 8, hipMemcpyDeviceToHost, st));
@@ -384,7 +411,7 @@ int prune_uncalled(GtCall& c) {
   std::atomic<int> perr(0);
   ltr::parallel_for(nl, 64, [&](int64_t l) { if (const int e = prune_locus(c, l, &res->pruned[(size_t)l])) perr.store(e); }, 16);
   if (perr.load()) {
-    ltr::set_error(c.ctx, perr.load() == 2 ? "ltr_plan_genotype: a sample without an optimal haplotype pair (NaN scores?)" : "ltr_plan_genotype: malformed haplotype blocks");
+    ltr::set_error(c.ctx, std::string(c.src.who) + (perr.load() == 2 ? ": a sample without an optimal haplotype pair (NaN scores?)" : ": malformed haplotype blocks"));
     return LTR_ERR_INVALID;
   }
   for (int64_t l = 0; l < nl; ++l) {
@@ -418,7 +445,7 @@ int gather_read_ll(GtCall& c) {
   for (int64_t l = 0; l < nl; ++l) {
     const LtrPruned* p = res->pruned[(size_t)l].get();
     GtLocus& g = gl[(size_t)l];
-    g.ll_off = c.plan->locus_ll_off[(size_t)l]; g.out_off = res->read_ll_off[(size_t)l]; g.map_off = p ? mo : -1;
+    g.ll_off = c.src.locus_off[l]; g.out_off = res->read_ll_off[(size_t)l]; g.map_off = p ? mo : -1;
     g.r0 = (int32_t)pb->locus_read_off[l]; g.r1 = (int32_t)pb->locus_read_off[l + 1]; g.H = res->H[(size_t)l]; g.Hn = p ? p->Hn : g.H;
     if (p) mo += p->Hn;
     res->read_ll_off[(size_t)l + 1] = g.out_off + (int64_t)(g.r1 - g.r0) * g.Hn;
@@ -429,7 +456,8 @@ int gather_read_ll(GtCall& c) {
   DEV_TRY(ctx, c.lease.alloc(&d_loci, (size_t)nl * sizeof(GtLocus)));
   DEV_TRY(ctx, c.lease.alloc(&d_rll, (size_t)std::max<int64_t>(nrll, 1) * 8));
   DEV_TRY(ctx, hipMemcpyAsync(d_loci, gl, (size_t)nl * sizeof(GtLocus), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(ltr_genotype_gather_kernel, dim3((unsigned)nl), dim3(64), 0, st, d_loci, c.plan->last_out, c.rd.pool_index, c.d_map, d_rll);
+  hipLaunchKernelGGL(c.src.direct ? ltr_genotype_gather_kernel<true> : ltr_genotype_gather_kernel<false>, dim3((unsigned)nl), dim3(64), 0, st, d_loci,
+                     c.src.base, c.rd.pool_index, c.d_map, d_rll);
   DEV_TRY(ctx, hipGetLastError());
   if (nrll) DEV_TRY(ctx, hipMemcpyAsync(res->read_ll.get(), d_rll, (size_t)nrll * 8, hipMemcpyDeviceToHost, st));
   return LTR_OK;
@@ -449,29 +477,65 @@ void merge_second_pass(GtCall& c) {
   }
 }
 
-}  // namespace
-
-// ltr_plan_genotype (fr == null) and ltr_plan_genotype_fields: the same stages; with fr the fields stage runs on the passes'
-// buffers before they go back to the pool, and the posterior blocks are fetched only when fr asks for them.
-static int plan_genotype(ltr_plan* plan, const ltr_genotype_batch* gb, const ltr_fields_request* fr, ltr_genotype_result** out) {
-  if (out) *out = nullptr;
-  if (!plan || !gb || !gb->pb || !out) return LTR_ERR_INVALID;
-  ltr_ctx* ctx = plan->ctx;
-  if (!ctx) return LTR_ERR_INVALID;                          // the context was destroyed before this plan
-  const ltr_posterior_batch* pb = gb->pb;
-  if (!plan->executed) { ltr::set_error(ctx, "ltr_plan_genotype: execute the plan first"); return LTR_ERR_INVALID; }
-  const int64_t nl = pb->n_loci;
-  if (nl != (int64_t)plan->locus_P.size()) { ltr::set_error(ctx, "genotype batch and plan disagree on the number of loci"); return LTR_ERR_INVALID; }
-  if (!gb->haps && nl > 0 && (gb->prune || fr)) { ltr::set_error(ctx, "ltr_plan_genotype: no haplotype blocks"); return LTR_ERR_INVALID; }
-  if (nl > 0 && (!pb->locus_read_off || !pb->n_samples || (pb->n_reads > 0 && (!pb->pool_index || !pb->log_p1 || !pb->log_p2 || !pb->sample_label)))) {
-    ltr::set_error(ctx, "ltr_plan_genotype: incomplete posterior batch"); return LTR_ERR_INVALID;
+// ---- ltr_ll_genotype: the caller's per-read matrices, one block on the device for the whole call (both passes, the gather and the
+// fields stage read it).  The matrices are scattered pageable arrays: the worker pool copies the loci of a chunk into one of two
+// pinned staging blocks while the copy of the chunk before is still on its way (an event per block says when it may be filled
+// again).  Chunks: as many loci as fit kLlChunkBytes, at least one (debug knob ll_chunk_loci: that many loci).
+constexpr size_t kLlChunkBytes = (size_t)8 << 20;
+int upload_ll(GtCall& c, const ltr_ll_batch* lb) {
+  ltr_ctx* ctx = c.ctx;
+  hipStream_t st = c.lease.st;
+  const int64_t nl = c.pb->n_loci, total = c.ll_off[(size_t)nl], knob = ctx->dbg.ll_chunk_loci;
+  double* d_ll = nullptr;
+  DEV_TRY(ctx, c.lease.alloc(&d_ll, (size_t)std::max<int64_t>(total, 1) * 8));
+  c.src.base = d_ll;
+  if (total == 0) return LTR_OK;
+  std::vector<int64_t> cut(1, 0);                               // chunk k: loci [cut[k], cut[k + 1])
+  int64_t largest = 0;
+  for (int64_t l0 = 0; l0 < nl;) {
+    int64_t l1 = l0 + 1;
+    if (knob > 0) l1 = std::min(nl, l0 + knob);
+    else while (l1 < nl && (size_t)(c.ll_off[(size_t)l1 + 1] - c.ll_off[(size_t)l0]) * 8 <= kLlChunkBytes) ++l1;
+    largest = std::max(largest, c.ll_off[(size_t)l1] - c.ll_off[(size_t)l0]);
+    cut.push_back(l1);
+    l0 = l1;
   }
+  const size_t nchunks = cut.size() - 1;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  for (int b = 0; b < (nchunks > 1 ? 2 : 1); ++b) {
+    size_t cap = 0; double* dev = nullptr;
+    c.stage.p[b] = ctx_take_pinned(ctx, (size_t)std::max<int64_t>(largest, 1) * 8, &cap, &dev);
+    if (!c.stage.p[b]) { ltr::set_error(ctx, "ltr_ll_genotype: out of pinned host memory"); return LTR_ERR_NOMEM; }
+    DEV_TRY(ctx, c.lease.event(&ev[b], false));
+  }
+  LTR_DBG("ll_genotype: upload of %lld bytes in %zu chunks begins", (long long)total * 8, nchunks);
+  for (size_t k = 0; k < nchunks; ++k) {
+    const int b = (int)(k & 1);
+    const int64_t l0 = cut[k], l1 = cut[k + 1], base = c.ll_off[(size_t)l0], n = c.ll_off[(size_t)l1] - base;
+    if (n == 0) continue;
+    if (k >= 2) DEV_TRY(ctx, hipEventSynchronize(ev[b]));       // the copy of chunk k - 2 has left this block
+    double* stage = c.stage.p[b];
+    ltr::parallel_for(l1 - l0, 16, [&](int64_t i) {
+      const int64_t l = l0 + i, len = c.ll_off[(size_t)l + 1] - c.ll_off[(size_t)l];
+      if (len) std::memcpy(stage + (c.ll_off[(size_t)l] - base), lb->log_aln_probs[l], (size_t)len * 8);
+    }, 16);
+    DEV_TRY(ctx, hipMemcpyAsync(d_ll + base, stage, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    DEV_TRY(ctx, hipEventRecord(ev[b], st));
+  }
+  if (ltr::g_trace.load(std::memory_order_relaxed)) {           // (the phase's own time: the trace waits for it, a plain call does not)
+    DEV_TRY(ctx, hipStreamSynchronize(st));
+    LTR_DBG("ll_genotype: upload of %lld bytes done", (long long)total * 8);
+  }
+  return LTR_OK;
+}
+
+// The stages of one call.  lb: the per-read matrices of ltr_ll_genotype, uploaded once every check has passed (null: c.src is a plan's buffer).
+// With fr the fields stage runs on the passes' buffers before they go back to the pool, and the posterior blocks are fetched
+// only when fr asks for them.
+int genotype_stages(GtCall& c, const ltr_ll_batch* lb, ltr_genotype_result** out) {
+  ltr_ctx* ctx = c.ctx; const ltr_genotype_batch* gb = c.gb; const ltr_posterior_batch* pb = c.pb; const ltr_fields_request* fr = c.fr;
+  const int64_t nl = pb->n_loci;
   const bool fetch_post = !fr || fr->want_posteriors;
-  ltr::TimedCall timed(ctx, ltr::kTimerPosterior);             // total_posterior_time_, genotyper.cpp:46,:80-81
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  LTR_GUARD_BEGIN
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  GtCall c(plan, gb, fr);
   ltr_genotype_result* res = c.res.get();
   if (int rc = layout_units(c)) return rc;
   if (c.nu == 0) {                                             // (no sample anywhere: nothing to compute; read_ll stays NULL)
@@ -479,7 +543,8 @@ static int plan_genotype(ltr_plan* plan, const ltr_genotype_batch* gb, const ltr
     *out = c.res.release(); return LTR_OK;
   }
   LTR_DBG("genotype: %zu units laid out", c.nu);
-  if (int rc = upload_reads(ctx, c.lease, pb, &c.rd)) return rc;
+  if (lb) if (int rc = upload_ll(c, lb)) return rc;
+  if (int rc = upload_reads(ctx, c.lease, pb, &c.rd, !c.src.direct)) return rc;
   // first pass: calc_log_sample_posteriors + get_optimal_haplotypes, :635
   const int64_t npost1 = res->post1_off[(size_t)nl];
   if (fetch_post) res->post1.reset(new double[(size_t)std::max<int64_t>(npost1, 1)]);
@@ -500,12 +565,39 @@ static int plan_genotype(ltr_plan* plan, const ltr_genotype_batch* gb, const ltr
   }
   if (gb->want_read_ll) if (int rc = gather_read_ll(c)) return rc;
   // the VCF fields of every locus (ltr_plan_fields.hip), on the final posterior blocks where they lie
-  if (fr) if (int rc = ltr_plan_fields_stage(plan, gb, fr, res, c.rd, c.d_map, c.pass, c.lease)) return rc;
+  if (fr) if (int rc = ltr_plan_fields_stage(ctx, c.src, gb, fr, res, c.rd, c.d_map, c.pass, c.lease)) return rc;
   DEV_TRY(ctx, c.lease.drain());
   LTR_DBG("genotype: second pass and gather done");
   merge_second_pass(c);
   *out = c.res.release();
   return LTR_OK;
+}
+
+}  // namespace
+
+// ltr_plan_genotype (fr == null) and ltr_plan_genotype_fields: the stages on the LL buffer of the plan's last execute
+static int plan_genotype(ltr_plan* plan, const ltr_genotype_batch* gb, const ltr_fields_request* fr, ltr_genotype_result** out) {
+  if (out) *out = nullptr;
+  if (!plan || !gb || !gb->pb || !out) return LTR_ERR_INVALID;
+  ltr_ctx* ctx = plan->ctx;
+  if (!ctx) return LTR_ERR_INVALID;                          // the context was destroyed before this plan
+  const ltr_posterior_batch* pb = gb->pb;
+  if (!plan->executed) { ltr::set_error(ctx, "ltr_plan_genotype: execute the plan first"); return LTR_ERR_INVALID; }
+  const int64_t nl = pb->n_loci;
+  if (nl != (int64_t)plan->locus_P.size()) { ltr::set_error(ctx, "genotype batch and plan disagree on the number of loci"); return LTR_ERR_INVALID; }
+  if (!gb->haps && nl > 0 && (gb->prune || fr)) { ltr::set_error(ctx, "ltr_plan_genotype: no haplotype blocks"); return LTR_ERR_INVALID; }
+  if (nl > 0 && (!pb->locus_read_off || !pb->n_samples || (pb->n_reads > 0 && (!pb->pool_index || !pb->log_p1 || !pb->log_p2 || !pb->sample_label)))) {
+    ltr::set_error(ctx, "ltr_plan_genotype: incomplete posterior batch"); return LTR_ERR_INVALID;
+  }
+  ltr::TimedCall timed(ctx, ltr::kTimerPosterior);             // total_posterior_time_, genotyper.cpp:46,:80-81
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  LTR_GUARD_BEGIN
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  LlSource src;                                                // the plan's buffer, byte for byte what the stages read before they took a source
+  src.base = plan->last_out; src.locus_off = plan->locus_ll_off.data(); src.H = plan->locus_H.data(); src.P = plan->locus_P.data();
+  src.pool_seed = plan->seed.data();
+  GtCall c(ctx, plan->last_stream, src, gb, fr);
+  return genotype_stages(c, nullptr, out);
   LTR_GUARD_END(ctx)
 }
 
@@ -516,6 +608,40 @@ int ltr_plan_genotype_fields(ltr_plan* plan, const ltr_genotype_batch* gb, const
   if (out) *out = nullptr;
   if (!fr) return LTR_ERR_INVALID;
   return plan_genotype(plan, gb, fr, out);
+}
+
+int ltr_ll_genotype(ltr_ctx* ctx, const ltr_ll_batch* lb, const ltr_genotype_batch* gb, const ltr_fields_request* fr, ltr_genotype_result** out) {
+  if (out) *out = nullptr;
+  if (!ctx || !lb || !gb || !gb->pb || !out) return LTR_ERR_INVALID;
+  const ltr_posterior_batch* pb = gb->pb;
+  const int64_t nl = pb->n_loci;
+  if (nl < 0) { ltr::set_error(ctx, "ltr_ll_genotype: a negative number of loci"); return LTR_ERR_INVALID; }
+  if (nl > 0 && (!lb->log_aln_probs || !lb->n_haps)) { ltr::set_error(ctx, "ltr_ll_genotype: incomplete LL batch (locus 0: no matrix list or no n_haps)"); return LTR_ERR_INVALID; }
+  if (!gb->haps && nl > 0 && (gb->prune || fr)) {
+    ltr::set_error(ctx, "ltr_ll_genotype: no haplotype blocks (locus 0 and every other: pruning and the fields need them)"); return LTR_ERR_INVALID;
+  }
+  if (nl > 0 && (!pb->locus_read_off || !pb->n_samples || (pb->n_reads > 0 && (!pb->log_p1 || !pb->log_p2 || !pb->sample_label)))) {
+    ltr::set_error(ctx, "ltr_ll_genotype: incomplete posterior batch"); return LTR_ERR_INVALID;
+  }
+  ltr::TimedCall timed(ctx, ltr::kTimerPosterior);
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  LTR_GUARD_BEGIN
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  LlSource src;
+  src.direct = true; src.H = lb->n_haps; src.read_seed = lb->seed_positions; src.who = "ltr_ll_genotype";
+  GtCall c(ctx, ctx->stream, src, gb, fr);
+  c.ll_off.assign((size_t)nl + 1, 0);                          // the blocks back to back, [R_l x H_l] each
+  for (int64_t l = 0; l < nl; ++l) {
+    const int64_t r0 = pb->locus_read_off[l], r1 = pb->locus_read_off[l + 1];
+    const int32_t H = lb->n_haps[l];
+    if (r0 < 0 || r1 < r0 || r1 > pb->n_reads || r1 > 0x7fffffff) { ltr::set_error(ctx, "bad posterior batch offsets (locus " + std::to_string(l) + ")"); return LTR_ERR_INVALID; }
+    if (H <= 0) { ltr::set_error(ctx, "ltr_ll_genotype: locus " + std::to_string(l) + ": n_haps must be positive"); return LTR_ERR_INVALID; }
+    if (r1 > r0 && !lb->log_aln_probs[l]) { ltr::set_error(ctx, "ltr_ll_genotype: locus " + std::to_string(l) + " has reads and no matrix"); return LTR_ERR_INVALID; }
+    c.ll_off[(size_t)l + 1] = c.ll_off[(size_t)l] + (r1 - r0) * (int64_t)H;
+  }
+  c.src.locus_off = c.ll_off.data();
+  return genotype_stages(c, lb, out);
+  LTR_GUARD_END(ctx)
 }
 
 void ltr_genotype_result_free(ltr_genotype_result* r) { delete r; }

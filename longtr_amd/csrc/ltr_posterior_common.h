@@ -42,16 +42,30 @@ __device__ __forceinline__ void ltr_normalise_argmax(double* p, int H, double* s
   gts[2 * slot] = b1; gts[2 * slot + 1] = b2;
 }
 
-// the read arrays of a posterior batch on the device
+// Where the log-likelihoods of a genotype call (ltr_plan_genotype.hip, ltr_plan_fields.hip) lie and how they are read:
+//   a plan's LL buffer    [P_l x H_l] blocks at the plan's offsets; a read's row is its pool's; seeds per pool, all loci back to back
+//   per-read matrices     (ltr_ll_genotype) [R_l x H_l] blocks uploaded back to back; a read's row is its own; seeds per read
+struct LlSource {
+  const double* base = nullptr;                // device
+  const int64_t* locus_off = nullptr;          // [n_loci] (host) the locus block in base
+  const int32_t* H = nullptr;                  // [n_loci] (host) its row length
+  const int32_t* P = nullptr;                  // [n_loci] (host) its rows; null with direct (one per read)
+  bool direct = false;                         // the read-to-row rule: false = pool_index[r], true = r - r0 (no pool_index anywhere)
+  const int32_t* pool_seed = nullptr;          // (host) seed position per pool
+  const int32_t* const* read_seed = nullptr;   // direct: [n_loci] seed position per read; null, or a null entry: every read aligned
+  const char* who = "ltr_plan_genotype";       // the entry point, for error texts
+};
+
+// the read arrays of a posterior batch on the device (pool_index: null when the LL source has a row per read)
 struct DevReads { int32_t *pool_index = nullptr, *label = nullptr; double *lp1 = nullptr, *lp2 = nullptr; };
-inline int upload_reads(ltr_ctx* ctx, DevLease& lease, const ltr_posterior_batch* pb, DevReads* d) {
+inline int upload_reads(ltr_ctx* ctx, DevLease& lease, const ltr_posterior_batch* pb, DevReads* d, bool with_pool_index = true) {
   const size_t nr = (size_t)pb->n_reads, n1 = std::max<size_t>(nr, 1);
-  DEV_TRY(ctx, lease.alloc(&d->pool_index, n1 * 4));
+  if (with_pool_index) DEV_TRY(ctx, lease.alloc(&d->pool_index, n1 * 4));
   DEV_TRY(ctx, lease.alloc(&d->label, n1 * 4));
   DEV_TRY(ctx, lease.alloc(&d->lp1, n1 * 8));
   DEV_TRY(ctx, lease.alloc(&d->lp2, n1 * 8));
   if (nr == 0) return LTR_OK;
-  DEV_TRY(ctx, hipMemcpyAsync(d->pool_index, pb->pool_index, nr * 4, hipMemcpyHostToDevice, lease.st));
+  if (with_pool_index) DEV_TRY(ctx, hipMemcpyAsync(d->pool_index, pb->pool_index, nr * 4, hipMemcpyHostToDevice, lease.st));
   DEV_TRY(ctx, hipMemcpyAsync(d->label, pb->sample_label, nr * 4, hipMemcpyHostToDevice, lease.st));
   DEV_TRY(ctx, hipMemcpyAsync(d->lp1, pb->log_p1, nr * 8, hipMemcpyHostToDevice, lease.st));
   DEV_TRY(ctx, hipMemcpyAsync(d->lp2, pb->log_p2, nr * 8, hipMemcpyHostToDevice, lease.st));
