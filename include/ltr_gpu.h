@@ -406,6 +406,18 @@ typedef struct ltr_posterior_batch {
 } ltr_posterior_batch;
 int ltr_plan_posteriors(ltr_plan* plan, const ltr_posterior_batch* pb,
                         double* log_sample_posteriors, double* sample_total_ll, int32_t* gts);
+/*
+ * Per-locus ploidy.  The reference decides ploidy per CHROMOSOME: genotyper_bam_processor.cpp:248 sets `haploid` for a locus whose
+ * chromosome is in --haploid-chrs and hands it to the locus's SeqStutterGenotyper (:294), from where it reaches the priors
+ * (genotyper.cpp:21-33), extract_genotypes_and_likelihoods (:132-256) and the FORMAT layout of write_vcf_record.  A resident
+ * plan, a shard or an LL batch cuts across chromosomes, so every batched consumer has a *_ploidy form that takes
+ *   locus_haploid  [n_loci], != 0 = the locus is on a haploid chromosome; NULL = pb->haploid for every locus.
+ *                  When given, pb->haploid is not read.
+ * Loci are independent: locus l of a mixed call carries the bits of the uniform call with haploid = (locus_haploid[l] != 0).
+ * ltr_plan_posteriors is this call with locus_haploid = NULL.
+ */
+int ltr_plan_posteriors_ploidy(ltr_plan* plan, const ltr_posterior_batch* pb, const uint8_t* locus_haploid,
+                               double* log_sample_posteriors, double* sample_total_ll, int32_t* gts);
 
 /* ---- consumer, next step: genotype fields ------------------------------------ */
 /*
@@ -603,6 +615,8 @@ void ltr_genotype_result_free(ltr_genotype_result* r);
  *   log_sample_posteriors [S x H' x H'], sample_total_ll [S], gts [S x 2] in the NEW indices
  *   read_ll         [R x H'] log_aln_probs_ per READ (not per pool), clamped at -600 as genotyper.cpp:57-58 leaves it: what
  *                   ltr_vcf_locus.log_aln_probs wants (NULL unless want_read_ll) */
+/* the ploidy locus l was genotyped with, whichever entry point made the result: 0 / 1, negative for a bad index */
+int32_t        ltr_genotype_result_haploid(const ltr_genotype_result* r, int64_t l);
 int64_t        ltr_genotype_result_n_loci(const ltr_genotype_result* r);
 int32_t        ltr_genotype_result_n_haps(const ltr_genotype_result* r, int64_t l);
 const int32_t* ltr_genotype_result_new_to_old(const ltr_genotype_result* r, int64_t l);
@@ -646,6 +660,13 @@ typedef struct ltr_fields_request {
   int32_t want_posteriors;     /* 0: the S x H' x H' blocks are NOT downloaded (ltr_genotype_result_log_sample_posteriors returns NULL) */
 } ltr_fields_request;
 int ltr_plan_genotype_fields(ltr_plan* plan, const ltr_genotype_batch* gb, const ltr_fields_request* fr, ltr_genotype_result** out);
+/* ltr_plan_genotype (fr == NULL) / ltr_plan_genotype_fields (fr given) with the ploidy of every locus (genotyper_bam_processor.cpp:248,
+ * :294; see ltr_plan_posteriors_ploidy): the priors of both passes (genotyper.cpp:21-33, seq_stutter_genotyper.cpp:405-408), n_gl /
+ * n_pgl, the GL / PHASEDGL terms and the strand rule of the fields (genotyper.cpp:132-256) follow the locus's own ploidy; the packed
+ * gls / pls / phased_gls of a locus have its own widths.  Those two entry points are this call with locus_haploid = NULL; errors
+ * are theirs, whether or not locus_haploid is given. */
+int  ltr_plan_genotype_ploidy(ltr_plan* plan, const ltr_genotype_batch* gb, const ltr_fields_request* fr /* NULL = as ltr_plan_genotype */,
+                              const uint8_t* locus_haploid, ltr_genotype_result** out);
 /* The same consumer WITHOUT a plan: ltr_plan_genotype (fr == NULL) or ltr_plan_genotype_fields (fr given) on per-read matrices in
  * caller memory -- what ltr_calc_hap_aln_probs returns, the state of SeqStutterGenotyper at seq_stutter_genotyper.cpp:634, also
  * after the seeded stutter path, with mate rows summed (:546-559) or re-scored under realign_* masks.  Every read is its own row:
@@ -666,6 +687,10 @@ typedef struct ltr_ll_batch {
 } ltr_ll_batch;
 int ltr_ll_genotype(ltr_ctx* ctx, const ltr_ll_batch* lb, const ltr_genotype_batch* gb,
                     const ltr_fields_request* fr /* NULL = as ltr_plan_genotype */, ltr_genotype_result** out);
+/* ... with the ploidy of every locus (genotyper_bam_processor.cpp:248, :294), as ltr_plan_genotype_ploidy: locus_haploid [n_loci],
+ * NULL = gb->pb->haploid for every locus (that is ltr_ll_genotype). */
+int ltr_ll_genotype_ploidy(ltr_ctx* ctx, const ltr_ll_batch* lb, const ltr_genotype_batch* gb, const ltr_fields_request* fr,
+                           const uint8_t* locus_haploid, ltr_genotype_result** out);
 /* views into the result (LTR_ERR_INVALID for a result of ltr_plan_genotype, which has none) */
 int ltr_genotype_result_fields(const ltr_genotype_result* r, int64_t l, ltr_locus_fields* out);
 
@@ -724,7 +749,9 @@ void ltr_vcf_field_set_free(ltr_vcf_field_set* f);
 int64_t ltr_vcf_record_from_fields(const ltr_vcf_locus* v, const ltr_locus_fields* f, const ltr_vcf_options* opt, char* out, int64_t cap, int32_t* pos);
 /* Every locus' record of a ltr_plan_genotype_fields result through ltr_vcf_record_from_fields, on the library's worker pool
  * under the host-thread budget (ltr_ctx_set_host_threads); the text does not depend on the number of threads.
- * loci [n_loci]: hap and block of each are ignored (ltr_genotype_result_blocks and the block the fields were made for are used).
+ * loci [n_loci]: hap, block and haploid of each are ignored: ltr_genotype_result_blocks, the block the fields were made for and the
+ * ploidy the locus was genotyped with (ltr_genotype_result_haploid) are used, so a haploid locus gets FORMAT
+ * GT:GB:Q:DP:DFLANKINDEL:GLDIFF and V-wide GL / PL, a diploid one the ten-field form, V(V+1)/2-wide GL / PL and PHASEDGL.
  * *text: the records back to back in locus order, each followed by '\n', NUL-terminated, to be released with
  * ltr_vcf_text_free; record l is [rec_off[l], rec_off[l + 1] - 1) (rec_off [n_loci + 1]); pos [n_loci] optional.
  * On an error (LTR_ERR_INVALID, ltr_last_error names the locus) *text stays NULL and rec_off / pos are not written. */

@@ -47,6 +47,7 @@ EXPORTS = [
     "ltr_genotype_result_sample_total_ll", "ltr_genotype_result_gts", "ltr_genotype_result_read_ll",
     "ltr_plan_genotype_fields", "ltr_genotype_result_fields", "ltr_genotype_result_vcf_records", "ltr_vcf_text_free",
     "ltr_vcf_fields", "ltr_vcf_field_set_view", "ltr_vcf_field_set_free", "ltr_vcf_record_from_fields", "ltr_ll_genotype",
+    "ltr_plan_posteriors_ploidy", "ltr_plan_genotype_ploidy", "ltr_ll_genotype_ploidy", "ltr_genotype_result_haploid",
 ]
 
 
@@ -164,6 +165,7 @@ def lib():
     L.ltr_pool_reads.restype = i32
     L.ltr_scatter_pool_probs.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.ltr_plan_posteriors.argtypes = [vp, C.POINTER(_abi.PosteriorBatch), vp, vp, vp]
+    L.ltr_plan_posteriors_ploidy.argtypes = [vp, C.POINTER(_abi.PosteriorBatch), vp, vp, vp, vp]
     L.ltr_posteriors.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, C.POINTER(dbl)]
     _lib = L
     return L
@@ -402,11 +404,12 @@ class Context:
                     loci_blocks=loci_blocks if loci_blocks is not None else [[dict(alleles=[b""] * int(h))] for h in n_haps])
 
     def genotype_ll(self, ll_list=None, seed_list=None, loci_blocks=None, locus_read_off=None, log_p1=None, log_p2=None, sample_label=None,
-                    n_samples=None, haploid=False, prune=True, want_read_ll=False, fields=None, sample_filtered=None, packed=None):
+                    n_samples=None, haploid=False, prune=True, want_read_ll=False, fields=None, sample_filtered=None, packed=None, locus_haploid=None):
         """ltr_ll_genotype: what Plan.genotype / Plan.genotype_fields do for a resident plan, on per-read matrices in host
         memory -- the output of calc_hap_aln_probs (any path: plans, the seeded stutter path, mates summed, realign masks).
         fields: None = no VCF fields (as Plan.genotype; posterior blocks are downloaded), or a dict with any of block,
         want_gls, want_pls, want_phased_gls, want_posteriors (as Plan.genotype_fields).  packed: a pack_ll_genotype image.
+        locus_haploid: the ploidy of every locus (ltr_ll_genotype_ploidy; `haploid` is then not read), None = `haploid` for all.
         Returns a GenotypeResult (close() it, or use it as a context manager)."""
         if packed is None:
             packed = self.pack_ll_genotype(ll_list, seed_list, loci_blocks, locus_read_off, log_p1, log_p2, sample_label, n_samples, haploid,
@@ -424,7 +427,12 @@ class Context:
             for k in ("want_gls", "want_pls", "want_phased_gls", "want_posteriors"):
                 setattr(fr, k, int(bool(fields.get(k, False))))
         h = C.c_void_p()
-        self._check(L.ltr_ll_genotype(self._h, C.byref(packed["lb"]), C.byref(packed["gb"]), None if fr is None else C.byref(fr), C.byref(h)))
+        pfr = None if fr is None else C.byref(fr)
+        if locus_haploid is None:
+            self._check(L.ltr_ll_genotype(self._h, C.byref(packed["lb"]), C.byref(packed["gb"]), pfr, C.byref(h)))
+        else:
+            lh = _locus_haploid(locus_haploid, len(packed["n_samples"]))
+            self._check(L.ltr_ll_genotype_ploidy(self._h, C.byref(packed["lb"]), C.byref(packed["gb"]), pfr, _p(lh), C.byref(h)))
         return GenotypeResult(self, h, packed)
 
     def close(self):
@@ -813,8 +821,9 @@ class Plan:
         self.ctx._check(lib().ltr_plan_last_kernel_ms(self._h, C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
-    def posteriors(self, locus_read_off, pool_index, log_p1, log_p2, sample_label, n_samples, haploid=False):
+    def posteriors(self, locus_read_off, pool_index, log_p1, log_p2, sample_label, n_samples, haploid=False, locus_haploid=None):
         """ltr_plan_posteriors: all loci, from the device-resident LL of the last execute.
+        locus_haploid: the ploidy of every locus (ltr_plan_posteriors_ploidy; `haploid` is then not read), None = `haploid` for all.
         Returns (post_flat, post_off[units+1], sample_total_ll, gts[units,2]); units = (locus, sample) in order."""
         lro = np.ascontiguousarray(locus_read_off, dtype=np.int64)
         pi = np.ascontiguousarray(pool_index, dtype=np.int32)
@@ -839,7 +848,11 @@ class Plan:
         pb.sample_label = sl.ctypes.data_as(C.POINTER(C.c_int32))
         pb.n_samples = ns.ctypes.data_as(C.POINTER(C.c_int32))
         pb.haploid = int(haploid)
-        self.ctx._check(lib().ltr_plan_posteriors(self._h, C.byref(pb), _p(post), _p(stl), _p(gts)))
+        if locus_haploid is None:
+            self.ctx._check(lib().ltr_plan_posteriors(self._h, C.byref(pb), _p(post), _p(stl), _p(gts)))
+        else:
+            lh = _locus_haploid(locus_haploid, len(ns))
+            self.ctx._check(lib().ltr_plan_posteriors_ploidy(self._h, C.byref(pb), _p(lh), _p(post), _p(stl), _p(gts)))
         return post[:off[-1]], off, stl[:len(sizes)], gts[:2 * len(sizes)].reshape(-1, 2)
 
     def _posterior_batch(self, locus_read_off, pool_index, log_p1, log_p2, sample_label, n_samples, haploid):
@@ -873,12 +886,17 @@ class Plan:
         gb.prune, gb.want_read_ll = int(bool(prune)), int(bool(want_read_ll))
         return dict(gb=gb, keep=(pb, keep, phs, arr, sf), n_samples=keep[5], locus_read_off=keep[0], loci_blocks=loci_blocks)
 
-    def genotype_packed(self, packed, decode=True):
-        """ltr_plan_genotype on a pack_genotype image.  decode=False: run, free the result, return None (timing)."""
+    def genotype_packed(self, packed, decode=True, locus_haploid=None):
+        """ltr_plan_genotype on a pack_genotype image.  decode=False: run, free the result, return None (timing).
+        locus_haploid: the ploidy of every locus (ltr_plan_genotype_ploidy), None = the image's `haploid` for all."""
         L = lib()
         _bind_genotype(L)
         h = C.c_void_p()
-        self.ctx._check(L.ltr_plan_genotype(self._h, C.byref(packed["gb"]), C.byref(h)))
+        if locus_haploid is None:
+            self.ctx._check(L.ltr_plan_genotype(self._h, C.byref(packed["gb"]), C.byref(h)))
+        else:
+            lh = _locus_haploid(locus_haploid, len(packed["n_samples"]))
+            self.ctx._check(L.ltr_plan_genotype_ploidy(self._h, C.byref(packed["gb"]), None, _p(lh), C.byref(h)))
         try:
             if not decode:
                 return None
@@ -897,7 +915,7 @@ class Plan:
                 pruned = any(removed)
                 rll = L.ltr_genotype_result_read_ll(h, l)
                 out.append(dict(
-                    n_haps=Hn, new_to_old=take(L.ltr_genotype_result_new_to_old(h, l), Hn, np.int32), allele_mapping=take(a2n, Ho, np.int32),
+                    haploid=L.ltr_genotype_result_haploid(h, l), n_haps=Hn, new_to_old=take(L.ltr_genotype_result_new_to_old(h, l), Hn, np.int32), allele_mapping=take(a2n, Ho, np.int32),
                     removed=removed, num_aff_blocks=L.ltr_genotype_result_num_aff_blocks(h, l),
                     num_aff_alleles=L.ltr_genotype_result_num_aff_alleles(h, l),
                     blocks=_abi.blocks_from_struct(L.ltr_genotype_result_blocks(h, l).contents) if pruned else old,
@@ -910,21 +928,23 @@ class Plan:
             L.ltr_genotype_result_free(h)
 
     def genotype(self, loci_blocks, locus_read_off, pool_index, log_p1, log_p2, sample_label, n_samples, haploid=False,
-                 sample_filtered=None, prune=True, want_read_ll=True):
+                 sample_filtered=None, prune=True, want_read_ll=True, locus_haploid=None):
         """ltr_plan_genotype: SeqStutterGenotyper::genotype after the alignment for every locus of the executed plan --
         posteriors, uncalled alleles pruned once (prune=True), posteriors again over the surviving haplotypes.  Returns per
         locus a dict: n_haps, new_to_old, allele_mapping, removed (per block), num_aff_blocks / num_aff_alleles, blocks (the
-        final block list), post [S, H', H'], sample_total_ll [S], gts [S, 2] (new indices), read_ll [R, H'] or None."""
+        final block list), post [S, H', H'], sample_total_ll [S], gts [S, 2] (new indices), read_ll [R, H'] or None, haploid (0 / 1).
+        locus_haploid: the ploidy of every locus (a whole-genome plan with --haploid-chrs), None = `haploid` for all."""
         return self.genotype_packed(self.pack_genotype(loci_blocks, locus_read_off, pool_index, log_p1, log_p2, sample_label, n_samples,
-                                                       haploid, sample_filtered, prune, want_read_ll))
+                                                       haploid, sample_filtered, prune, want_read_ll), locus_haploid=locus_haploid)
 
     def genotype_fields(self, loci_blocks=None, locus_read_off=None, pool_index=None, log_p1=None, log_p2=None, sample_label=None,
                         n_samples=None, haploid=False, sample_filtered=None, prune=True, want_read_ll=False, block=None,
-                        want_gls=False, want_pls=False, want_phased_gls=False, want_posteriors=False, packed=None):
+                        want_gls=False, want_pls=False, want_phased_gls=False, want_posteriors=False, packed=None, locus_haploid=None):
         """ltr_plan_genotype_fields: ltr_plan_genotype and the VCF fields of every locus computed on the device (GT, Q, PQ,
         GLDIFF, DP, DSNP, PSNP, MALLREADS' alleles; GL / PL / PHASEDGL on request).  block: per locus, None = the first repeat
         block.  Posterior blocks / per-read matrices are downloaded only when asked for.  packed: a pack_genotype image (its
-        want_read_ll holds).  Returns a GenotypeResult (close() it, or use it as a context manager)."""
+        want_read_ll holds).  locus_haploid: the ploidy of every locus (ltr_plan_genotype_ploidy), None = `haploid` for all.
+        Returns a GenotypeResult (close() it, or use it as a context manager)."""
         if packed is None:
             packed = self.pack_genotype(loci_blocks, locus_read_off, pool_index, log_p1, log_p2, sample_label, n_samples, haploid,
                                         sample_filtered, prune, want_read_ll)
@@ -939,7 +959,11 @@ class Plan:
         fr.want_gls, fr.want_pls, fr.want_phased_gls = int(bool(want_gls)), int(bool(want_pls)), int(bool(want_phased_gls))
         fr.want_posteriors = int(bool(want_posteriors))
         h = C.c_void_p()
-        self.ctx._check(L.ltr_plan_genotype_fields(self._h, C.byref(packed["gb"]), C.byref(fr), C.byref(h)))
+        if locus_haploid is None:
+            self.ctx._check(L.ltr_plan_genotype_fields(self._h, C.byref(packed["gb"]), C.byref(fr), C.byref(h)))
+        else:
+            lh = _locus_haploid(locus_haploid, len(packed["n_samples"]))
+            self.ctx._check(L.ltr_plan_genotype_ploidy(self._h, C.byref(packed["gb"]), C.byref(fr), _p(lh), C.byref(h)))
         return GenotypeResult(self.ctx, h, packed)
 
     def set_timing(self, on=True):
@@ -1214,6 +1238,13 @@ class GenotypeResult:
     def n_loci(self):
         return int(lib().ltr_genotype_result_n_loci(self._h))
 
+    def haploid(self, l):
+        """ltr_genotype_result_haploid: the ploidy locus l was genotyped with (0 / 1)."""
+        rc = lib().ltr_genotype_result_haploid(self._h, int(l))
+        if rc < 0:
+            raise LtrError(rc, "ltr_genotype_result_haploid")
+        return int(rc)
+
     def fields(self, l):
         """The LocusFields.to_dict() image of locus l (copies)."""
         f = _abi.LocusFields()
@@ -1248,7 +1279,7 @@ class GenotypeResult:
 
     def vcf_records(self, packed_vcf_loci, options=None):
         """ltr_genotype_result_vcf_records: (list of VCF lines, positions) for every locus, formatted on the worker pool.
-        packed_vcf_loci: one _abi.PackedVcfLocus per locus (its blocks / block are replaced by the result's own)."""
+        packed_vcf_loci: one _abi.PackedVcfLocus per locus (its blocks / block / haploid are replaced by the result's own)."""
         L = lib()
         n = self.n_loci
         if len(packed_vcf_loci) != n:
@@ -1265,12 +1296,20 @@ class GenotypeResult:
         return [raw[off[l]:off[l + 1] - 1].decode() for l in range(n)], pos[:n].copy()
 
 
+def _locus_haploid(locus_haploid, n_loci):
+    """The [n_loci] uint8 array of the *_ploidy entry points."""
+    lh = np.ascontiguousarray(locus_haploid).astype(bool).astype(np.uint8)
+    if lh.shape != (n_loci,):
+        raise LtrError(_abi.LTR_ERR_INVALID, "locus_haploid: one entry per locus")
+    return lh
+
+
 def _bind_genotype(L):
     vp, i64, i32 = C.c_void_p, C.c_int64, C.c_int32
     L.ltr_plan_genotype.argtypes = [vp, C.POINTER(_abi.GenotypeBatch), C.POINTER(vp)]
     L.ltr_genotype_result_free.argtypes, L.ltr_genotype_result_free.restype = [vp], None
     L.ltr_genotype_result_n_loci.argtypes, L.ltr_genotype_result_n_loci.restype = [vp], i64
-    for f, rt in (("n_haps", i32), ("num_aff_blocks", i32), ("num_aff_alleles", i32), ("new_to_old", C.POINTER(i32)),
+    for f, rt in (("n_haps", i32), ("haploid", i32), ("num_aff_blocks", i32), ("num_aff_alleles", i32), ("new_to_old", C.POINTER(i32)),
                   ("allele_mapping", C.POINTER(i32)), ("gts", C.POINTER(i32)), ("blocks", C.POINTER(_abi.HaplotypeBlocks)),
                   ("log_sample_posteriors", C.POINTER(C.c_double)), ("sample_total_ll", C.POINTER(C.c_double)), ("read_ll", C.POINTER(C.c_double))):
         fn = getattr(L, "ltr_genotype_result_" + f)
@@ -1278,6 +1317,8 @@ def _bind_genotype(L):
     L.ltr_genotype_result_removed.argtypes, L.ltr_genotype_result_removed.restype = [vp, i64, i32, C.POINTER(C.POINTER(i32))], i32
     L.ltr_plan_genotype_fields.argtypes = [vp, C.POINTER(_abi.GenotypeBatch), C.POINTER(_abi.FieldsRequest), C.POINTER(vp)]
     L.ltr_ll_genotype.argtypes = [vp, C.POINTER(_abi.LlBatch), C.POINTER(_abi.GenotypeBatch), C.POINTER(_abi.FieldsRequest), C.POINTER(vp)]
+    L.ltr_plan_genotype_ploidy.argtypes = [vp, C.POINTER(_abi.GenotypeBatch), C.POINTER(_abi.FieldsRequest), vp, C.POINTER(vp)]
+    L.ltr_ll_genotype_ploidy.argtypes = [vp, C.POINTER(_abi.LlBatch), C.POINTER(_abi.GenotypeBatch), C.POINTER(_abi.FieldsRequest), vp, C.POINTER(vp)]
     L.ltr_genotype_result_fields.argtypes = [vp, i64, C.POINTER(_abi.LocusFields)]
     L.ltr_genotype_result_vcf_records.argtypes = [vp, C.POINTER(_abi.VcfLocus), C.POINTER(_abi.VcfOptions), C.POINTER(vp), vp, vp]
     L.ltr_vcf_text_free.argtypes, L.ltr_vcf_text_free.restype = [vp], None

@@ -19,6 +19,7 @@ struct LtrPruned {
 struct ltr_genotype_result {
   int64_t n_loci = 0;
   std::vector<int32_t> S, H, n_blocks;           // per locus
+  std::vector<uint8_t> haploid;                  // per locus: its ploidy, resolved once at the top of the call (LocusPloidy); every stage reads this
   std::vector<int64_t> unit_off, post1_off;      // [n_loci + 1]
   std::unique_ptr<double[]> post1, post2, read_ll;      // first-pass blocks (plan's H), second-pass blocks of the pruned loci
   std::vector<double> stl;                       // [units] final
@@ -30,7 +31,6 @@ struct ltr_genotype_result {
   // ---- ltr_plan_genotype_fields only ----
   bool has_fields = false;
   ltr_ctx* ctx = nullptr;                        // (for ltr_last_error of ltr_genotype_result_vcf_records)
-  int32_t haploid = 0;
   std::vector<int32_t> f_block, f_V;             // per locus: the block the fields are for, its alleles
   std::vector<int64_t> f_gl_off, f_pgl_off, f_read_off;   // [n_loci + 1]: gls / pls, phased_gls, reads
   std::unique_ptr<int32_t[]> f_i32;              // best_gts [2 nu], n_aligned, n_snp, n_s1, n_s2 [nu each], read_allele [reads]

@@ -243,14 +243,15 @@ int64_t layout_loci(const LlSource* src, const ltr_genotype_batch* gb, ltr_genot
     FieldLocus& F = floci[(size_t)l];
     F.ll_off = src->locus_off[l]; F.map_off = p ? mo : -1; F.tab_off = tab;
     F.gl_off = res->f_gl_off[(size_t)l]; F.pgl_off = res->f_pgl_off[(size_t)l];
-    F.r0 = (int32_t)pb->locus_read_off[l]; F.r1 = (int32_t)pb->locus_read_off[l + 1]; F.H = H; F.Hn = Hn; F.V = V; F.haploid = pb->haploid ? 1 : 0;
-    F.n_gl = pb->haploid ? V : V * (V + 1) / 2; F.n_pgl = pb->haploid ? V : V * V;
+    const int haploid = res->haploid[(size_t)l];                 // the locus's own (genotyper_bam_processor.cpp:248 -> :294): widths, priors and offsets below follow it
+    F.r0 = (int32_t)pb->locus_read_off[l]; F.r1 = (int32_t)pb->locus_read_off[l + 1]; F.H = H; F.Hn = Hn; F.V = V; F.haploid = haploid;
+    F.n_gl = haploid ? V : V * (V + 1) / 2; F.n_pgl = haploid ? V : V * V;
     // priors (the heterozygous one of a haploid call is 0, genotyper.cpp:210) and configuration terms (:204-241) as ltr_genotype.cpp:108-111
     double hom_prior, het_prior;
-    ltr_log_priors(Hn, pb->haploid, &hom_prior, &het_prior);
-    if (pb->haploid) het_prior = 0.0;
+    ltr_log_priors(Hn, haploid, &hom_prior, &het_prior);
+    if (haploid) het_prior = 0.0;
     const double lH = std::log((double)Hn), lV = std::log((double)V), l2 = std::log(2.0);
-    const double gl_cfg = pb->haploid ? l2 + lH - lV : l2 + 2 * (lH - lV), pgl_cfg = pb->haploid ? lH - lV : 2 * (lH - lV);
+    const double gl_cfg = haploid ? l2 + lH - lV : l2 + 2 * (lH - lV), pgl_cfg = haploid ? lH - lV : 2 * (lH - lV);
     F.hom_gl = hom_prior + gl_cfg; F.het_gl = het_prior + gl_cfg; F.hom_pgl = hom_prior + pgl_cfg; F.het_pgl = het_prior + pgl_cfg;
     if (p) mo += p->Hn;
     tab += 2 * (int64_t)Hn + V + 1;
@@ -377,7 +378,8 @@ int ltr_genotype_result_fields(const ltr_genotype_result* r, int64_t l, ltr_locu
   const int64_t nu = r->unit_off[(size_t)r->n_loci], u0 = r->unit_off[(size_t)l];
   const int32_t S = r->S[(size_t)l], V = r->f_V[(size_t)l];
   out->S = S; out->R = (int32_t)(r->f_read_off[(size_t)l + 1] - r->f_read_off[(size_t)l]); out->V = V; out->block = r->f_block[(size_t)l];
-  out->n_gl = r->haploid ? V : V * (V + 1) / 2; out->n_pgl = r->haploid ? V : V * V;
+  const bool haploid = r->haploid[(size_t)l] != 0;
+  out->n_gl = haploid ? V : V * (V + 1) / 2; out->n_pgl = haploid ? V : V * V;
   const int32_t* i32 = r->f_i32.get();
   const double* f64 = r->f_f64.get();
   out->best_gts = i32 + 2 * u0;
@@ -407,6 +409,7 @@ int ltr_genotype_result_vcf_records(const ltr_genotype_result* r, const ltr_vcf_
     ltr_vcf_locus v = loci[l];
     v.hap = ltr_genotype_result_blocks(r, l);                   // the final block list (the pruned copy, or the caller's)
     v.block = r->f_block[(size_t)l];
+    v.haploid = r->haploid[(size_t)l];                          // the ploidy the fields were made with: FORMAT and the GL / PL / PHASEDGL widths
     int64_t rc = ltr_genotype_result_fields(r, l, &f);
     if (rc == LTR_OK) rc = ltr::vcf_record_string(&v, &f, opt, &rec[(size_t)l], &rpos[(size_t)l]);
     if (rc < 0) {

@@ -245,6 +245,7 @@ struct GtCall {
   LlSource src;                                     // where the scores lie and how a read finds its row: the plan's buffer, or the block upload_ll fills
   std::vector<int64_t> ll_off;                      // ... the locus offsets of that block (src.locus_off)
   PinnedPair stage;                                 // ... its staging
+  const uint8_t* locus_haploid;                     // the caller's ploidy per locus; null: pb->haploid for all (resolved into res->haploid by layout_units)
   std::unique_ptr<ltr_genotype_result> res;
   GtUnit* units = nullptr; size_t nu = 0;           // the first pass's units (ctx->gt_units)
   std::vector<uint8_t> aligned;                     // per unit: one of the sample's reads was aligned (:262-266)
@@ -252,8 +253,8 @@ struct GtCall {
   double* stl2 = nullptr; int32_t* gts2 = nullptr;  // ... its totals and best pairs (lease.host)
   DevReads rd; int32_t* d_map = nullptr; DevPass pass[2];
   DevLease lease;
-  GtCall(ltr_ctx* x, hipStream_t st, const LlSource& s, const ltr_genotype_batch* g, const ltr_fields_request* f)
-      : ctx(x), gb(g), pb(g->pb), fr(f), src(s), stage(x), res(new ltr_genotype_result()), lease(x, st) {}
+  GtCall(ltr_ctx* x, hipStream_t st, const LlSource& s, const ltr_genotype_batch* g, const ltr_fields_request* f, const uint8_t* lh)
+      : ctx(x), gb(g), pb(g->pb), fr(f), src(s), stage(x), locus_haploid(lh), res(new ltr_genotype_result()), lease(x, st) {}
 };
 
 // ---- host, all loci at once: the result laid out, labels checked, every sample's reads listed in read order, aligned_read (:262-266) ----
@@ -269,6 +270,8 @@ int layout_units(GtCall& c) {
   if (gb->haps) res->haps.assign(gb->haps, gb->haps + nl); else res->haps.assign((size_t)nl, nullptr);
   res->unit_off.assign((size_t)nl + 1, 0); res->post1_off.assign((size_t)nl + 1, 0);
   res->pruned.resize((size_t)nl); res->n_blocks.assign((size_t)nl, 0);
+  res->haploid.assign((size_t)std::max<int64_t>(nl, 0), 0);
+  const LocusPloidy ploidy(pb, c.locus_haploid);
   std::vector<int64_t> pool_base(src.direct ? 0 : (size_t)nl + 1, 0);   // first pool (= read of the plan) of every locus
   int32_t max_H = 1;
   for (int64_t l = 0; l < nl; ++l) {
@@ -280,6 +283,7 @@ int layout_units(GtCall& c) {
     res->post1_off[(size_t)l + 1] = res->post1_off[(size_t)l] + (int64_t)S * H * H;
     if (!src.direct) pool_base[(size_t)l + 1] = pool_base[(size_t)l] + src.P[l];
     max_H = std::max(max_H, H);
+    res->haploid[(size_t)l] = (uint8_t)ploidy(l);
   }
   const size_t nu = c.nu = (size_t)res->unit_off[(size_t)nl];
   res->identity.resize((size_t)max_H);
@@ -291,7 +295,7 @@ int layout_units(GtCall& c) {
   c.aligned.assign(nu, 0);
   std::atomic<int> bad(0);
   std::atomic<int64_t> bad_haps(-1), bad_block(-1);
-  if (fr) { res->has_fields = true; res->ctx = ctx; res->haploid = pb->haploid ? 1 : 0; res->f_block.assign((size_t)nl, 0); res->f_V.assign((size_t)nl, 0); }
+  if (fr) { res->has_fields = true; res->ctx = ctx; res->f_block.assign((size_t)nl, 0); res->f_V.assign((size_t)nl, 0); }
   ltr::parallel_for(nl, 64, [&](int64_t l) {
     const int64_t r0 = pb->locus_read_off[l], r1 = pb->locus_read_off[l + 1], u0 = res->unit_off[(size_t)l];
     const int32_t S = pb->n_samples[l], H = src.H[l];
@@ -326,7 +330,7 @@ int layout_units(GtCall& c) {
       u.ll_off = src.locus_off[l]; u.post_off = res->post1_off[(size_t)l] + (int64_t)s * H * H; u.map_off = -1;
       u.r0 = (int32_t)r0; u.r1 = (int32_t)r1;
       u.H = H; u.Hn = H; u.out = (int32_t)(u0 + s); u.sample = s;
-      ltr_log_priors(H, pb->haploid, &u.homoz, &u.hetz);
+      ltr_log_priors(H, res->haploid[(size_t)l], &u.homoz, &u.hetz);
     }
   });
   if (bad_haps.load() >= 0) {
@@ -424,7 +428,7 @@ int prune_uncalled(GtCall& c) {
     for (int32_t s = 0; s < S; ++s) {
       GtUnit u = c.units[(size_t)(res->unit_off[(size_t)l] + s)];
       u.post_off = c.npost2 + (int64_t)s * p->Hn * p->Hn; u.map_off = map_off; u.Hn = p->Hn; u.out = (int32_t)c.units2.size();
-      ltr_log_priors(p->Hn, c.pb->haploid, &u.homoz, &u.hetz);  // :405-408: priors of the new number of haplotypes
+      ltr_log_priors(p->Hn, res->haploid[(size_t)l], &u.homoz, &u.hetz);   // :405-408: priors of the new number of haplotypes, the locus's ploidy
       c.units2.push_back(u);
     }
     c.npost2 += (int64_t)S * p->Hn * p->Hn;
@@ -575,8 +579,8 @@ int genotype_stages(GtCall& c, const ltr_ll_batch* lb, ltr_genotype_result** out
 
 }  // namespace
 
-// ltr_plan_genotype (fr == null) and ltr_plan_genotype_fields: the stages on the LL buffer of the plan's last execute
-static int plan_genotype(ltr_plan* plan, const ltr_genotype_batch* gb, const ltr_fields_request* fr, ltr_genotype_result** out) {
+// ltr_plan_genotype (fr == null), ltr_plan_genotype_fields and ltr_plan_genotype_ploidy: the stages on the LL buffer of the plan's last execute
+static int plan_genotype(ltr_plan* plan, const ltr_genotype_batch* gb, const ltr_fields_request* fr, const uint8_t* locus_haploid, ltr_genotype_result** out) {
   if (out) *out = nullptr;
   if (!plan || !gb || !gb->pb || !out) return LTR_ERR_INVALID;
   ltr_ctx* ctx = plan->ctx;
@@ -596,21 +600,26 @@ static int plan_genotype(ltr_plan* plan, const ltr_genotype_batch* gb, const ltr
   LlSource src;                                                // the plan's buffer, byte for byte what the stages read before they took a source
   src.base = plan->last_out; src.locus_off = plan->locus_ll_off.data(); src.H = plan->locus_H.data(); src.P = plan->locus_P.data();
   src.pool_seed = plan->seed.data();
-  GtCall c(ctx, plan->last_stream, src, gb, fr);
+  GtCall c(ctx, plan->last_stream, src, gb, fr, locus_haploid);
   return genotype_stages(c, nullptr, out);
   LTR_GUARD_END(ctx)
 }
 
 extern "C" {
 
-int ltr_plan_genotype(ltr_plan* plan, const ltr_genotype_batch* gb, ltr_genotype_result** out) { return plan_genotype(plan, gb, nullptr, out); }
+// the ploidy per locus (genotyper_bam_processor.cpp:248 -> :294); the two entry points below are this one with locus_haploid = null
+int ltr_plan_genotype_ploidy(ltr_plan* plan, const ltr_genotype_batch* gb, const ltr_fields_request* fr, const uint8_t* locus_haploid, ltr_genotype_result** out) {
+  return plan_genotype(plan, gb, fr, locus_haploid, out);
+}
+int ltr_plan_genotype(ltr_plan* plan, const ltr_genotype_batch* gb, ltr_genotype_result** out) { return ltr_plan_genotype_ploidy(plan, gb, nullptr, nullptr, out); }
 int ltr_plan_genotype_fields(ltr_plan* plan, const ltr_genotype_batch* gb, const ltr_fields_request* fr, ltr_genotype_result** out) {
   if (out) *out = nullptr;
   if (!fr) return LTR_ERR_INVALID;
-  return plan_genotype(plan, gb, fr, out);
+  return ltr_plan_genotype_ploidy(plan, gb, fr, nullptr, out);
 }
 
-int ltr_ll_genotype(ltr_ctx* ctx, const ltr_ll_batch* lb, const ltr_genotype_batch* gb, const ltr_fields_request* fr, ltr_genotype_result** out) {
+int ltr_ll_genotype_ploidy(ltr_ctx* ctx, const ltr_ll_batch* lb, const ltr_genotype_batch* gb, const ltr_fields_request* fr, const uint8_t* locus_haploid,
+                           ltr_genotype_result** out) {
   if (out) *out = nullptr;
   if (!ctx || !lb || !gb || !gb->pb || !out) return LTR_ERR_INVALID;
   const ltr_posterior_batch* pb = gb->pb;
@@ -629,7 +638,7 @@ int ltr_ll_genotype(ltr_ctx* ctx, const ltr_ll_batch* lb, const ltr_genotype_bat
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   LlSource src;
   src.direct = true; src.H = lb->n_haps; src.read_seed = lb->seed_positions; src.who = "ltr_ll_genotype";
-  GtCall c(ctx, ctx->stream, src, gb, fr);
+  GtCall c(ctx, ctx->stream, src, gb, fr, locus_haploid);
   c.ll_off.assign((size_t)nl + 1, 0);                          // the blocks back to back, [R_l x H_l] each
   for (int64_t l = 0; l < nl; ++l) {
     const int64_t r0 = pb->locus_read_off[l], r1 = pb->locus_read_off[l + 1];
@@ -643,11 +652,18 @@ int ltr_ll_genotype(ltr_ctx* ctx, const ltr_ll_batch* lb, const ltr_genotype_bat
   return genotype_stages(c, lb, out);
   LTR_GUARD_END(ctx)
 }
+int ltr_ll_genotype(ltr_ctx* ctx, const ltr_ll_batch* lb, const ltr_genotype_batch* gb, const ltr_fields_request* fr, ltr_genotype_result** out) {
+  return ltr_ll_genotype_ploidy(ctx, lb, gb, fr, nullptr, out);
+}
 
 void ltr_genotype_result_free(ltr_genotype_result* r) { delete r; }
 
 #define GT_LOCUS(r, l, fail) if (!(r) || (l) < 0 || (l) >= (r)->n_loci) return fail
 int64_t ltr_genotype_result_n_loci(const ltr_genotype_result* r) { return r ? r->n_loci : LTR_ERR_INVALID; }
+int32_t ltr_genotype_result_haploid(const ltr_genotype_result* r, int64_t l) {
+  GT_LOCUS(r, l, LTR_ERR_INVALID);
+  return r->haploid[(size_t)l] ? 1 : 0;
+}
 int32_t ltr_genotype_result_n_haps(const ltr_genotype_result* r, int64_t l) {
   GT_LOCUS(r, l, LTR_ERR_INVALID);
   return r->pruned[(size_t)l] ? r->pruned[(size_t)l]->Hn : r->H[(size_t)l];

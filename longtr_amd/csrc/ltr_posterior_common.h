@@ -14,6 +14,15 @@ inline void ltr_log_priors(int32_t H, int haploid, double* homoz, double* hetz) 
   *hetz = haploid ? -1.7976931348623157e308 / 2 : -lH - lH1;
 }
 
+// The ploidy of every locus of a call.  The reference decides it per chromosome (genotyper_bam_processor.cpp:248 -> :294, --haploid-chrs);
+// a plan or an LL batch cuts across chromosomes, so the *_ploidy entry points take it per locus: the caller's array [n_loci]
+// (pb->haploid is then not read), or null = pb->haploid for every locus.
+struct LocusPloidy {
+  const uint8_t* per_locus; int batch;
+  LocusPloidy(const ltr_posterior_batch* pb, const uint8_t* locus_haploid) : per_locus(locus_haploid), batch(locus_haploid ? 0 : (pb->haploid ? 1 : 0)) {}
+  int operator()(int64_t l) const { return per_locus ? (per_locus[l] ? 1 : 0) : batch; }
+};
+
 // column a of a read's row in the final haplotype order (cmap: new_to_old, null = identity), clamped
 __device__ __forceinline__ double ltr_clamped_ll(const double* __restrict__ row, const int32_t* __restrict__ cmap, int a) {
   const int src = cmap ? cmap[a] : a;
