@@ -223,7 +223,10 @@ __device__ double short_side(const ShortArgs& A, const Side& sd, const double* a
             if (-i < block_len + D) { LN(lp, np) = A.int_log[block_len + D + i] + log_prob; np++; }
             prob = d_flse(lp, np, lane, A.log_thresh);
           }
-          const double pre_prob = (j - base_len < 0 ? 0 : LN(Mp, j - base_len));
+          // An EMPTY block's row is the row before it (:72-73: matrix_index == prev_row_index): the reference fills it in place, so an
+          // insertion (base_len > 0) reads the block-row values of the positions before j, not the flank row's
+          const double* Pv = (block_len == 0 && base_len > 0) ? Mc : Mp;
+          const double pre_prob = (j - base_len < 0 ? 0 : LN(Pv, j - base_len));
           bp[art_idx] = art[art_idx] + prob + pre_prob;                // :91
         }
         // fast_log_sum_exp(block_probs), :103
@@ -517,6 +520,10 @@ __global__ __launch_bounds__(kShortThreads) __attribute__((amdgpu_waves_per_eu(8
     double* g_row = A.g_row + (size_t)ps * A.S;
     const int S = sd.seq_len, block_len = sd.len1, num_del = sd.num_del;
     const int max_del = -period * num_del;
+    // An EMPTY block's row is the row before it (HapAligner.cpp:72-73: matrix_index == prev_row_index) and the reference fills it in
+    // place, left to right: an insertion's pre_prob (:90, base_len > 0) is the BLOCK row's value base_len positions back.  Then the
+    // row is a recurrence over the read positions: the terms without pre_prob in parallel, the row itself by one thread.
+    const bool in_place = block_len == 0;
     __syncthreads();                                           // (the previous (pair, side)'s readers are done with the LDS arrays)
     for (int j = tid; j < S; j += kShortThreads) { s_seq[j] = sd.seq[j]; s_cor[j] = sd.correct[j]; s_wr[j] = sd.wrong[j]; s_prev[j] = g_row[j]; }
     {
@@ -625,12 +632,35 @@ __global__ __launch_bounds__(kShortThreads) __attribute__((amdgpu_waves_per_eu(8
             prob = mx + d_fasterlog((float)total);
           }
           const double pre_prob = (j - base_len < 0 ? 0 : s_prev[j - base_len]);
-          term = art[ai] + prob + pre_prob;                    // :91
+          term = in_place && base_len > 0 ? art[ai] + prob : art[ai] + prob + pre_prob;       // :91 (in place: pre_prob joins below)
         }
       }
       terms[item] = term;
     }
     __syncthreads();                                           // (workgroup scope: orders the global stores above, too)
+    if (in_place) {
+      if (tid == 0) {
+        for (int j = 0; j < S; ++j) {
+          double bp[kNumArt];
+#pragma unroll
+          for (int a = 0; a < kNumArt; ++a) {
+            const int base_len = min((a - kMaxDel) * period, j + 1);
+            bp[a] = terms[(size_t)a * S + j];
+            if (base_len > 0) bp[a] += (j - base_len < 0 ? 0 : s_prev[j - base_len]);       // (positions before j: already the block's row)
+          }
+          double mx = bp[0];
+#pragma unroll
+          for (int a = 1; a < kNumArt; ++a) if (mx < bp[a]) mx = bp[a];
+          double total = 0;
+#pragma unroll
+          for (int a = 0; a < kNumArt; ++a) { const double diff = bp[a] - mx; if (diff > A.log_thresh) total += d_fasterexp((float)diff); }
+          const double v = mx + d_fasterlog((float)total);
+          s_prev[j] = v; g_row[j] = v;
+          if (j == S - 1) A.g_last[(size_t)ps * (A.HS + 2) + (sd.len0 - 1)] = v;                // last[stutter_R], stutter_R = len0 - 1
+        }
+      }
+      continue;                                                // (the loop's first __syncthreads separates s_prev's next writers)
+    }
     for (int j = tid; j < S; j += kShortThreads) {             // fast_log_sum_exp(block_probs), :103
       double mx = terms[j];
 #pragma unroll

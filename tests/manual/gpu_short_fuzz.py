@@ -1,6 +1,8 @@
 """Manual GPU check: differential fuzz of the seeded stutter path (a-7).  Random period-1 loci -- repeat lengths 1 .. 90,
 2 .. 6 alleles, 1 .. 40 raw reads with error rates up to 8 %, random and extreme base qualities, reads without a seed,
-random realign masks, random stutter models, several loci per call -- scored by ltr_calc_hap_aln_probs (all loci of a batch
+random realign masks, random stutter models, several loci per call; about a third of the reads are crafted (short_util.crafted_read
+on the locus' own blocks: seed in either flank, sides from 4 to past 512 bases, reads that start or end inside a flank or inside
+the repeat) -- scored by ltr_calc_hap_aln_probs (all loci of a batch
 in one set of launches) and by ltr_process_reads (one locus per call); both must equal the CPU restatement bit for bit.
     python tests/manual/gpu_short_fuzz.py [seconds] [seed]"""
 import os, sys, time
@@ -8,6 +10,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import oracle_lib as ol
+import short_util as su
 from longtr_amd import _abi, _lib, synth
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
@@ -28,7 +31,15 @@ while time.time() - t0 < budget:
         tr = int(rng.choice([rng.integers(1, 10), rng.integers(10, 40), rng.integers(40, 91)]))
         err = float(rng.choice([0.0, 0.002, 0.02, 0.08]))
         blocks, alns = synth.homopolymer_locus(rng, tr, int(rng.integers(2, 7)), int(rng.integers(1, 41)), sub_rate=err, indel_rate=err / 2)
+        lf_len, rf_len, n_al = len(blocks[0]["alleles"][0]), len(blocks[2]["alleles"][0]), len(blocks[1]["alleles"])
+        big = rng.random() < 0.1                                  # one locus in ten: sides past 512 -> the whole call on the lane-per-pair kernel
         for i in range(len(alns)):
+            if rng.random() < 1 / 3:                              # a crafted read: the side lengths and ends homopolymer_locus never draws
+                side = int(rng.choice([4, 17, 63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 512, 513, 700] if big else [4, 17, 63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 512]))
+                hap_len = lf_len + len(blocks[1]["alleles"][0]) + rf_len
+                far = int(rng.integers(-(hap_len - 12), 20))      # the other end: anywhere from deep inside the haplotype to 20 bases past it
+                if rng.random() < 0.5: alns[i] = su.crafted_read(blocks, int(rng.integers(n_al)), su.left_pad_for(lf_len, side), max(far, -(len(blocks[1]["alleles"][0]) + rf_len - 1)), "left", rng)
+                else: alns[i] = su.crafted_read(blocks, int(rng.integers(n_al)), max(far, -(lf_len + len(blocks[1]["alleles"][0]) - 1)), su.right_pad_for(rf_len, side), "right", rng)
             u = rng.random()
             q = np.frombuffer(alns[i]["qual"], dtype=np.uint8).copy()
             if u < 0.05: alns[i] = dict(alns[i], cigar=[("X", len(alns[i]["seq"]))])          # no seed: an all-zero row

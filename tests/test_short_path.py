@@ -112,6 +112,21 @@ def test_stutter_pieces_live_against_the_reference_build():
         a, _, _ = ol.stutter_block_row("oracle", sp, block, period, it % 2, seq, qual, prev)
         b, _, _ = ol.stutter_block_row("ref", sp, block, period, it % 2, seq, qual, prev)
         assert np.array_equal(_bits(a), _bits(b)), (block, seq)
+    # the row at the lengths where ltr_short.hip's geometry changes (tests/test_gpu_short_geometry.py): read sides around the
+    # strip widths and the 512 switch, blocks that are empty, shorter than MAX_STUTTER_REPEAT_DEL, and longer than most sides
+    n = 0
+    for seq_len in (4, 127, 128, 129, 255, 256, 257, 511, 512, 513):
+        for block_len in (0, 1, 2, 5, 6, 7, 300):
+            block = b"A" * block_len
+            seq = bytes(int(x) for x in rng.choice(list(b"AAAAAAC"), size=seq_len))
+            qual = bytes(int(q) for q in rng.integers(30, 80, size=seq_len))
+            prev = np.cumsum(-rng.random(seq_len))
+            for left_align in (0, 1):
+                a, _, _ = ol.stutter_block_row("oracle", sp, block, 1, left_align, seq, qual, prev)
+                b, _, _ = ol.stutter_block_row("ref", sp, block, 1, left_align, seq, qual, prev)
+                assert np.array_equal(_bits(a), _bits(b)), (seq_len, block_len, left_align)
+                n += 1
+    assert n == 140
 
 
 # ---- the outer functions that link against the compiled reference: compute_aln_logprob (HapAligner.cpp:165-233),
