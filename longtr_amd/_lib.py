@@ -693,6 +693,43 @@ def debug_threshold_groups(class_first, merge=True, keep_waves=False):
     return nw, w, npairs
 
 
+LAUNCH_KINDS = ("one-wave", "packed", "multi", "packed-multi", "plan", "workgroup")      # ltrp::LaunchKind
+
+
+def debug_plan_schedule(batch, grids, params=None, mode=-1, n_cu=256, plan_kernel=0, no_multi=0, chain=0, chain_min_w=0, chain_max_w=0,
+                        plan_share=0, cap=0):
+    """Test hook ltr_debug_plan_schedule (csrc/ltr_plan.h): describe_batch, class statistics and ltrp::build_schedule on a
+    _abi.PackedBatch, no GPU.  grids: made-up occupancy grids, one per class (certificate, then exact), then of the multi-width
+    one-wave launch, the multi-width packed launch and the plan kernel.  dict(launches, by_class: lists of dict(kind, cls, W,
+    grid, small, cmax, pairs, cells, members); entries: list of dict(kind, W, first, pairs, queue_class, first_wave); n_tabs,
+    use_plan, max_grid, max_grid_wide, max_len, xcand, class_first, x_grid)."""
+    L = lib()
+    L.ltr_debug_plan_schedule.argtypes = [C.POINTER(_abi.AlignParams), C.c_int, C.c_int, C.POINTER(_abi.LocusBatch), C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    nk = L.ltr_debug_num_classes()
+    g = np.ascontiguousarray(grids, dtype=np.int32)
+    assert g.size == nk + 3
+    knobs = np.asarray([plan_kernel, no_multi, chain, chain_min_w, chain_max_w, plan_share, cap], dtype=np.int32)
+    prm = params or _abi.default_params()
+    n_exact = nk - sum(1 for k in range(nk) if L.ltr_kernel_family(k) != 3)
+    out, x_grid = np.zeros(8 + n_exact + nk + 1, dtype=np.int64), np.zeros(n_exact, dtype=np.int32)
+    lcap, mcap, ecap = 2 * nk, 2 * nk + 128, 256
+    launch, cells, members, entry = np.zeros((lcap, 8), np.int32), np.zeros(lcap), np.zeros(mcap, np.int32), np.zeros((ecap, 6), np.int32)
+    rc = L.ltr_debug_plan_schedule(C.byref(prm), int(mode), int(n_cu), C.byref(batch.struct), _p(g), _p(knobs), _p(out), _p(x_grid),
+                                   lcap, _p(launch), _p(cells), mcap, _p(members), ecap, _p(entry))
+    if rc != 0:
+        raise LtrError(rc, "ltr_debug_plan_schedule")
+    rows, at = [], 0
+    for i in range(int(out[0] + out[1])):
+        kind, cls, w, grid, small, cmax, pairs, nm = (int(v) for v in launch[i])
+        rows.append(dict(kind=LAUNCH_KINDS[kind], cls=cls, W=w, grid=grid, small=bool(small), cmax=cmax, pairs=pairs, cells=float(cells[i]),
+                         members=[int(m) for m in members[at:at + nm]]))
+        at += nm
+    ents = [dict(zip(("kind", "W", "first", "pairs", "queue_class", "first_wave"), (int(v) for v in entry[i]))) for i in range(int(out[2]))]
+    return dict(launches=rows[:int(out[0])], by_class=rows[int(out[0]):], entries=ents, n_tabs=int(out[3]), use_plan=bool(out[4]),
+                max_grid=int(out[5]), max_grid_wide=int(out[6]), max_len=int(out[7]), xcand=out[8:8 + n_exact].copy(), class_first=out[8 + n_exact:].copy(), x_grid=x_grid)
+
+
 def tbi_parse(tbi_path, max_refs=4096):
     """Test hook ltr_debug_tbi_parse: dict(format, col_seq, col_beg, col_end, meta, skip, names, bins, chunks) or LtrError."""
     L = lib()

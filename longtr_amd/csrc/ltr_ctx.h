@@ -115,10 +115,8 @@ struct ltr_plan : ltrp::BatchPlan {     // (what ltrp::describe_batch decided: s
   uint32_t* d_queue = nullptr;          // one counter per bin
   double* d_scratch = nullptr;
   int32_t scratch_stride = 0;
-  int bin_grid[ltrp::kNumFast] = {0};
-  bool bin_small[ltrp::kNumFast] = {false};     // the class cannot fill the GPU's wave slots once
-  int max_grid = 0;
-  int max_grid_wide = 1;                // grid of the W = 20 exact launch (candidates of the 4-wave list)
+  ltrp::ClassStats stats;               // nominal cells and longest read of every class
+  ltrp::Schedule sched;                 // the launches of an execute, their order and grids; the plan kernel's table (ltrp::build_schedule)
   double* last_out = nullptr;
   hipStream_t last_stream = nullptr;
   std::vector<hipStream_t> streams;     // every stream an execute of this plan was queued on (synchronised before its buffers are released)
@@ -129,33 +127,10 @@ struct ltr_plan : ltrp::BatchPlan {     // (what ltrp::describe_batch decided: s
   hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
   hipEvent_t ev_fast = nullptr, ev_x[kNumExact + 1] = {nullptr};   // exact launches side by side: after the certificate launches / joined back (+ 1: the W = 20 launch)
   hipEvent_t ev_close[kNumExact][4] = {{nullptr}};   // "every certificate launch that can feed exact list c has been queued", one per launch stream
-  std::vector<int> order;               // certificate classes with pairs, longest reads first: the launch order
-  int order_pos[ltrp::kNumKernels] = {0};     // position of every class in it (-1: empty class); exact class c: order.size() + c
-  int32_t cls_cmax[ltrp::kNumFast] = {0};     // longest read (columns, m - 1) of every certificate class
-  // the one-wave classes of strip widths kMultiMinW .. kWMax as ONE persistent launch (ltr_dp_multi_kernel), listed under
-  // the widest of them: multi_rep (-1: no such launch), its classes widest first in multi_classes
-  int multi_rep = -1, multi_grid = 0;
-  bool multi_small = false;
-  std::vector<int> multi_classes;
-  // ... and the packed launches of strip widths kPackMultiMinW .. kPackWMax (ltr_dp_pack_multi_kernel), listed under the
-  // representative class of the widest of them: pmulti_rep (-1: none), the representatives of its widths widest first
-  int pmulti_rep = -1, pmulti_grid = 0;
-  bool pmulti_small = false;
-  std::vector<int> pmulti_reps;
-  PackTable* d_pk_tabs = nullptr;
-  // the PLAN KERNEL (ltr_dp_plan.hpp): every one-wave class and every packed strip width of the plan in ONE persistent launch,
-  // listed under plan_rep (-1: a launch per class / the multi-width launches); its entries longest pairs first
-  int plan_rep = -1, plan_grid = 0;
-  bool plan_small = false;
-  std::vector<PlanEntry> plan_entries;
-  PlanEntry* d_pl_entries = nullptr;
+  PackTable* d_pk_tabs = nullptr;       // sched.pack_tabs
+  PlanEntry* d_pl_entries = nullptr;    // sched.plan_entries
   unsigned long long* d_wave_clock = nullptr;   // (debug) two wall-clock words per wavefront of the plan kernel
-  std::vector<int> order2;              // the launch order with those launches split into their classes again (ltr_plan_set_timing level 2)
-  int order_pos2[ltrp::kNumKernels] = {0};
-  int pack_rep[ltrp::kNumPack] = {0};         // packed class j: the class its launch is listed under (one launch per strip width), -1 = no pairs
   hipEvent_t bin_ev[ltrp::kNumKernels + 1] = {nullptr};   // bracket every DP launch on the launch stream
-  double bin_cells[ltrp::kNumFast] = {0};
-  double x_cells[kNumExact] = {0};      // nominal cells of the pairs pre-seeded into every exact list
   uint32_t* d_ctrl_init = nullptr;      // image of the control words (queues = 0, redo count = n_generic)
   int32_t* d_redo_init = nullptr;       // indices of the generic pairs: copied over the head of the redo list every execute
   bool last_wg_thr = false;             // ... and the last execute scored them with the threshold kernels first
@@ -164,12 +139,10 @@ struct ltr_plan : ltrp::BatchPlan {     // (what ltrp::describe_batch decided: s
   double* h_ll = nullptr; size_t h_ll_cap = 0;
   bool ctrl_fresh = false;              // the control words arrived with the upload: the first execute skips their reset
   int timed = 0;                        // the last execute recorded per-launch events (level)
-  int timing = 0;                       // record a HIP event around every launch (ltr_plan_set_timing): 1 = as launched, 2 = the multi-width launch class by class
+  int timing = 0;                       // record a HIP event around every launch (ltr_plan_set_timing): 1 = as launched, 2 = the multi-width launches class by class
   int32_t* d_redo_list = nullptr;       // kNumExact lists (capacity n_pairs each): pairs the certificate kernels handed to the exact kernels
   uint32_t* d_redo_count = nullptr;     // their lengths (control words)
   int64_t redo_cap = 1;
-  int redo_grid = 0;
-  int x_grid[kNumExact] = {0};          // launch grid of every exact kernel; 0 = no pair of this plan can land in its list
   uint32_t seed_total = 0;
   int last_launches = 0;
   bool executed = false;

@@ -1,7 +1,8 @@
 // ltr_plan.h -- host-side planning of a batch (no HIP in here): the table of launch classes, the rule that
 // gives every (read, haplotype) pair its class and launch-order key, and the sort that lays the pairs out
 // class by class, longest first, and describe_batch, the host half of ltr_plan_create that strings them together
-// (ltr_plan_build.hip adds the uploads); tests/test_plan_units.py exercises them on the CPU through the ltr_debug_* entry points.
+// and build_schedule, which turns the description into the list of launches (ltr_plan_build.hip adds the grid query and the
+// uploads, ltr_plan_run.hip walks the list); tests/test_plan_units.py exercises them on the CPU through the ltr_debug_* entry points.
 #ifndef LTR_PLAN_H_
 #define LTR_PLAN_H_
 
@@ -210,6 +211,56 @@ struct __attribute__((visibility("hidden"))) BatchPlan {
 int describe_batch(const ltr_locus_batch* b, const ModelConsts& mc, int indel_flank_len, int mode, int n_cu, const ltr::DebugKnobs& dbg,
                    const BatchScratch& w, BatchPlan* d, std::string* err) __attribute__((visibility("hidden")));
 
+// Nominal cells and longest read (columns, m - 1) of every certificate class, nominal cells of the pairs that start out in every
+// exact list: one pass over the sorted pairs (w.sorted, w.order, w.key as describe_batch left them).
+struct ClassStats { double bin_cells[kNumFast] = {0}; int32_t cls_cmax[kNumFast] = {0}; double x_cells[kNumExact] = {0}; };
+void class_stats(const BatchPlan& d, const BatchScratch& w, ClassStats* st) __attribute__((visibility("hidden")));
+
+// ---- the launch schedule of a plan ------------------------------------------------------------------------------------------
+// One first-pass launch.  Launches that take several classes -- a packed launch takes every lanes-per-pair class of its strip
+// width; the multi-width launches and the plan kernel take whole families -- use the queue word, the statistics slot and the
+// pair range of ONE of their classes, cls: the widest that has pairs.
+enum LaunchKind { kLaunchOne = 0, kLaunchPack, kLaunchMulti, kLaunchPackMulti, kLaunchPlan, kLaunchWg };
+struct Launch {
+  int kind = kLaunchOne;
+  int cls = 0;                 // the class it is launched, timed and reported under
+  int W = 0;                   // strip width (kLaunchOne, kLaunchPack, kLaunchWg)
+  int grid = 1;                // persistent grid
+  bool small = false;          // cannot fill the GPU's wave slots once
+  int32_t cmax = 0;            // longest read (columns) of any member: the launch order, and when the exact lists close
+  int64_t pairs = 0;
+  double cells = 0.0;          // nominal
+  // member classes, widest first: n_one one-wave classes, then n_pack packed widths as the widest lanes-per-pair class of each
+  // that has pairs (what a single-width packed launch is listed under)
+  int n_one = 0, n_pack = 0;
+  int16_t members[kNumBins + kPackWMax] = {0};
+};
+// Resident workgroups (occupancy x CUs) of every launch the schedule sizes: the context asks the runtime once.
+struct OccupancyGrids { int cls[kNumFast] = {0}; int multi = 0, pack_multi = 0, plan = 0; int exact[kNumExact] = {0}; };
+struct __attribute__((visibility("hidden"))) Schedule {
+  std::vector<Launch> launches;          // in launch order: longest cmax first, ties in descending class order
+  std::vector<Launch> by_class;          // ... with the multi-width launches class by class again (ltr_plan_set_timing level 2)
+  std::vector<PlanEntry> plan_entries;   // the plan kernel's table in walk order, with the wavefronts' starting shares
+  std::vector<PackTable> pack_tabs;      // range tables of the packed widths of a kLaunchPackMulti / kLaunchPlan launch, widest first
+  int x_grid[kNumExact] = {0};           // launch grid of every exact kernel; 0 = no pair of this plan can land in its list
+  int max_grid = 1;                      // largest grid of a launch that parks column blocks in scratch strips
+  int max_grid_wide = 1;                 // grid of the W = 20 exact launch (candidates of the 4-wave list)
+  const Launch* plan_launch() const { for (const Launch& L : launches) if (L.kind == kLaunchPlan) return &L; return nullptr; }
+  // the launches at a timing level (the plan kernel is never split: its classes score their failed certificates in line, and
+  // no exact launch is sized for what a single-class kernel would queue)
+  const std::vector<Launch>& at_level(int level) const { return (level >= 2 && !plan_launch()) ? by_class : launches; }
+  // position in such a list of the launch that is listed under class k, or -1 (no pairs; a member of another class's launch)
+  static int find(const std::vector<Launch>& list, int k);
+  // (lanes per pair, strip width, pairs) of every class a launch over several classes takes, in launch order; 0 for the others
+  int ranges(const Launch& L, const int* bin_first, int32_t* lanes_per_pair, int32_t* strip_width, int64_t* n_pairs) const;
+  // scratch strips are finite: no launch that uses them (one-wave bodies) gets more than cap workgroups
+  void cap_grids(int cap);
+};
+// The schedule of a described batch.  Pure: class ranges and statistics, occupancy grids and A/B knobs (chain*, plan_share) in.
+// Settles in *d what depends on it: without anything for the plan kernel to score use_plan falls back and the exact launches
+// take the list starters (xcand); with it the plan kernel scores them itself (x_seed = 0).
+void build_schedule(BatchPlan* d, const ClassStats& st, const OccupancyGrids& occ, const ltr::DebugKnobs& dbg, Schedule* out) __attribute__((visibility("hidden")));
+
 // ---- pure pieces of ltr_plan_execute --------------------------------------------------------------------------------------
 // Threshold first pass of the workgroup classes: which kernel scores a class (nw waves, strips of w columns; nw 0 = not a
 // workgroup class with pairs) and how many pairs the launch it leads takes (np 0: led by a class before it).
@@ -235,7 +286,18 @@ void build_threshold_table(float c, double* out);
 // out_f64[0..1] = cells, input bytes, class_first[ltr_debug_num_classes() + 1], per sorted pair its descriptor fields
 // (n, m, out_idx) and key; the reason of an LTR_ERR_INVALID goes to err[err_cap].
 // ltr_debug_threshold_groups: ltrp::threshold_groups; nw / w / np hold ltr_debug_num_classes() entries each.
+// ltr_debug_plan_schedule: describe_batch, class_stats and build_schedule.  grids[ltr_debug_num_classes() + 3]: the occupancy grid of
+// every certificate class, of the exact kernels, then of the multi-width one-wave launch, the multi-width packed launch and the plan
+// kernel.  knobs[7] = plan_kernel, no_multi, chain, chain_min_w, chain_max_w, plan_share, grid cap (0: none).  Per launch 8 words
+// in launch[launch_cap][8] = kind, class, strip width, grid, small, cmax, pairs, members and its cells in launch_cells[]; the
+// members of all launches one after the other in members[member_cap]; per entry 6 words in entry[entry_cap][6] = kind, strip
+// width, first pair, pairs, queue class, first_wave.  out[8 + kNumExact] = launches, level-2 launches (listed behind the first),
+// entries, pack tables, use_plan, max_grid, max_grid_wide, max_len, then xcand[kNumExact], then class_first[ltr_debug_num_classes() + 1];
+// x_grid[kNumExact].
 extern "C" {
+int ltr_debug_plan_schedule(const ltr_align_params* p, int mode, int n_cu, const ltr_locus_batch* b, const int32_t* grids, const int32_t* knobs,
+                            int64_t* out, int32_t* x_grid, int launch_cap, int32_t* launch, double* launch_cells, int member_cap, int32_t* members,
+                            int entry_cap, int32_t* entry);
 int ltr_debug_describe_batch(const ltr_align_params* p, int mode, int n_cu, const ltr_locus_batch* b, int64_t* out_i64, double* out_f64,
                              int32_t* class_first, int64_t pair_cap, int32_t* pair_n, int32_t* pair_m, int64_t* pair_out_idx, int16_t* pair_key,
                              char* err, int err_cap);

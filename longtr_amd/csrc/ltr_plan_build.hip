@@ -1,6 +1,6 @@
 // ltr_plan_build.hip -- ltr_plan_create / ltr_plan_destroy: what ltrp::describe_batch (ltr_plan.cpp) decided about a batch
-// becomes a plan on the device -- class statistics, launch order, grid sizes, the upload (one block for a compact plan, separate
-// buffers otherwise), scratch strips and events.  Running a plan: ltr_plan_run.hip.
+// becomes a plan on the device -- the grid query, the launch schedule (ltrp::build_schedule), the upload (one block for a compact
+// plan, separate buffers otherwise), scratch strips and events.  Running a plan: ltr_plan_run.hip.
 
 #include <cmath>
 #include <cstring>
@@ -73,110 +73,7 @@ static void destroy_plan(ltr_plan* plan, const bool ctx_locked) {
   delete plan;
 }
 
-// ---- units of ltr_plan_create (host side; the class rule and the sort live in ltr_plan.cpp) ----------------------------
-
-// Nominal cells and longest read of every class: blocks of the sorted pairs on the host cores (a block spans a few
-// classes; a class's pairs are one contiguous range), partial sums merged in block order.
-static void plan_class_stats(ltr_plan* plan, const RawBuf<PairDesc>& sorted, const RawBuf<int32_t>& order, const RawBuf<int16_t>& key) {
-  {
-    const size_t np = sorted.size();
-    const int64_t n_blk = (int64_t)((np + kPlanBlock - 1) / kPlanBlock);
-    struct Part { int k0 = 0, k1 = -1; std::vector<double> cl; std::vector<int32_t> cm; };
-    std::vector<Part> parts((size_t)n_blk);
-    auto class_of = [&](size_t i) { int k = 0; while (plan->bin_first[k + 1] <= (int)i) ++k; return k; };
-    ltr::parallel_for(n_blk, np < 20000 ? n_blk + 1 : 1, [&](int64_t c) {                         // (a one-locus plan: not worth waking the worker pool)
-      const size_t i0 = (size_t)c * kPlanBlock, i1 = std::min(np, i0 + kPlanBlock);
-      Part& P = parts[(size_t)c];
-      int k = class_of(i0);
-      P.k0 = k; P.k1 = k;
-      double cl = 0.0; int32_t cm = 0;
-      for (size_t i = i0; i < i1; ++i) {
-        while (plan->bin_first[k + 1] <= (int)i) { P.cl.push_back(cl); P.cm.push_back(cm); cl = 0.0; cm = 0; ++k; P.k1 = k; }
-        if (key[(size_t)order[i]] > 0) cl += (double)sorted[i].n * (double)sorted[i].m;
-        cm = std::max(cm, sorted[i].m - 1);
-      }
-      P.cl.push_back(cl); P.cm.push_back(cm);
-    }, 1);
-    for (int k = 0; k < kNumFast; ++k) { plan->bin_cells[k] = 0.0; plan->cls_cmax[k] = 0; }
-    for (int c = 0; c < kNumExact; ++c) plan->x_cells[c] = 0.0;
-    for (const Part& P : parts)
-      for (int k = P.k0; k <= P.k1 && np > 0; ++k) {
-        const double cl = P.cl[(size_t)(k - P.k0)];
-        if (k < kNumFast) { plan->bin_cells[k] += cl; plan->cls_cmax[k] = std::max(plan->cls_cmax[k], P.cm[(size_t)(k - P.k0)]); }
-        else if (k < kNumKernels) plan->x_cells[k - kNumFast] += cl;
-      }
-  }
-}
-
-// Launch order of the certificate classes and which of them share a launch (packed: one launch per strip width; automatic
-// mode, large plans: the multi-width launches).  Pure function of plan->bin_first / cls_cmax.
-static void plan_launch_order(ltr_plan* plan, const bool use_multi) {
-  // launch order of the certificate classes: longest reads first (the classes that can feed the exact lists of long reads
-  // are through early, and those lists' launches -- a handful of pairs, each as long as its longest pair -- run beside
-  // the remaining certificate launches instead of behind the last one)
-  // (the packed classes of one strip width -- 32, 16, 8, 4, 2 lanes per pair -- are ONE launch, ltr_dp_pack.hpp: it is listed
-  // under the first of them that has pairs, its representative, and is as long as the longest read of any of them)
-  for (int k = kPackFirst; k < kWg4First; ++k) plan->pack_rep[k - kPackFirst] = -1;
-  for (int w = 1; w <= kPackWMax; ++w) {
-    int rep = -1, cm = 0;
-    for (int sft = kPackMaxShift; sft >= kPackMinShift; --sft) {
-      const int k = ltrp::pack_class(sft, w);
-      if (plan->bin_first[k + 1] <= plan->bin_first[k]) continue;
-      if (rep < 0) rep = k;
-      cm = std::max(cm, plan->cls_cmax[k]);
-    }
-    if (rep < 0) continue;
-    for (int sft = kPackMaxShift; sft >= kPackMinShift; --sft) {
-      const int k = ltrp::pack_class(sft, w);
-      if (plan->bin_first[k + 1] > plan->bin_first[k]) plan->pack_rep[k - kPackFirst] = rep;
-    }
-    plan->cls_cmax[rep] = cm;
-  }
-  // (... and in automatic mode the one-wave classes of strip widths kMultiMinW .. kWMax are ONE launch too,
-  // ltr_dp_multi_kernel: listed under the widest of them that has pairs)
-  // (... or, under the plan kernel, EVERY one-wave class and every packed width: one launch, listed under plan_rep)
-  const bool use_plan = plan->use_plan;
-  if (use_multi || use_plan) {
-    for (int k = kNumBins - 1; k >= (use_plan ? 0 : kMultiMinW - 1); --k) if (plan->bin_first[k + 1] > plan->bin_first[k]) plan->multi_classes.push_back(k);
-    if (plan->multi_classes.size() >= (use_plan ? 1u : 2u)) plan->multi_rep = plan->multi_classes[0]; else plan->multi_classes.clear();
-  }
-  int32_t multi_cmax = 0, pmulti_cmax = 0;
-  for (int k : plan->multi_classes) multi_cmax = std::max(multi_cmax, plan->cls_cmax[k]);
-  if (use_multi || use_plan) {
-    for (int w = kPackWMax; w >= (use_plan ? 1 : kPackMultiMinW); --w) {
-      int r2 = -1;
-      for (int sft = kPackMaxShift; sft >= kPackMinShift && r2 < 0; --sft) r2 = plan->pack_rep[ltrp::pack_class(sft, w) - kPackFirst];
-      if (r2 >= 0) plan->pmulti_reps.push_back(r2);
-    }
-    if (plan->pmulti_reps.size() >= (use_plan ? 1u : 2u)) plan->pmulti_rep = plan->pmulti_reps[0]; else plan->pmulti_reps.clear();
-  }
-  for (int k : plan->pmulti_reps) pmulti_cmax = std::max(pmulti_cmax, plan->cls_cmax[k]);
-  if (use_plan) plan->plan_rep = plan->multi_rep >= 0 ? plan->multi_rep : plan->pmulti_rep;
-  auto in_multi = [&](int k) {
-    if (use_plan) return k < kWg4First;
-    if (plan->multi_rep >= 0 && k < kNumBins && k >= kMultiMinW - 1) return true;
-    return plan->pmulti_rep >= 0 && k >= kPackFirst && k < kWg4First && class_info(k).W >= kPackMultiMinW;
-  };
-  for (int k = kNumFast - 1; k >= 0; --k) {
-    if (plan->bin_first[k + 1] <= plan->bin_first[k]) continue;
-    if (k >= kPackFirst && k < kWg4First && plan->pack_rep[k - kPackFirst] != k) continue;
-    plan->order2.push_back(k);
-    if (use_plan ? (in_multi(k) && k != plan->plan_rep) : (in_multi(k) && k != plan->multi_rep && k != plan->pmulti_rep)) continue;
-    plan->order.push_back(k);
-  }
-  std::stable_sort(plan->order2.begin(), plan->order2.end(), [&](int x, int y) { return plan->cls_cmax[x] > plan->cls_cmax[y]; });
-  for (int k = 0; k < kNumKernels; ++k) plan->order_pos2[k] = -1;
-  for (size_t i = 0; i < plan->order2.size(); ++i) plan->order_pos2[plan->order2[i]] = (int)i;
-  for (int c = 0; c < kNumExact; ++c) plan->order_pos2[kNumFast + c] = (int)plan->order2.size() + c;
-  if (plan->multi_rep >= 0) plan->cls_cmax[plan->multi_rep] = multi_cmax;       // (>= its own: the exact lists close no earlier for it)
-  if (plan->pmulti_rep >= 0) plan->cls_cmax[plan->pmulti_rep] = pmulti_cmax;
-  if (plan->plan_rep >= 0) plan->cls_cmax[plan->plan_rep] = std::max(multi_cmax, pmulti_cmax);
-  std::stable_sort(plan->order.begin(), plan->order.end(), [&](int x, int y) { return plan->cls_cmax[x] > plan->cls_cmax[y]; });
-  for (int k = 0; k < kNumKernels; ++k) plan->order_pos[k] = -1;
-  for (size_t i = 0; i < plan->order.size(); ++i) plan->order_pos[plan->order[i]] = (int)i;
-  for (int c = 0; c < kNumExact; ++c) plan->order_pos[kNumFast + c] = (int)plan->order.size() + c;
-
-}
+// ---- units of ltr_plan_create (the class rule, the sort, the class statistics and the launch schedule live in ltr_plan.cpp) ----
 
 #define GRID_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return e_; } while (0)
 // Resident workgroups of every launch class (occupancy x CUs), asked from the runtime once per context.
@@ -218,143 +115,6 @@ static hipError_t ctx_query_grids(ltr_ctx* ctx) {
 }
 #undef GRID_TRY
 
-// Persistent grid of every launch of the plan, "small" flags (a launch that cannot fill the GPU's wave slots once), the range
-// tables of the multi-width packed launch (uploaded by the caller).  plan->counts: pairs per class after folding; plan->xcand:
-// pairs that could end up in each exact list.
-static void plan_size_grids(ltr_ctx* ctx, ltr_plan* plan, std::vector<PackTable>* pack_tabs) {
-  const int* counts = plan->counts;
-  const int64_t* xcand = plan->xcand;
-  const int* g = ctx->full_grid;
-  plan->redo_grid = ctx->full_redo_grid;
-  for (int k = 0; k < kNumFast; ++k) {
-    const ClassInfo ci = class_info(k);
-    if (ci.family == kFamWg) {                                                // one pair per workgroup, no scratch strips
-      plan->bin_grid[k] = std::min(g[k], std::max(counts[k], 1));
-      plan->bin_small[k] = counts[k] < g[k];
-      continue;
-    }
-    int waves = counts[k];
-    if (k == plan->multi_rep) {
-      // the multi-width launch takes every class of its group; its grid is kept next to the class's own (level-2 timing launches the classes one by one)
-      int all = 0;
-      for (int k2 : plan->multi_classes) all += counts[k2];
-      plan->multi_grid = std::min(ctx->full_multi_grid, std::max((all + kBlockWaves - 1) / kBlockWaves, 1));
-      plan->multi_small = (all + kBlockWaves - 1) / kBlockWaves < ctx->full_multi_grid;
-      plan->max_grid = std::max(plan->max_grid, plan->multi_grid);
-    }
-    if (ci.family == kFamPack) {
-      // a packed wave takes 64 / LP pairs; the launch (listed under its representative) takes every lanes-per-pair block of the width
-      waves = 0;
-      if (plan->pack_rep[k - kPackFirst] == k)
-        for (int sft = kPackMinShift; sft <= kPackMaxShift; ++sft) { const int per = 64 >> sft; waves += (counts[ltrp::pack_class(sft, ci.W)] + per - 1) / per; }
-    }
-    plan->bin_grid[k] = std::min(g[k], std::max((waves + kBlockWaves - 1) / kBlockWaves, 1));
-    plan->bin_small[k] = (waves + kBlockWaves - 1) / kBlockWaves < g[k];
-    if (ci.family == kFamOne) plan->max_grid = std::max(plan->max_grid, plan->bin_grid[k]);
-  }
-  if (plan->pmulti_rep >= 0) {
-    // the multi-width packed launch: one table per strip width (its ranges as the single-width launch would get them), widest first
-    std::vector<PackTable>& tabs = *pack_tabs;
-    tabs.clear();
-    int groups_all = 0;
-    for (int rep : plan->pmulti_reps) {
-      PackTable T;
-      std::memset(&T, 0, sizeof(T));
-      T.W = class_info(rep).W; T.queue_class = rep;
-      ltrp::pack_ranges(plan->bin_first, T.W, T.shift, T.first, T.end, T.grp_end);
-      groups_all += T.grp_end[4];
-      tabs.push_back(T);
-    }
-    plan->pmulti_grid = std::min(ctx->full_pmulti_grid, std::max((groups_all + kBlockWaves - 1) / kBlockWaves, 1));
-    plan->pmulti_small = (groups_all + kBlockWaves - 1) / kBlockWaves < ctx->full_pmulti_grid;
-  }
-  if (plan->use_plan && plan->plan_rep >= 0) {
-    // The plan kernel's entries: every one-wave class, every packed width (table t of pack_tabs), the entry with the longest
-    // pairs first (modelled steps x strip cost of its longest read); the launch's wavefronts start spread over the entries in
-    // proportion to their modelled work (cells x (1 + per-step overhead / W)) and walk the table from the top afterwards.
-    struct Ent { PlanEntry e; double longest, work; };
-    std::vector<Ent> ents;
-    int waves_all = 0;
-    for (int k : plan->multi_classes) {
-      const int w = class_info(k).W, np = plan->bin_first[k + 1] - plan->bin_first[k];
-      PlanEntry e; std::memset(&e, 0, sizeof(e));
-      e.kind = 0; e.W = w; e.first = plan->bin_first[k]; e.n_pairs = np; e.queue_class = k; e.tab = 0; e.limit = np;
-      // the chained walk (ltr_dp_chain.hpp: no fill and drain of the skew between the pairs of a class; on request) for the strip
-      // widths whose reads fill the wave's scratch strip, where the next pair's first row is parked
-      {
-        const int64_t need = 2 * (int64_t)w * 64 + ((w + 3) / 4) * 32 + 2;
-        const int64_t have = 6 * (int64_t)(((plan->max_len + 2 + 15) / 16) * 16);
-        const int lo = ctx->dbg.chain_min_w > 0 ? ctx->dbg.chain_min_w : kMultiMinW, hi = ctx->dbg.chain_max_w > 0 ? ctx->dbg.chain_max_w : kWMax;
-        if (ctx->dbg.chain > 0 && plan->sym_at_create && w >= std::max(lo, (int)kMultiMinW) && w <= hi && need <= have) e.kind = 3;   // (off by default: measured slower, ltr_dp_chain.hpp)
-      }
-      const int ncb = (plan->cls_cmax[k] + 64 * w - 1) / (64 * w);
-      ents.push_back({e, (double)std::max(ncb, 1) * (plan->cls_cmax[k] + 64.0) * (w + 1.5), plan->bin_cells[k] * (1.0 + 1.5 / w)});
-      waves_all += np;
-    }
-    for (size_t t = 0; t < pack_tabs->size(); ++t) {
-      const PackTable& T = (*pack_tabs)[t];
-      PlanEntry e; std::memset(&e, 0, sizeof(e));
-      e.kind = 1; e.W = T.W; e.queue_class = T.queue_class; e.tab = (int32_t)t; e.limit = T.grp_end[4];
-      double cells = 0.0; int cmax = 0, lp = 2;
-      for (int sft = kPackMinShift; sft <= kPackMaxShift; ++sft) {
-        const int k2 = ltrp::pack_class(sft, T.W);
-        if (plan->bin_first[k2 + 1] > plan->bin_first[k2]) { cells += plan->bin_cells[k2]; lp = 1 << sft; }
-      }
-      cmax = plan->cls_cmax[T.queue_class];
-      ents.push_back({e, (cmax + (double)lp) * (T.W + 1.5), cells * (1.0 + 1.5 / T.W)});
-      waves_all += e.limit;
-    }
-    {
-      // The pairs that START OUT in an exact list -- bytes outside ACGT, length differences no certificate can hold
-      // (Rules::risky_dd_pos / _neg) -- are scored by the plan kernel itself, FIRST: they are the longest jobs of the plan (an exact body of
-      // 1 - 3 ms per pair on one wavefront).  (Measured on MI355X, 1250 loci of config 3: as launches of their own beside the plan
-      // kernel they found no free wave slot before its workgroups left and the pass ended 3 ms after the plan kernel, 34.0 ms; as
-      // its last work they were its tail, 33.8 ms; first, 30.4 ms.)  The exact launches of such a plan only take what the
-      // workgroup classes queue on the device.
-      for (int c = 0; c < kNumExact; ++c) {
-        const int np = plan->bin_first[kNumFast + c + 1] - plan->bin_first[kNumFast + c];
-        plan->x_seed[c] = 0;
-        if (np <= 0) continue;
-        PlanEntry e; std::memset(&e, 0, sizeof(e));
-        e.kind = 2; e.W = (c == kXGeneric) ? 0 : 1; e.first = plan->bin_first[kNumFast + c]; e.n_pairs = np; e.queue_class = ltrp::kStartQueueSlot + c; e.limit = np;   // (a counter of its own: list c's exact launch may run as well, fed by the workgroup classes)
-        ents.push_back({e, 1e30 - c, plan->x_cells[c] * 1.4});
-        waves_all += np;
-      }
-    }
-    std::stable_sort(ents.begin(), ents.end(), [](const Ent& x, const Ent& y) { return x.longest > y.longest; });
-    plan->plan_grid = std::min(ctx->full_plan_grid, std::max((waves_all + kBlockWaves - 1) / kBlockWaves, 1));
-    plan->plan_small = (waves_all + kBlockWaves - 1) / kBlockWaves < ctx->full_plan_grid;
-    plan->max_grid = std::max(plan->max_grid, plan->plan_grid);
-    double total = 0.0, run = 0.0;
-    for (const Ent& x : ents) total += x.work;
-    const double n_waves = (double)plan->plan_grid * kBlockWaves;
-    plan->plan_entries.clear();
-    for (Ent& x : ents) {
-      x.e.first_wave = total > 0.0 ? (int32_t)std::min(n_waves, std::floor(n_waves * run / total)) : 0;
-      run += x.work;
-      plan->plan_entries.push_back(x.e);
-    }
-    if (!plan->plan_entries.empty()) plan->plan_entries[0].first_wave = 0;
-    // (Measured on MI355X, plan kernel with the shares against every wavefront starting at the top of the table
-    // (ltr_ctx_set_debug "plan_share" = 1): shards of config 3 of 625 / 1250 / 2500 / 5000 loci 15.5 - 15.6 against 15.8 - 16.0 ms,
-    // 30.2 against 30.4, 59.4 both, 125.8 against 125.1 - 125.5; shards of the catalogue of 6250 / 12 500 loci 4.57 against 4.99,
-    // 8.09 against 8.54 -- 3072 wavefronts racing down a table of 30 - 40 short entries pop every counter 3072 times.  While
-    // failed certificates still ended the launch (first version) the shares looked worse: 32.28 against 31.68 ms at 1250 loci.)
-    if (ctx->dbg.plan_share == 1) for (size_t i = 1; i < plan->plan_entries.size(); ++i) plan->plan_entries[i].first_wave = 0x7fffffff;
-  }
-  // exact kernels: launched only when some pair of the plan can land in their list
-  for (int c = 0; c < kNumExact; ++c) {
-    if (xcand[c] <= 0) { plan->x_grid[c] = 0; continue; }
-    const bool wgx = (c == kXWg4 || c == kXWg8);
-    const int64_t wgs = wgx ? xcand[c] : (xcand[c] + kBlockWaves - 1) / kBlockWaves;
-    plan->x_grid[c] = (int)std::min<int64_t>(ctx->full_x_grid[c], std::max<int64_t>(wgs, 1));
-    if (!wgx) plan->max_grid = std::max(plan->max_grid, plan->x_grid[c]);      // (the one-wave kernels park column blocks in scratch strips)
-  }
-  plan->redo_grid = plan->x_grid[kXGeneric];
-  plan->max_grid = std::max(plan->max_grid, 1);
-  plan->max_grid_wide = (int)std::max<int64_t>(1, std::min<int64_t>((xcand[kXWg4] + kBlockWaves - 1) / kBlockWaves, 1 << 20));
-}
-
 #define PLAN_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { ltr::set_error(ctx, std::string(#call) + ": " + hipGetErrorString(e_)); return LTR_ERR_HIP; } } while (0)
 
 // One ltr_plan_create, under ctx->mu: the half-built plan, what the device is given besides the batch itself, and the steps that
@@ -369,7 +129,6 @@ struct PlanBuild {
   ltr_plan* plan = nullptr;
   hipEvent_t ev_copied = nullptr;          // the copies out of the caller's arrays / the context's staging (separate upload)
   // host images of the small device arrays
-  std::vector<PackTable> tabs;             // range tables of the multi-width packed launch
   std::vector<uint32_t> ctrl;              // control words (queues = 0, list lengths = the seeds)
   std::vector<int32_t> init;               // the pre-seeded list heads
   bool want_clock = false;
@@ -395,24 +154,17 @@ struct PlanBuild {
   int size_scratch_and_fan();
 };
 
-// The host side: ltrp::describe_batch in the context's work arrays, then class statistics, launch order and the model tables.
+// The host side: ltrp::describe_batch in the context's work arrays, then class statistics and the model tables.
 int PlanBuild::describe() {
   plan = new ltr_plan();
   plan->ctx = ctx;
   plan->n_reads = b->n_reads;
   ltr_ctx::PlanScratch& s = ctx->scratch;
   std::string why;
-  const int rc0 = ltrp::describe_batch(b, ctx->mc, ctx->params.indel_flank_len, ctx->pair_packing, ctx->n_cu, ctx->dbg,
-                                       ltrp::BatchScratch{s.pairs, s.sorted, s.key, s.bin, s.order, s.read_acgt, s.hap_acgt}, plan, &why);
+  const ltrp::BatchScratch w{s.pairs, s.sorted, s.key, s.bin, s.order, s.read_acgt, s.hap_acgt};
+  const int rc0 = ltrp::describe_batch(b, ctx->mc, ctx->params.indel_flank_len, ctx->pair_packing, ctx->n_cu, ctx->dbg, w, plan, &why);
   if (rc0 != LTR_OK) { ltr::set_error(ctx, why); return rc0; }
-  plan_class_stats(plan, s.sorted, s.order, s.key);
-  plan_launch_order(plan, plan->use_multi);
-  if (plan->use_plan && plan->plan_rep < 0) {
-    // nothing for the plan kernel to score (workgroup classes and list starters only): the exact launches take the starters
-    plan->use_plan = false;
-    for (int c = 0; c < kNumExact; ++c) plan->xcand[c] += plan->xstart[c];
-  }
-
+  ltrp::class_stats(*plan, w, &plan->stats);
   LTR_DBG("plan: %zu pairs, max_len %d", s.sorted.size(), plan->max_len);
   const int rc = build_tables(ctx, (int64_t)plan->max_len + 2);
   if (rc != LTR_OK) return rc;
@@ -420,7 +172,7 @@ int PlanBuild::describe() {
   return LTR_OK;
 }
 
-// Sizes of the device arrays, grids, the host images of the small arrays, and where everything sits in a compact plan's block.
+// Sizes of the device arrays, the launch schedule, the host images of the small arrays, and where everything sits in a compact plan's block.
 int PlanBuild::layout() {
   RawBuf<PairDesc>& sorted = ctx->scratch.sorted;
   const int32_t max_len = plan->max_len;
@@ -432,10 +184,19 @@ int PlanBuild::layout() {
   const size_t hap_tail = (size_t)kHapPad + (size_t)max_len + 384;   // (+ the workgroup kernels' 64-row chunks, two ahead)
   hap_buf = (size_t)std::max<int64_t>(hbytes, 1) + kHapPad + hap_tail;
   read_buf = (size_t)std::max<int64_t>(rbytes, 1) + kReadPad;       // (the packed kernels load a lane's strip of bytes unclamped)
-  // persistent grid per launch (occupancy x CUs, asked from the runtime once per context), the tables of the multi-width packed launch,
-  // the images of the control words and of the pre-seeded list heads: everything the device is given besides the batch itself
+  // the launches with their persistent grids (occupancy x CUs, asked from the runtime once per context), the plan kernel's table and
+  // the tables of the packed widths, the images of the control words and of the pre-seeded list heads: everything the device is
+  // given besides the batch itself
   if (!ctx->have_grids) PLAN_TRY(ctx_query_grids(ctx));
-  plan_size_grids(ctx, plan, &tabs);
+  {
+    ltrp::OccupancyGrids occ;
+    std::copy(ctx->full_grid, ctx->full_grid + kNumFast, occ.cls);
+    std::copy(ctx->full_x_grid, ctx->full_x_grid + kNumExact, occ.exact);
+    occ.multi = ctx->full_multi_grid; occ.pack_multi = ctx->full_pmulti_grid; occ.plan = ctx->full_plan_grid;
+    ltrp::build_schedule(plan, plan->stats, occ, ctx->dbg, &plan->sched);
+  }
+  const std::vector<PlanEntry>& entries = plan->sched.plan_entries;
+  const std::vector<PackTable>& tabs = plan->sched.pack_tabs;
   ctrl.assign(kCtrlWords, 0);
   for (int c = 0; c < kNumExact; ++c) ctrl[kRedoCountSlot + c] = (uint32_t)plan->x_seed[c];
   // image of the pre-seeded list heads: the sorted-array indices bin_first[kNumFast] .. n_pairs, in order
@@ -443,10 +204,10 @@ int PlanBuild::layout() {
   init.assign((size_t)std::max(n_seed, 1), 0);
   for (int g2 = 0; g2 < n_seed; ++g2) init[(size_t)g2] = plan->bin_first[kNumFast] + g2;
   plan->redo_cap = (int64_t)std::max<size_t>(sorted.size(), 1);
-  want_clock = !plan->plan_entries.empty() && ctx->dbg.wave_clock > 0;
+  want_clock = !entries.empty() && ctx->dbg.wave_clock > 0;
   auto up256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
   o_queue = 0; o_ctrl = up256(o_queue + kCtrlWords * sizeof(uint32_t)); o_ent = up256(o_ctrl + kCtrlWords * sizeof(uint32_t));
-  o_tabs = up256(o_ent + std::max<size_t>(plan->plan_entries.size(), 1) * sizeof(PlanEntry));
+  o_tabs = up256(o_ent + std::max<size_t>(entries.size(), 1) * sizeof(PlanEntry));
   o_init = up256(o_tabs + std::max<size_t>(tabs.size(), 1) * sizeof(PackTable)); o_pairs = up256(o_init + init.size() * sizeof(int32_t));
   o_reads = up256(o_pairs + std::max<size_t>(sorted.size(), 1) * sizeof(PairDesc)); o_haps = up256(o_reads + read_buf);
   o_codes = up256(o_haps + hap_buf); image_bytes = up256(o_codes + hap_buf * sizeof(uint16_t));
@@ -464,6 +225,8 @@ int PlanBuild::layout() {
 // reach, so ltr_plan_fetch is an event wait and a memcpy.  Same kernels, same launch, same bits.
 int PlanBuild::upload_compact() {
   RawBuf<PairDesc>& sorted = ctx->scratch.sorted;
+  const std::vector<PlanEntry>& entries = plan->sched.plan_entries;
+  const std::vector<PackTable>& tabs = plan->sched.pack_tabs;
   PLAN_TRY(ctx->pool.alloc((void**)&plan->d_block, block_bytes));
   uint8_t* const base = (uint8_t*)plan->d_block;
   plan->d_queue = (uint32_t*)(base + o_queue); plan->d_ctrl_init = (uint32_t*)(base + o_ctrl); plan->d_pl_entries = (PlanEntry*)(base + o_ent);
@@ -471,7 +234,7 @@ int PlanBuild::upload_compact() {
   plan->d_reads = base + o_reads; plan->d_haps = base + o_haps; plan->d_hap_codes = (uint16_t*)(base + o_codes);
   plan->d_redo_list = (int32_t*)(base + o_list);
   plan->d_redo_count = plan->d_queue + kRedoCountSlot;
-  if (plan->plan_entries.empty()) plan->d_pl_entries = nullptr;
+  if (entries.empty()) plan->d_pl_entries = nullptr;
   if (tabs.empty()) plan->d_pk_tabs = nullptr;
   // the image: the context's pinned staging block, free again once the previous compact plan's copy is through
   if (ctx->compact_ev_pending) { PLAN_TRY(hipEventSynchronize(ctx->compact_ev)); ctx->compact_ev_pending = false; }
@@ -480,7 +243,7 @@ int PlanBuild::upload_compact() {
   std::memset(img, 0, o_pairs);                                                      // control words, table padding
   std::memcpy(img + o_ctrl, ctrl.data(), ctrl.size() * sizeof(uint32_t));
   std::memcpy(img + o_queue, ctrl.data(), ctrl.size() * sizeof(uint32_t));       // (the control words themselves: the first execute needs no reset)
-  if (!plan->plan_entries.empty()) std::memcpy(img + o_ent, plan->plan_entries.data(), plan->plan_entries.size() * sizeof(PlanEntry));
+  if (!entries.empty()) std::memcpy(img + o_ent, entries.data(), entries.size() * sizeof(PlanEntry));
   if (!tabs.empty()) std::memcpy(img + o_tabs, tabs.data(), tabs.size() * sizeof(PackTable));
   std::memcpy(img + o_init, init.data(), init.size() * sizeof(int32_t));
   if (!sorted.empty()) std::memcpy(img + o_pairs, sorted.data(), sorted.size() * sizeof(PairDesc));
@@ -512,6 +275,8 @@ int PlanBuild::upload_compact() {
 
 int PlanBuild::upload_separate() {
   RawBuf<PairDesc>& sorted = ctx->scratch.sorted;
+  const std::vector<PlanEntry>& entries = plan->sched.plan_entries;
+  const std::vector<PackTable>& tabs = plan->sched.pack_tabs;
   PLAN_TRY(ctx->pool.alloc((void**)&plan->d_reads, read_buf));
   PLAN_TRY(ctx->pool.alloc((void**)&plan->d_haps, hap_buf));
   PLAN_TRY(ctx->pool.alloc((void**)&plan->d_hap_codes, hap_buf * sizeof(uint16_t)));
@@ -556,9 +321,9 @@ int PlanBuild::upload_separate() {
     PLAN_TRY(ctx->pool.alloc((void**)&plan->d_wave_clock, nb));
     PLAN_TRY(hipMemset(plan->d_wave_clock, 0, nb));
   }
-  if (!plan->plan_entries.empty()) {
-    PLAN_TRY(ctx->pool.alloc((void**)&plan->d_pl_entries, plan->plan_entries.size() * sizeof(PlanEntry)));
-    PLAN_TRY(hipMemcpy(plan->d_pl_entries, plan->plan_entries.data(), plan->plan_entries.size() * sizeof(PlanEntry), hipMemcpyHostToDevice));
+  if (!entries.empty()) {
+    PLAN_TRY(ctx->pool.alloc((void**)&plan->d_pl_entries, entries.size() * sizeof(PlanEntry)));
+    PLAN_TRY(hipMemcpy(plan->d_pl_entries, entries.data(), entries.size() * sizeof(PlanEntry), hipMemcpyHostToDevice));
   }
   PLAN_TRY(ctx->pool.alloc((void**)&plan->d_redo_list, (size_t)plan->redo_cap * kNumExact * sizeof(int32_t)));
   PLAN_TRY(ctx->pool.alloc((void**)&plan->d_ctrl_init, ctrl.size() * sizeof(uint32_t)));
@@ -588,13 +353,8 @@ int PlanBuild::size_scratch_and_fan() {
     // used to start behind the 23 ms of the W = 10 class)
     plan->fan_lanes = (ctx->pair_packing < 0 && (plan->n_pairs >= (int64_t)16 * ctx->n_cu || plan->uses_wg) && plan->n_pairs < fan_below) ? fan_n : 1;
     const int cap = (int)std::max<size_t>(16, ((size_t)8 << 30) / (per_wave * kBlockWaves * ((size_t)plan->fan_lanes + 1)));
-    for (int k = 0; k < kNumBins; ++k) plan->bin_grid[k] = std::min(plan->bin_grid[k], cap);
-    plan->multi_grid = std::min(plan->multi_grid, cap);
-    plan->plan_grid = std::min(plan->plan_grid, cap);
-    for (int c = 0; c <= kXLong; ++c) plan->x_grid[c] = std::min(plan->x_grid[c], cap);
-    plan->redo_grid = plan->x_grid[kXGeneric];
-    plan->max_grid = std::min(plan->max_grid, cap);
-    plan->scratch_lane_stride = (size_t)plan->max_grid * kBlockWaves * 6 * (size_t)plan->scratch_stride;
+    plan->sched.cap_grids(cap);
+    plan->scratch_lane_stride = (size_t)plan->sched.max_grid * kBlockWaves * 6 * (size_t)plan->scratch_stride;
     PLAN_TRY(ctx->pool.alloc((void**)&plan->d_scratch, plan->scratch_lane_stride * sizeof(double) * ((size_t)plan->fan_lanes + 1)));   // (+ 1: the kXLong exact launch, see ltr_plan_execute)
     if (plan->fan_lanes > 1) {
       PLAN_TRY(hipEventCreateWithFlags(&plan->ev_fork, hipEventDisableTiming));

@@ -63,19 +63,16 @@ struct Execute {
   const bool fan;                           // the launches are dealt over the lanes
   const int nl, nb;                         // lanes; big lanes (with four lanes the last two take the small classes)
   const bool x_fan;                         // the exact launches run on side streams of their own
-  const bool use_plan, split_multi;
+  const std::vector<Launch>& list;          // the launches, in order (level-2 timing: the multi-width launches class by class)
 
   Execute(ltr_plan* p, ltr_ctx* c, double* d_out_ll, void* stream_v);
-  bool is_plan(int k) const { return use_plan && k == plan->plan_rep; }
-  bool is_multi(int k) const { return !use_plan && !split_multi && k == plan->multi_rep; }
-  bool is_pmulti(int k) const { return !use_plan && !split_multi && k == plan->pmulti_rep; }
   int snapshot_tables();
   int reset_control_words();
   int ensure_exact_events();
   hipStream_t exact_stream(int which) const;
   int behind_the_lanes(int c, hipStream_t s2, bool small_events);
   int launch_exact_list(int c, bool small_events);
-  int launch_class(int k, int li);
+  int launch_class(const Launch& L, int li);
   void note_wg_stats();
   int run();
 };
@@ -91,14 +88,11 @@ static bool exact_lists_fan_out(const ltr_plan* plan, const ltr_ctx* ctx) {
 // longest pair, whatever the GPU could do meanwhile) over lanes nb .. nl-1, queued FIRST: they trickle into the tails
 // of the big launches all along the plan instead of following the last of them one after the other (measured on
 // MI355X, a 1250-locus plan: ten small launches of 0.3 - 3 ms each behind the last big one, 4.5 ms of 33).
-// level-2 timing: the multi-width launch class by class (the single-class kernels: same bodies).  Not under the plan kernel:
-// its classes score their failed certificates in line, and no exact launch is sized for what a single-class kernel would queue
+// (level-2 timing: the single-class kernels have the same bodies)
 Execute::Execute(ltr_plan* p, ltr_ctx* c, double* d_out_ll, void* stream_v)
     : plan(p), ctx(c), st(stream_v ? (hipStream_t)stream_v : c->stream), out(d_out_ll ? d_out_ll : p->d_ll), lanes{st, c->aux[2], c->aux[3], c->aux[1]},
       fan(plan->fan_lanes > 1 && !plan->timing && st != lanes[1] && st != lanes[2] && st != lanes[3]),
-      nl(fan ? plan->fan_lanes : 1), nb(nl >= 4 ? 2 : nl), x_fan(exact_lists_fan_out(p, c)),
-      use_plan(plan->use_plan && plan->plan_rep >= 0),      // (either model: the launch picks the instance of the parameters in force now)
-      split_multi(plan->timing >= 2 && !use_plan) {}
+      nl(fan ? plan->fan_lanes : 1), nb(nl >= 4 ? 2 : nl), x_fan(exact_lists_fan_out(p, c)), list(plan->sched.at_level(plan->timing)) {}
 
 // The kernel arguments every launch starts from: the plan's buffers, the model tables in force now, which first pass the
 // workgroup classes get (sym, wg_thr, thr: set here and nowhere else, before the first launch).
@@ -215,7 +209,7 @@ int Execute::behind_the_lanes(int c, hipStream_t s2, bool small_events) {
 int Execute::launch_exact_list(int c, bool small_events) {
   x_done[c] = true;
   const bool usable = (c == kXGeneric) || A.xlut;
-  const int grid = (c == kXGeneric && !A.xlut) ? std::max(plan->x_grid[c], (plan->n_pairs > 0) ? 1 : 0) : plan->x_grid[c];
+  const int grid = (c == kXGeneric && !A.xlut) ? std::max(plan->sched.x_grid[c], (plan->n_pairs > 0) ? 1 : 0) : plan->sched.x_grid[c];
   if (!(usable && grid > 0 && plan->n_pairs > 0)) return LTR_OK;
   KernelArgs X = A;
   X.first_pair = 0; X.n_pairs = 0; X.index = A.xlist[c]; X.n_pairs_dev = plan->d_redo_count + c;
@@ -232,7 +226,7 @@ int Execute::launch_exact_list(int c, bool small_events) {
     KernelArgs B = X;
     B.queue = plan->d_queue + kNumKernels;                   // (a queue word of its own: zeroed with the others)
     B.c_hi = 64 * kXWideW;
-    const int gw = std::max(1, std::min(ctx->full_x_wide_grid, plan->max_grid_wide));
+    const int gw = std::max(1, std::min(ctx->full_x_wide_grid, plan->sched.max_grid_wide));
     hipStream_t ws = exact_stream(kNumExact);
     if (ws != xs && (rc2 = behind_the_lanes(c, ws, small_events)) != LTR_OK) return rc2;
     ltrk::launch_exact(ltrk::kXWideLaunch, sym, dim3((unsigned)gw), ws, B);
@@ -273,42 +267,46 @@ int Execute::launch_exact_list(int c, bool small_events) {
   return LTR_OK;
 }
 
-int Execute::launch_class(int k, int li) {
+int Execute::launch_class(const Launch& L, int li) {
+  const int k = L.cls;
   int np = plan->bin_first[k + 1] - plan->bin_first[k];
   if (wg_thr && thr.nw[k] != 0) { if (thr.np[k] == 0) return LTR_OK; np = thr.np[k]; }      // (scored by the launch of the class that leads its group)
   A.first_pair = plan->bin_first[k]; A.n_pairs = np; A.queue = plan->d_queue + k;
-  const dim3 grid((unsigned)(is_plan(k) ? plan->plan_grid : (is_multi(k) ? plan->multi_grid : (is_pmulti(k) ? plan->pmulti_grid : plan->bin_grid[k]))));
-  const ClassInfo ci = class_info(k);
+  const dim3 grid((unsigned)L.grid);
   hipStream_t ls = lanes[li];
   A.scratch = plan->d_scratch + (size_t)li * plan->scratch_lane_stride;
-  A.lp_shift = ci.lp_shift;
-  if (ci.family == kFamPack) ltrp::pack_ranges(plan->bin_first, ci.W, A.pk_shift, A.pk_first, A.pk_end, A.pk_grp_end);
-  if (is_plan(k)) {
-    A.pk_tabs = plan->d_pk_tabs; A.pk_ntabs = (int32_t)plan->pmulti_reps.size(); A.queue_base = plan->d_queue;
-    A.pl_entries = plan->d_pl_entries; A.pl_n = (int32_t)plan->plan_entries.size();
-    ltrk::launch_plan(sym, grid, ls, A);
-  } else if (is_pmulti(k)) {
-    A.pk_tabs = plan->d_pk_tabs; A.pk_ntabs = (int32_t)plan->pmulti_reps.size(); A.queue_base = plan->d_queue;
-    ltrk::launch_pack_multi(sym, grid, ls, A);
-  } else if (is_multi(k)) {
-    A.mk_n = 0; A.queue_base = plan->d_queue;
-    for (int k2 : plan->multi_classes) {                       // widest strips first
-      A.mk_w[A.mk_n] = class_info(k2).W; A.mk_first[A.mk_n] = plan->bin_first[k2]; A.mk_np[A.mk_n] = plan->bin_first[k2 + 1] - plan->bin_first[k2];
-      A.mk_class[A.mk_n] = k2;
-      ++A.mk_n;
-    }
-    ltrk::launch_multi(sym, grid, ls, A);
-  } else if (ci.family == kFamOne) ltrk::launch_onewave(ci.W, sym, grid, ls, A);
-  else if (ci.family == kFamPack) ltrk::launch_pack(ci.W, sym, grid, ls, A);
-  else if (wg_thr && thr.nw[k] != 0) {
-    // (all of them on the plan's own stream, one after the other: two persistent eight-wave launches of different register
-    // budgets side by side keep half-empty CUs from each other -- config5hifi, thresholds first: 21 + 12 ms alone, 41 ms side by side)
-    const int gt = std::max(1, std::min(np, ctx->full_wgt_grid[thr.nw[k] == 8 ? 1 : 0][thr.w[k]]));
-    ltrk::launch_wgt(thr.nw[k], thr.w[k], dim3((unsigned)gt), lanes[0], A);
+  A.lp_shift = class_info(k).lp_shift;
+  switch (L.kind) {
+    case kLaunchPlan:                                          // (either model: the launch picks the instance of the parameters in force now)
+      A.pl_entries = plan->d_pl_entries; A.pl_n = (int32_t)plan->sched.plan_entries.size();
+      [[fallthrough]];
+    case kLaunchPackMulti:
+      A.pk_tabs = plan->d_pk_tabs; A.pk_ntabs = (int32_t)plan->sched.pack_tabs.size(); A.queue_base = plan->d_queue;
+      if (L.kind == kLaunchPlan) ltrk::launch_plan(sym, grid, ls, A); else ltrk::launch_pack_multi(sym, grid, ls, A);
+      break;
+    case kLaunchMulti:
+      A.mk_n = L.n_one; A.queue_base = plan->d_queue;
+      for (int r = 0; r < L.n_one; ++r) {                      // widest strips first
+        const int k2 = L.members[r];
+        A.mk_w[r] = class_info(k2).W; A.mk_first[r] = plan->bin_first[k2]; A.mk_np[r] = plan->bin_first[k2 + 1] - plan->bin_first[k2]; A.mk_class[r] = k2;
+      }
+      ltrk::launch_multi(sym, grid, ls, A);
+      break;
+    case kLaunchOne: ltrk::launch_onewave(L.W, sym, grid, ls, A); break;
+    case kLaunchPack:
+      ltrp::pack_ranges(plan->bin_first, L.W, A.pk_shift, A.pk_first, A.pk_end, A.pk_grp_end);
+      ltrk::launch_pack(L.W, sym, grid, ls, A);
+      break;
+    default:
+      if (wg_thr && thr.nw[k] != 0) {
+        // (all of them on the plan's own stream, one after the other: two persistent eight-wave launches of different register
+        // budgets side by side keep half-empty CUs from each other -- config5hifi, thresholds first: 21 + 12 ms alone, 41 ms side by side)
+        const int gt = std::max(1, std::min(np, ctx->full_wgt_grid[thr.nw[k] == 8 ? 1 : 0][thr.w[k]]));
+        ltrk::launch_wgt(thr.nw[k], thr.w[k], dim3((unsigned)gt), lanes[0], A);
+      } else ltrk::launch_wg(class_info(k).waves, L.W, grid, ls, A);
   }
-  else ltrk::launch_wg(ci.waves, ci.W, grid, ls, A);
   HIP_TRY(ctx, hipGetLastError());
-  LTR_DBG("launched class %d grid %d pairs %d on lane %d", k, plan->bin_grid[k], np, li);
+  LTR_DBG("launched class %d grid %d pairs %d on lane %d", k, L.grid, np, li);
   ++launches;
   return LTR_OK;
 }
@@ -335,8 +333,8 @@ int Execute::run() {
   int rc;
   if ((rc = snapshot_tables()) != LTR_OK || (rc = reset_control_words()) != LTR_OK) return rc;
   HIP_TRY(ctx, hipEventRecord(plan->ev0, st));
-  // Launch order: the certificate classes longest reads first (plan->order), then the exact kernels; with per-launch
-  // timing, launch number o runs between bin_ev[o] and bin_ev[o+1] (plan->order_pos).
+  // Launch order: the first-pass launches longest reads first (ltrp::build_schedule), then the exact kernels; with per-launch
+  // timing, launch number o runs between bin_ev[o] and bin_ev[o+1].
   // (The classes are independent and every launch ends in a tail in which only its longest pairs still run: the
   // launches alternate between two streams, see ltr_plan_create.)
   int o = 0;
@@ -346,17 +344,16 @@ int Execute::run() {
     for (int k = 1; k < nl; ++k) HIP_TRY(ctx, hipStreamWaitEvent(lanes[k], plan->ev_fork, 0));
   }
   if (x_fan && (rc = ensure_exact_events()) != LTR_OK) return rc;
-  const std::vector<int>& launch_order = split_multi ? plan->order2 : plan->order;
-  std::vector<int> big, small;                                  // both longest reads first
-  for (int k : launch_order) ((nl > nb && (is_plan(k) ? plan->plan_small : (is_multi(k) ? plan->multi_small : (is_pmulti(k) ? plan->pmulti_small : plan->bin_small[k])))) ? small : big).push_back(k);
+  std::vector<const Launch*> big, small;                        // both longest reads first
+  for (const Launch& L : list) ((nl > nb && L.small) ? small : big).push_back(&L);
   // the small classes first, on their own lanes; per exact list an event on each of those lanes once nothing small still
   // to come can feed it
   bool small_closed[kNumExact] = {false};
   for (size_t p = 0; p < small.size(); ++p) {
-    const int rc2 = launch_class(small[p], nb + (int)(p % (size_t)(nl - nb)));
+    const int rc2 = launch_class(*small[p], nb + (int)(p % (size_t)(nl - nb)));
     if (rc2 != LTR_OK) return rc2;
     if (x_fan && A.xlut) {
-      const int next_cmax = (p + 1 < small.size()) ? plan->cls_cmax[small[p + 1]] : -1;
+      const int next_cmax = (p + 1 < small.size()) ? small[p + 1]->cmax : -1;
       for (int c = kNumExact - 1; c > kXShort; --c)
         if (!small_closed[c] && next_cmax < kListMinC[c]) {
           small_closed[c] = true;
@@ -366,12 +363,12 @@ int Execute::run() {
   }
   for (size_t p = 0; p < big.size(); ++p) {
     // (round-robin; giving every launch to the stream with less work queued so far measured 0.4 % slower)
-    const int rc2 = launch_class(big[p], (int)(p % (size_t)nb));
+    const int rc2 = launch_class(*big[p], (int)(p % (size_t)nb));
     if (rc2 != LTR_OK) return rc2;
     if (plan->timing) HIP_TRY(ctx, hipEventRecord(plan->bin_ev[++o], st));
     // exact lists nothing still to come can feed: the next class holds only shorter reads than the list takes
     if (x_fan && A.xlut) {
-      const int next_cmax = (p + 1 < big.size()) ? plan->cls_cmax[big[p + 1]] : -1;
+      const int next_cmax = (p + 1 < big.size()) ? big[p + 1]->cmax : -1;
       for (int c = kNumExact - 1; c > kXShort; --c)
         if (!x_done[c] && next_cmax < kListMinC[c] && next_cmax >= 0) { const int rc3 = launch_exact_list(c, small_closed[c]); if (rc3 != LTR_OK) return rc3; }
     }
@@ -395,7 +392,7 @@ int Execute::run() {
   plan->last_wg_thr = wg_thr;
   plan->last_out = out; plan->last_stream = st; plan->last_launches = launches; plan->executed = true;
   if (std::find(plan->streams.begin(), plan->streams.end(), st) == plan->streams.end()) plan->streams.push_back(st);
-  plan->timed = (use_plan && plan->timing >= 2) ? 1 : plan->timing;     // (the plan kernel is never split: its launches were timed as launched)
+  plan->timed = plan->sched.plan_launch() ? std::min(plan->timing, 1) : plan->timing;     // (the plan kernel is never split: its launches were timed as launched)
   plan->kernel_ms_counted = false;
   return LTR_OK;
 }
@@ -503,38 +500,14 @@ int ltr_plan_kernel_stats(ltr_plan* plan, int k, int* strip_width, int64_t* n_pa
   const int xc = k - kNumFast;
   static const int kXW[kNumExact] = {kExactW, kXShortW, kXMidW, kXLongW, 0, 0};     // (workgroup exact kernels pick the width per pair)
   if (strip_width) *strip_width = redo ? kXW[xc] : class_info(k).W;
-  // a packed launch scores every lanes-per-pair block of its strip width: its pairs, cells and time are reported under
-  // its representative class (ltr_plan_kernel_ranges names the blocks), the other classes of the width report nothing
-  const bool pack = !redo && k >= kPackFirst && k < kWg4First;
-  double cl = redo ? plan->x_cells[xc] : plan->bin_cells[k];
-  int64_t np = redo ? 0 : plan->bin_first[k + 1] - plan->bin_first[k];
-  const bool plan_member = !redo && plan->use_plan && plan->plan_rep >= 0 && k < kWg4First;
-  if (plan_member) {
-    // the plan kernel: every one-wave class and packed width in one launch, reported under plan_rep
-    cl = 0.0; np = 0;
-    if (k == plan->plan_rep) for (int k2 = 0; k2 < kWg4First; ++k2) { cl += plan->bin_cells[k2]; np += plan->bin_first[k2 + 1] - plan->bin_first[k2]; }
-  }
-  const bool multi_member = !plan_member && !redo && plan->multi_rep >= 0 && plan->timed < 2 && k < kNumBins && k >= kMultiMinW - 1;
-  if (multi_member) {
-    // ... and so does the multi-width one-wave launch (unless the last execute ran it class by class: timing level 2)
-    cl = 0.0; np = 0;
-    if (k == plan->multi_rep) for (int k2 : plan->multi_classes) { cl += plan->bin_cells[k2]; np += plan->bin_first[k2 + 1] - plan->bin_first[k2]; }
-  }
-  if (pack && !plan_member) {
-    cl = 0.0; np = 0;
-    auto add_width = [&](int w) {
-      for (int sft = kPackMinShift; sft <= kPackMaxShift; ++sft) {
-        const int k2 = ltrp::pack_class(sft, w);
-        cl += plan->bin_cells[k2]; np += plan->bin_first[k2 + 1] - plan->bin_first[k2];
-      }
-    };
-    const bool in_pm = plan->pmulti_rep >= 0 && plan->timed < 2 && class_info(k).W >= kPackMultiMinW;
-    if (in_pm) { if (k == plan->pmulti_rep) for (int rep : plan->pmulti_reps) add_width(class_info(rep).W); }
-    else if (plan->pack_rep[k - kPackFirst] == k) add_width(class_info(k).W);
-  }
-  if (cells) *cells = cl;
+  // a launch that scores several classes -- every lanes-per-pair block of a packed strip width, a multi-width launch, the plan
+  // kernel -- reports its pairs, cells and time under the class it is listed under (ltr_plan_kernel_ranges names the classes),
+  // its other classes report nothing; launch number o ran between bin_ev[o] and bin_ev[o+1] (see ltr_plan_execute)
+  const std::vector<Launch>& list = plan->sched.at_level(plan->timed);
+  const int o = redo ? (int)list.size() + xc : Schedule::find(list, k);
+  if (cells) *cells = redo ? plan->stats.x_cells[xc] : (o >= 0 ? list[(size_t)o].cells : 0.0);
   if (n_pairs) {
-    *n_pairs = np;
+    *n_pairs = (redo || o < 0) ? 0 : list[(size_t)o].pairs;
     if (redo && plan->executed) {                      // pairs the certificates could not clear (+ the non-ACGT ones, generic list)
       uint32_t c[kInlineCountOff + kNumExact] = {0};
       HIP_TRY(ctx, hipStreamSynchronize(plan->last_stream));
@@ -544,13 +517,9 @@ int ltr_plan_kernel_stats(ltr_plan* plan, int k, int* strip_width, int64_t* n_pa
   }
   if (ms) {
     *ms = 0.f;
-    if (plan->executed && plan->timed) {
-      // launch number o ran between bin_ev[o] and bin_ev[o+1] (see ltr_plan_execute)
-      const int o = plan->timed >= 2 ? plan->order_pos2[k] : plan->order_pos[k];
-      if (o >= 0) {
-        HIP_TRY(ctx, hipEventSynchronize(plan->bin_ev[o + 1]));
-        HIP_TRY(ctx, hipEventElapsedTime(ms, plan->bin_ev[o], plan->bin_ev[o + 1]));
-      }
+    if (plan->executed && plan->timed && o >= 0) {
+      HIP_TRY(ctx, hipEventSynchronize(plan->bin_ev[o + 1]));
+      HIP_TRY(ctx, hipEventElapsedTime(ms, plan->bin_ev[o], plan->bin_ev[o + 1]));
     }
   }
   return LTR_OK;
@@ -558,68 +527,27 @@ int ltr_plan_kernel_stats(ltr_plan* plan, int k, int* strip_width, int64_t* n_pa
 
 int ltr_plan_kernel_ranges(ltr_plan* plan, int k, int32_t* lanes_per_pair, int32_t* strip_width, int64_t* n_pairs) {
   if (!plan || k < 0 || k >= kNumKernels) return LTR_ERR_INVALID;
-  int nr = 0;
-  if (plan->use_plan && plan->plan_rep >= 0) {
-    if (k >= kWg4First || k != plan->plan_rep) return 0;
-    // (at most kNumBins + kNumPack ranges: the caller's arrays hold ltr_num_kernels() entries)
-    for (int k2 : plan->multi_classes) {
-      if (lanes_per_pair) lanes_per_pair[nr] = 64;
-      if (strip_width) strip_width[nr] = class_info(k2).W;
-      if (n_pairs) n_pairs[nr] = plan->bin_first[k2 + 1] - plan->bin_first[k2];
-      ++nr;
-    }
-    for (int rep : plan->pmulti_reps)
-      for (int sft = kPackMaxShift; sft >= kPackMinShift; --sft) {
-        const int k2 = ltrp::pack_class(sft, class_info(rep).W);
-        const int c2 = plan->bin_first[k2 + 1] - plan->bin_first[k2];
-        if (c2 <= 0) continue;
-        if (lanes_per_pair) lanes_per_pair[nr] = 1 << sft;
-        if (strip_width) strip_width[nr] = class_info(rep).W;
-        if (n_pairs) n_pairs[nr] = c2;
-        ++nr;
-      }
-    return nr;
-  }
-  if (k == plan->multi_rep && plan->timed < 2) {
-    for (int k2 : plan->multi_classes) {
-      if (lanes_per_pair) lanes_per_pair[nr] = 64;
-      if (strip_width) strip_width[nr] = class_info(k2).W;
-      if (n_pairs) n_pairs[nr] = plan->bin_first[k2 + 1] - plan->bin_first[k2];
-      ++nr;
-    }
-    return nr;
-  }
-  if (!(k >= kPackFirst && k < kWg4First) || plan->pack_rep[k - kPackFirst] != k) return 0;
-  auto width = [&](int w) {
-    for (int sft = kPackMaxShift; sft >= kPackMinShift; --sft) {
-      const int k2 = ltrp::pack_class(sft, w);
-      const int c2 = plan->bin_first[k2 + 1] - plan->bin_first[k2];
-      if (c2 <= 0) continue;
-      if (lanes_per_pair) lanes_per_pair[nr] = 1 << sft;
-      if (strip_width) strip_width[nr] = w;
-      if (n_pairs) n_pairs[nr] = c2;
-      ++nr;
-    }
-  };
-  const bool in_pm = plan->pmulti_rep >= 0 && plan->timed < 2 && class_info(k).W >= kPackMultiMinW;
-  if (in_pm) { if (k == plan->pmulti_rep) for (int rep : plan->pmulti_reps) width(class_info(rep).W); }
-  else width(class_info(k).W);
-  return nr;
+  const std::vector<Launch>& list = plan->sched.at_level(plan->timed);
+  const int o = Schedule::find(list, k);
+  return o < 0 ? 0 : plan->sched.ranges(list[(size_t)o], plan->bin_first, lanes_per_pair, strip_width, n_pairs);
 }
 
-int ltr_plan_kernel_class(const ltr_plan* plan) { return (plan && plan->use_plan) ? plan->plan_rep : -1; }
+int ltr_plan_kernel_class(const ltr_plan* plan) {
+  const Launch* P = plan ? plan->sched.plan_launch() : nullptr;
+  return P ? P->cls : -1;
+}
 
 int ltr_plan_debug_entries(const ltr_plan* plan, int32_t* kind, int32_t* strip_width, int64_t* n_pairs, double* cells, int cap) {
   if (!plan || cap < 0) return LTR_ERR_INVALID;
-  const int n = (int)plan->plan_entries.size();
+  const int n = (int)plan->sched.plan_entries.size();
   for (int i = 0; i < std::min(n, cap); ++i) {
-    const PlanEntry& e = plan->plan_entries[(size_t)i];
+    const PlanEntry& e = plan->sched.plan_entries[(size_t)i];
     int64_t np = e.n_pairs; double cl = 0.0;
-    if (e.kind == 0 || e.kind == 3) cl = plan->bin_cells[e.queue_class];
-    else if (e.kind == 1) {
-      np = 0;
-      for (int sft = kPackMinShift; sft <= kPackMaxShift; ++sft) { const int k2 = ltrp::pack_class(sft, e.W); cl += plan->bin_cells[k2]; np += plan->bin_first[k2 + 1] - plan->bin_first[k2]; }
-    } else cl = plan->x_cells[e.queue_class - ltrp::kStartQueueSlot];
+    if (e.kind == 2) cl = plan->stats.x_cells[e.queue_class - ltrp::kStartQueueSlot];
+    else {                                                       // (a class, or a packed width: what its own launch would report)
+      const Launch& L = plan->sched.by_class[(size_t)Schedule::find(plan->sched.by_class, e.queue_class)];
+      np = L.pairs; cl = L.cells;
+    }
     if (kind) kind[i] = e.kind;
     if (strip_width) strip_width[i] = e.W;
     if (n_pairs) n_pairs[i] = np;
@@ -632,7 +560,7 @@ int ltr_plan_debug_wave_clocks(ltr_plan* plan, uint64_t* out, int64_t cap) {
   if (!plan || !plan->ctx || !out || cap < 0) return LTR_ERR_INVALID;
   if (!plan->d_wave_clock || !plan->executed) return 0;
   ltr_ctx* ctx = plan->ctx;
-  const int64_t n = (int64_t)plan->plan_grid * kBlockWaves;
+  const int64_t n = (int64_t)plan->sched.plan_launch()->grid * kBlockWaves;
   if (cap < 4 * n + 4096 + 256) return LTR_ERR_INVALID;
   HIP_TRY(ctx, hipStreamSynchronize(plan->last_stream));
   HIP_TRY(ctx, hipMemcpy(out, plan->d_wave_clock, ((size_t)n * 4 + 4096 + 256) * sizeof(uint64_t), hipMemcpyDeviceToHost));

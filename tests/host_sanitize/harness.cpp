@@ -1,5 +1,5 @@
 // tests/host_sanitize/harness.cpp -- TEST INFRASTRUCTURE.
-// Fuzzes the host-only entry points of the C-ABI library (ltr_host.cpp, ltr_genotype.cpp) under
+// Fuzzes the host-only entry points of the C-ABI library (ltr_host.cpp, ltr_genotype.cpp, the planning units of ltr_plan.cpp) under
 // AddressSanitizer + UBSan on the CPU: trimming, haplotype enumeration, pooling, scatter, genotype
 // fields, and ltr_process_reads' host half (trim + haplotype strings) up to the point where it
 // would hand the batch to the GPU.  The four library-internal symbols those files need from the HIP
@@ -19,10 +19,13 @@
 #include <unistd.h>
 
 #include "../../longtr_amd/csrc/ltr_internal.h"
+#include "../../longtr_amd/csrc/ltr_plan.h"
 
 struct ltr_ctx { ltr_align_params p; std::string err; std::vector<uint8_t> host_bytes[4]; std::mutex call_mu, err_mu; ltr::DebugKnobs knobs; bool fake_device = false; };
 struct ltr_plan { int64_t ll_size = 0, pairs = 0; };               // (the fake device's plan: sizes only)
 namespace ltr {
+std::atomic<int> g_trace{0};                                      // (the trace switch and its clock live with the context, ltr_ctx.hip)
+double dbg_ms() { return 0.0; }
 void set_error(ltr_ctx* ctx, const std::string& msg) { if (ctx) { std::lock_guard<std::mutex> lk(ctx->err_mu); ctx->err = msg; } }
 ltr_align_params ctx_params(const ltr_ctx* ctx) { return ctx->p; }
 DebugKnobs ctx_debug(const ltr_ctx* ctx) { return ctx->knobs; }
@@ -39,6 +42,10 @@ int short_batch_add(ltr_ctx*, ShortBatch* b, const ltr_haplotype_blocks*, const 
                     const uint8_t*, double*, int32_t*) { b->n++; return LTR_OK; }
 int short_batch_merge(ltr_ctx*, ShortBatch* dst, ShortBatch* src) { dst->n += src->n; src->n = 0; return LTR_OK; }
 int short_batch_run(ltr_ctx*, ShortBatch*) { return LTR_ERR_NO_DEVICE; }
+}
+namespace ltrp {                                                   // (no page-locked memory without a device: RawBuf falls back to malloc)
+void* pinned_alloc(size_t) { return nullptr; }
+void pinned_free(void*) {}
 }
 static std::atomic<long> g_batches(0), g_pairs(0);                 // (the stub scorer is called from two threads at once below)
 // A context with fake_device set gets plans that "run": every row the library asks for comes back as its own index, so that the
@@ -400,6 +407,36 @@ int main(int argc, char** argv) {
     ltr_genotype_fields f = {gts.data(), a.data(), b2.data(), c.data(), d.data(), it % 3 ? gl.data() : nullptr, it % 2 ? gd.data() : nullptr,
                              it % 5 ? pls.data() : nullptr, it % 7 ? pg.data() : nullptr};
     (void)ltr_extract_genotypes(S, H, V, h2a.data(), hap, post.data(), stl.data(), best.data(), &f);
+    checks++;
+  }
+  // ---- the launch schedule of a plan (ltrp::describe_batch, class_stats, build_schedule): random batches, every schedule ----
+  for (int it = 0; it < 300; ++it) {
+    const int n_loci = ri(0, 12);
+    std::vector<int64_t> lro(1, 0), lho(1, 0), ro(1, 0), ho(1, 0);
+    std::string rb, hb;
+    for (int l = 0; l < n_loci; ++l) {
+      const int base = (it % 7 == 0) ? ri(1, 3000) : ri(1, 700), nr = ri(0, 6), nh = ri(0, 4);
+      for (int r = 0; r < nr; ++r) { std::string s = rseq(std::max(1, base + ri(-30, 30))); if (ri(0, 20) == 0) s[0] = 'N'; rb += s; ro.push_back((int64_t)rb.size()); }
+      for (int h = 0; h < nh; ++h) { hb += rseq(ri(0, 9) == 0 ? ri(0, 60) : base + 60 + ri(-20, 20)); ho.push_back((int64_t)hb.size()); }
+      lro.push_back((int64_t)ro.size() - 1); lho.push_back((int64_t)ho.size() - 1);
+    }
+    ltr_locus_batch b = {};
+    b.n_loci = n_loci; b.locus_read_off = lro.data(); b.locus_hap_off = lho.data();
+    b.n_reads = (int64_t)ro.size() - 1; b.read_bytes = (const uint8_t*)rb.data(); b.read_off = ro.data();
+    b.n_haps = (int64_t)ho.size() - 1; b.hap_bytes = (const uint8_t*)hb.data(); b.hap_off = ho.data();
+    ltr_align_params prm = {-1.0f, -0.458675f, -1.0f, it % 4 == 0 ? -0.5f : -0.458675f, -0.00005800168f, -10.448214f, -10.448214f, 5, 0};   // (every fourth: an asymmetric model)
+    const int nk = ltr_debug_num_classes();
+    std::vector<int32_t> grids((size_t)nk + 3);
+    for (auto& g : grids) g = ri(1, 40);
+    const int32_t knobs[7] = {ri(0, 1), ri(-1, 1), ri(0, 1), ri(0, 20), ri(0, 20), ri(0, 1), ri(0, 9)};
+    const int mode = (it % 3 == 0) ? ri(-1, 8) : -1;
+    std::vector<int64_t> out((size_t)8 + kNumExact + nk + 1);
+    std::vector<int32_t> xg(kNumExact), launch((size_t)2 * nk * 8), members((size_t)2 * nk + 128), entry(256 * 6);
+    std::vector<double> cells((size_t)2 * nk);
+    const int rc = ltr_debug_plan_schedule(&prm, mode, ri(1, 4), &b, grids.data(), knobs, out.data(), xg.data(), 2 * nk, launch.data(), cells.data(),
+                                           (int)members.size(), members.data(), 256, entry.data());
+    if (rc != LTR_OK && rc != LTR_ERR_INVALID) { std::printf("plan_schedule rc %d\n", rc); return 1; }
+    if (rc == LTR_OK && (out[0] > nk || out[1] > nk || out[2] > 256 || out[5] < 1)) { std::printf("plan_schedule out of range\n"); return 1; }
     checks++;
   }
   std::printf("host sanitizer harness: %ld cases, %ld batches reached the scorer (%ld pairs)\n", checks, g_batches.load(), g_pairs.load());

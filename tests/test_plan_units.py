@@ -355,3 +355,197 @@ def test_threshold_groups_merge_neighbouring_narrow_eight_wave_classes():
                 if counts[k]:
                     ci = class_info(k)
                     assert nw[k] == ci["waves"] and w[k] == ci["W"] + (ci["W"] & 1)
+
+
+# ---- the launch schedule of a plan (ltrp::build_schedule) through ltr_debug_plan_schedule: every expectation below is worked out
+# ---- here from the loci, never read back from the function ----
+
+def _locus(rng, m, n_reads, n_haps, hap_len=None):
+    """n_reads reads of m bases against n_haps haplotypes whose window (the haplotype less 2 x 30 of flank) is m bases too."""
+    seq = lambda n: bytes(rng.choice(list(b"ACGT"), size=n).astype(np.uint8))
+    return [seq(m) for _ in range(n_reads)], [seq(m + 60 if hap_len is None else hap_len) for _ in range(n_haps)]
+
+
+def _grids(value=1000, **named):
+    """Made-up occupancy grids: `value` everywhere; named: class index (int key via cls=...) or multi / pack_multi / plan."""
+    g = np.full(NK + 3, value, dtype=np.int32)
+    for name, v in named.items():
+        g[{"multi": NK, "pack_multi": NK + 1, "plan": NK + 2}[name]] = v
+    return g
+
+
+def _class(family, W, lanes):
+    return next(k for k in range(NK) if (class_info(k)["family"], class_info(k)["W"], class_info(k)["lanes"]) == (family, W, lanes))
+
+
+def test_schedule_a_packed_width_is_one_launch_under_its_widest_segments():
+    rng = np.random.default_rng(21)
+    # mode 8: two lanes per pair whenever the read fits 2 x 20 columns, else the next segment width that holds it in 20 columns:
+    # 640 columns = 32 x 20, 160 = 8 x 20 (4 x 20 is too few), 40 = 2 x 20 -- strip width 20 at 32, 8 and 2 lanes per pair
+    batch = _abi.PackedBatch([_locus(rng, 641, 3, 2), _locus(rng, 161, 5, 2), _locus(rng, 41, 20, 2)])
+    k32, k8, k2 = _class(1, 20, 32), _class(1, 20, 8), _class(1, 20, 2)
+    s = _lib.debug_plan_schedule(batch, _grids(), mode=8)
+    first = s["class_first"]
+    assert [int(first[k + 1] - first[k]) for k in (k32, k8, k2)] == [6, 10, 40] and first[NK] == 56
+    assert len(s["launches"]) == 1 and s["by_class"] == s["launches"] and not s["use_plan"] and not s["entries"]
+    l = s["launches"][0]
+    # waves: 6 pairs two at a time, 10 pairs eight at a time, 40 pairs 32 at a time = 3 + 2 + 2; four waves a workgroup
+    assert (l["kind"], l["cls"], l["W"], l["members"]) == ("packed", k32, 20, [k32])
+    assert l["cmax"] == 640 and l["pairs"] == 56 and l["cells"] == 6 * 641.0 * 641 + 10 * 161.0 * 161 + 40 * 41.0 * 41
+    assert l["grid"] == 2 and l["small"]
+    # ... capped by the occupancy grid of the class it is listed under (and by no other class's)
+    g = _grids()
+    g[k32] = 1
+    l = _lib.debug_plan_schedule(batch, g, mode=8)["launches"][0]
+    assert l["grid"] == 1 and not l["small"]
+    g = _grids()
+    g[k8] = g[k2] = 1
+    assert _lib.debug_plan_schedule(batch, g, mode=8)["launches"][0]["grid"] == 2
+    # without the 32-lane pairs the launch is listed under the 8-lane class
+    s = _lib.debug_plan_schedule(_abi.PackedBatch([_locus(rng, 161, 5, 2), _locus(rng, 41, 20, 2)]), _grids(), mode=8)
+    assert [(l["cls"], l["cmax"], l["pairs"], l["grid"]) for l in s["launches"]] == [(k8, 160, 50, 1)]
+
+
+def _mixed_batch(rng, one_wave=(1201, 801), packed=(601, 481), extra=()):
+    """Automatic mode at one CU (every batch counts as large: short reads are packed): one-wave classes for the reads beyond 641
+    bases, packed classes below (41-base reads: 40 columns = 8 lanes x 5); 41-base reads against a 40-base haplotype are shortcuts
+    (constant score): they keep the one-wave class of their length, W = 1.  24 pairs a one-wave class, 48 a packed one: six rounds of one CU's four wave slots, so
+    that no class is folded into a wider one."""
+    loci = [_locus(rng, m, 4, 6) for m in one_wave] + [_locus(rng, m, 4, 12) for m in packed]
+    loci.append(_locus(rng, 41, 4, 12))
+    loci.append(_locus(rng, 41, 4, 6, hap_len=40))
+    loci.extend(extra)
+    return _abi.PackedBatch(loci)
+
+
+def test_schedule_launch_per_class_is_ordered_by_longest_read_ties_in_class_order():
+    s = _lib.debug_plan_schedule(_mixed_batch(np.random.default_rng(22)), _grids(), n_cu=1, plan_kernel=1, no_multi=1)
+    assert s["launches"] == s["by_class"] and not s["use_plan"] and not s["entries"] and s["n_tabs"] == 0
+    assert all((l["kind"], l["pairs"]) in (("one-wave", 24), ("packed", 48)) for l in s["launches"])
+    # W: 1200 columns in one block of 64 x 19, 800 in 64 x 13; packed 600 = 32 x 19, 480 = 32 x 15, 40 = 8 x 5; the shortcuts 40 = 64 x 1
+    assert [(l["kind"], l["W"], l["cmax"]) for l in s["launches"]] == [
+        ("one-wave", 19, 1200), ("one-wave", 13, 800), ("packed", 19, 600), ("packed", 15, 480), ("packed", 5, 40), ("one-wave", 1, 40)]
+    assert s["launches"][4]["cls"] > s["launches"][5]["cls"]                 # the tie at 40 columns: descending class index
+    assert s["launches"][5]["cells"] == 0.0 and s["launches"][4]["cells"] == 48 * 41.0 * 41      # (a shortcut has no cells)
+    # 24 waves (one pair / two pairs each), four waves a workgroup; 48 pairs eight at a time = 6 waves
+    assert [l["grid"] for l in s["launches"]] == [6, 6, 6, 6, 2, 6] and all(l["small"] for l in s["launches"])
+
+
+def test_schedule_multi_width_launches_need_two_widths_with_pairs():
+    rng = np.random.default_rng(23)
+    kMultiMinW, kPackMultiMinW = 11, 13
+    s = _lib.debug_plan_schedule(_mixed_batch(rng), _grids(multi=5), n_cu=1, plan_kernel=1, no_multi=-1)
+    got = [(l["kind"], l["cmax"], l["pairs"], [class_info(k)["W"] for k in l["members"]]) for l in s["launches"]]
+    assert got == [("multi", 1200, 48, [19, 13]), ("packed-multi", 600, 96, [19, 15]), ("packed", 40, 48, [5]), ("one-wave", 40, 24, [1])]
+    assert all(class_info(k)["W"] >= kMultiMinW for k in s["launches"][0]["members"]) and all(class_info(k)["W"] >= kPackMultiMinW for k in s["launches"][1]["members"])
+    multi, pmulti = s["launches"][:2]
+    assert multi["cls"] == _class(0, 19, 64) and multi["grid"] == 5 and not multi["small"]        # 48 waves = 12 workgroups against 5 resident
+    assert pmulti["cls"] == _class(1, 19, 32) and pmulti["grid"] == 12 and pmulti["small"] and s["n_tabs"] == 2     # 2 x 24 waves
+    assert multi["cells"] == 24 * (1201.0 * 1201 + 801.0 * 801)
+    # the level-2 list holds every class separately
+    assert [(l["kind"], l["W"], l["cmax"], l["pairs"]) for l in s["by_class"]] == [
+        ("one-wave", 19, 1200, 24), ("one-wave", 13, 800, 24), ("packed", 19, 600, 48), ("packed", 15, 480, 48), ("packed", 5, 40, 48), ("one-wave", 1, 40, 24)]
+    # one width each: nothing to share, a launch per class
+    s = _lib.debug_plan_schedule(_mixed_batch(rng, one_wave=(1201,), packed=(601,)), _grids(), n_cu=1, plan_kernel=1, no_multi=-1)
+    assert [(l["kind"], l["W"], l["cmax"]) for l in s["launches"]] == [("one-wave", 19, 1200), ("packed", 19, 600), ("packed", 5, 40), ("one-wave", 1, 40)]
+    assert s["launches"] == s["by_class"] and s["n_tabs"] == 0
+    # two one-wave widths, one of them below kMultiMinW: 700 columns = 64 x 11, 40 (the shortcuts) = 64 x 1
+    s = _lib.debug_plan_schedule(_mixed_batch(rng, one_wave=(701,), packed=()), _grids(), n_cu=1, plan_kernel=1, no_multi=-1)
+    assert [(l["kind"], l["W"]) for l in s["launches"] if l["kind"] != "packed"] == [("one-wave", 11), ("one-wave", 1)] and len(s["launches"]) == 3
+
+
+def _entry_longest(e, cmax, lanes=64):
+    """The plan kernel's launch-order model of an entry: column blocks x (longest read + fill) x strip cost; packed: one block."""
+    if e["kind"] == 1:
+        return (cmax + float(lanes)) * (e["W"] + 1.5)
+    return max(-(-cmax // (64 * e["W"])), 1) * (cmax + 64.0) * (e["W"] + 1.5)
+
+
+def test_schedule_plan_kernel_is_one_launch_with_a_table_longest_first():
+    rng = np.random.default_rng(24)
+    # two list starters on top of the mixed batch: a read with a byte outside ACGT (generic list), a read 520 bases longer than
+    # its window (no certificate can hold that: the list of its length, 820 columns = kXLong)
+    n_read = _locus(rng, 201, 1, 2)
+    n_read[0][0] = n_read[0][0][:5] + b"N" + n_read[0][0][6:]
+    risky = _locus(rng, 821, 1, 3, hap_len=301 + 60)
+    batch = _mixed_batch(rng, extra=[n_read, risky])
+    s = _lib.debug_plan_schedule(batch, _grids(plan=20), n_cu=1)
+    assert s["use_plan"] and len(s["launches"]) == 1 and s["n_tabs"] == 3
+    p = s["launches"][0]
+    one = [_class(0, w, 64) for w in (19, 13, 1)]
+    packs = [_class(1, 19, 32), _class(1, 15, 32), _class(1, 5, 8)]
+    assert p["kind"] == "plan" and p["cls"] == one[0] and p["members"] == one + packs and p["cmax"] == 1200 and p["pairs"] == 3 * 24 + 3 * 48
+    # wavefronts: 3 x 24 one-wave pairs + 24 + 24 + 6 packed groups + 2 + 3 starters = 131 -> 33 workgroups against 20 resident
+    assert p["grid"] == 20 and not p["small"] and s["max_grid"] == 20
+    assert (s["xcand"] == 0).all() and (s["x_grid"] == 0).all()              # the plan kernel scores failed certificates and starters itself
+    ents = s["entries"]
+    assert [(e["kind"], e["W"], e["pairs"]) for e in ents[:2]] == [(2, 0, 2), (2, 1, 3)]      # the starters, generic list first
+    cmax = {(0, 19): 1200, (0, 13): 800, (0, 1): 40, (1, 19): 600, (1, 15): 480, (1, 5): 40}
+    # (the entry of the class the launch is listed under carries the launch's longest read, the first packed width the longest of
+    # any packed width: here their own)
+    want = sorted(cmax, key=lambda kw: -_entry_longest(dict(kind=kw[0], W=kw[1]), cmax[kw], lanes=8 if kw[1] == 5 else 32))
+    assert [(e["kind"], e["W"]) for e in ents[2:]] == want
+    assert [e["pairs"] for e in ents[2:] if e["kind"] == 0] == [24, 24, 24]
+    fw = [e["first_wave"] for e in ents]
+    assert fw[0] == 0 and fw == sorted(fw) and fw[-1] <= p["grid"] * 4 and len(set(fw)) > 2
+    s1 = _lib.debug_plan_schedule(batch, _grids(plan=20), n_cu=1, plan_share=1)
+    assert [e["first_wave"] for e in s1["entries"]] == [0] + [0x7fffffff] * (len(ents) - 1)
+    assert [(e["kind"], e["W"]) for e in s1["entries"]] == [(e["kind"], e["W"]) for e in ents]
+
+    # chain = 1: the chained walk (kind 3) for one-wave widths kMultiMinW .. kWMax whose scratch strip holds the parked row
+    def chained(sched, lo=11, hi=20):
+        have = 6 * ((sched["max_len"] + 2 + 15) // 16) * 16
+        out = []
+        for e in sched["entries"]:
+            need = 2 * e["W"] * 64 + ((e["W"] + 3) // 4) * 32 + 2
+            out.append(3 if e["kind"] == 0 and lo <= e["W"] <= hi and need <= have else e["kind"])
+        return out
+    sc = _lib.debug_plan_schedule(batch, _grids(plan=20), n_cu=1, chain=1)
+    assert sc["max_len"] == 1201 and [e["kind"] for e in sc["entries"]] == chained(sc) and [e["kind"] for e in sc["entries"]].count(3) == 2
+    sc = _lib.debug_plan_schedule(batch, _grids(plan=20), n_cu=1, chain=1, chain_min_w=14)
+    assert [e["kind"] for e in sc["entries"]] == chained(sc, lo=14) and [e["kind"] for e in sc["entries"]].count(3) == 1
+    sc = _lib.debug_plan_schedule(batch, _grids(plan=20), n_cu=1, chain=1, chain_min_w=3)       # (never below kMultiMinW)
+    assert [e["kind"] for e in sc["entries"]].count(3) == 2
+    asym = _abi.make_params((-1.0, -0.45, -1.0, -0.5, -0.0001, -10.0, -9.0))
+    sc = _lib.debug_plan_schedule(batch, _grids(plan=20), n_cu=1, chain=1, params=asym)
+    assert sc["use_plan"] and 3 not in [e["kind"] for e in sc["entries"]]
+    # a strip too short for the parked row: the W = 11 class holds shortcuts only (701-base reads against a 40-base haplotype), and
+    # shortcuts do not size the strips -- 201-base reads do: need = 2 x 11 x 64 + 3 x 32 + 2 = 1506 > have = 6 x 208 = 1248
+    short = _abi.PackedBatch([_locus(rng, 701, 4, 6, hap_len=40), _locus(rng, 201, 4, 6)])
+    sc = _lib.debug_plan_schedule(short, _grids(), n_cu=1, chain=1)
+    assert sc["max_len"] == 201 and [(e["kind"], e["W"]) for e in sc["entries"]] == [(0, 11), (1, 7)] and chained(sc) == [0, 1]
+
+
+def test_schedule_without_work_for_the_plan_kernel_falls_back_to_the_exact_launches():
+    rng = np.random.default_rng(25)
+    # a small batch (it cannot fill 256 CUs) with few long pairs: 1400 columns on four-wave workgroups, strips of 6 columns
+    wg = _locus(rng, 1401, 3, 2)
+    n_read = _locus(rng, 201, 1, 2)
+    n_read[0][0] = n_read[0][0][:5] + b"N" + n_read[0][0][6:]
+    s = _lib.debug_plan_schedule(_abi.PackedBatch([wg, n_read]), _grids(), n_cu=256)
+    assert not s["use_plan"] and not s["entries"] and s["n_tabs"] == 0
+    assert [(l["kind"], l["W"], l["cmax"], l["pairs"], l["grid"], l["members"]) for l in s["launches"]] == [("workgroup", 6, 1400, 6, 6, [])]
+    assert class_info(s["launches"][0]["cls"])["lanes"] == 256 and s["by_class"] == s["launches"]
+    # the two starters are the generic exact launch's; a failed certificate of the workgroup pairs lands in the four-wave list
+    assert s["xcand"].tolist() == [2, 0, 0, 0, 6, 0] and s["x_grid"].tolist() == [1, 0, 0, 0, 6, 0]
+    # with one pair for it the plan kernel takes the starters: they leave the exact launches' sizes
+    s = _lib.debug_plan_schedule(_abi.PackedBatch([wg, n_read, _locus(rng, 201, 1, 1)]), _grids(), n_cu=256)
+    assert s["use_plan"] and s["xcand"].tolist() == [0, 0, 0, 0, 6, 0] and [e["kind"] for e in s["entries"]] == [2, 0]
+    assert [l["kind"] for l in s["launches"]] == ["workgroup", "plan"]
+
+
+def test_schedule_grid_cap_lowers_the_strip_launches_only():
+    rng = np.random.default_rng(26)
+    # 100 one-wave pairs (a small batch keeps one pair per wavefront) = 25 workgroups; ten workgroup pairs = 10 workgroups
+    batch = _abi.PackedBatch([_locus(rng, 301, 10, 10), _locus(rng, 1401, 5, 2)])
+    for kw, kind in ((dict(), "plan"), (dict(plan_kernel=1, no_multi=1), "one-wave")):
+        s = _lib.debug_plan_schedule(batch, _grids(), n_cu=256, **kw)
+        assert [(l["kind"], l["grid"]) for l in s["launches"]] == [("workgroup", 10), (kind, 25)] and s["max_grid"] == 25
+        c = _lib.debug_plan_schedule(batch, _grids(), n_cu=256, cap=7, **kw)
+        assert [(l["kind"], l["grid"]) for l in c["launches"]] == [("workgroup", 10), (kind, 7)] and c["max_grid"] == 7
+        assert all(l["grid"] == (10 if l["kind"] == "workgroup" else 7) for l in c["by_class"])
+        assert [{**l, "grid": 0} for l in c["launches"]] == [{**l, "grid": 0} for l in s["launches"]]       # nothing else moves
+        # the exact launches that park column blocks in strips are capped, the workgroup lists are not
+        assert (c["x_grid"][:4] == np.minimum(s["x_grid"][:4], 7)).all() and (c["x_grid"][4:] == s["x_grid"][4:]).all()
+        big = _lib.debug_plan_schedule(batch, _grids(), n_cu=256, cap=40, **kw)
+        assert big["launches"] == s["launches"] and big["max_grid"] == 25
