@@ -505,8 +505,8 @@ int64_t ltr_extract_sequence(const ltr_read_set* rs, int32_t i, int32_t region_s
  * the reads: HaplotypeGenerator::add_haplotype_block (:530-578: region padded by indel_flank_len, candidate
  * alleles by the exact-sequence rules of gen_candidate_seqs :295-373, sorted and trimmed :474-480, :14-82) and
  * fuse_haplotype_blocks (:580-607) -> [flank <= 35 bp][repeat block][flank <= 35 bp].  The partial-order-alignment
- * clustering of reads without a candidate (:376-472, spoa) is NOT performed; the result says how many reads /
- * samples the reference would have clustered.  ctx may be NULL (it only receives the hap-build time).
+ * clustering of reads without a candidate (:376-472, spoa) is NOT performed here (ltr_build_haplotypes_clustered below
+ * does it, with medoids for the consensus); the result says how many reads / samples the reference would have clustered.  ctx may be NULL (it only receives the hap-build time).
  * A failed construction (the reference's failure_msg_) is not an error status: blocks() is NULL, failure() the text.
  */
 typedef struct ltr_hap_result ltr_hap_result;
@@ -530,6 +530,79 @@ const char* ltr_hap_result_failure(const ltr_hap_result* r);
 int32_t     ltr_hap_result_unplaced_reads(const ltr_hap_result* r);
 int32_t     ltr_hap_result_samples_needing_clustering(const ltr_hap_result* r);
 void        ltr_hap_result_free(ltr_hap_result* r);
+
+/* ---- reads without an exact allele: clustered into inexact candidate alleles (GPU distances, host clustering) -------- */
+/*
+ * The distance of HaplotypeGenerator::needleman_wunsch (HaplotypeGenerator.cpp:201-234: unit costs, bytes compared for
+ * equality as at :223 -- 'N' equals 'N', nothing is case-folded) for ALL pairs of every group of sequences, capped:
+ *   dist + dist_off[g]   U_g x U_g int32, row-major, symmetric, zero diagonal; entry = min(levenshtein(a, b), cap)
+ * with 1 <= cap <= 32767.  Empty sequences are legal (d("", x) = len(x)).  Only i < j is computed and the result mirrored; a pair
+ * with |n - m| >= cap (and a pair with an empty side) is written by the host and never launched; a group of at most one
+ * sequence launches nothing.  A sequence belongs to at most one group, and the bytes of a group are remapped to at most 32
+ * codes: a group with more distinct bytes is LTR_ERR_INVALID.  Every error is LTR_ERR_INVALID + ltr_last_error naming the
+ * group; then nothing is launched and dist is untouched.  The kernel is the bit-vector block algorithm (Myers 1999 / Hyyro),
+ * ltr_editdist.hip; the cap is applied to the result only.  No CPU fallback: without a context LTR_ERR_NO_DEVICE.
+ */
+typedef struct ltr_seq_groups {
+  int64_t        n_groups;
+  const int64_t* group_seq_off;   /* [n_groups+1] first sequence of each group */
+  int64_t        n_seqs;
+  const uint8_t* seq_bytes;       /* concatenated */
+  const int64_t* seq_off;         /* [n_seqs+1] */
+} ltr_seq_groups;
+int ltr_edit_distances(ltr_ctx* ctx, const ltr_seq_groups* sg, int32_t cap, int32_t* dist, const int64_t* dist_off);
+/*
+ * The clustering of gen_candidate_seqs (:399-470) for ONE sample, as a function of its U unique unplaced sequences (any order,
+ * no duplicates), how many reads carry each, their distance matrix capped at 701 (ltr_edit_distances; host code, no GPU) and
+ * the candidate alleles present so far:
+ *   order        the lexicographically first sequence first (the first std::map key, :400-402), the rest by
+ *                orderByLengthAndSequence (:403)
+ *   ladder       T in {20,50,80,100,150,200,300,400,500,600,700} (:405); the first T that passes the coverage rule ends it
+ *   greedy_clustering (:237-268)  sequence against the centroids in creation order, the smallest score < T (first on ties),
+ *                a 16th centroid fails the threshold
+ *   score < T    decided from the matrix: needleman_wunsch(a, b, score, T) has score < T <=> d(a, b) < T for T <= 700.  ONE
+ *                EXCEPTION, reproduced by argument position in the greedy step and in merge_clusters: with an empty second
+ *                argument (the centroid) and a non-empty first, the reference's inner loop never runs and it answers T + 1
+ *   refinement (:418-440)  DEVIATION: where the reference takes the partial-order-alignment consensus (poa, :427) the cluster's
+ *                MEDOID stands in -- the member x minimising sum_y count[y] * dist[x][y] over the members, ties to the earlier in
+ *                length-then-sequence order; clusters in std::map order of their centroid, new centroids sorted from the
+ *                second on (:437), merge_clusters (:271-293) with j from 1, (centroid i, centroid j) argument order; until
+ *                no merge happens
+ *   acceptance (:446-469)  a cluster counts when its reads are > min((int)(0.10 * ignored), 10); T passes when the counted
+ *                reads are >= (int)(0.80 * ignored); the counted centroids that are no candidate yet are the new alleles
+ * Result: threshold (accepted T or -1: then no clusters), the clusters in std::map order of their centroid -- centroids and
+ * members as indices into the caller's sequences --, counted[c], new_allele[c].  Free with ltr_cluster_result_free.
+ */
+typedef struct ltr_cluster_result ltr_cluster_result;
+int ltr_cluster_sequences(const uint8_t* seq_bytes, const int64_t* seq_off, const int32_t* counts, int32_t n_seqs, const int32_t* dist,
+                          const uint8_t* cand_bytes, const int64_t* cand_off, int32_t n_cands, ltr_cluster_result** out);
+int32_t        ltr_cluster_result_threshold(const ltr_cluster_result* r);
+int32_t        ltr_cluster_result_n_clusters(const ltr_cluster_result* r);
+const int32_t* ltr_cluster_result_centroids(const ltr_cluster_result* r);       /* [n_clusters] */
+const uint8_t* ltr_cluster_result_new_allele(const ltr_cluster_result* r);      /* [n_clusters] */
+const uint8_t* ltr_cluster_result_counted(const ltr_cluster_result* r);         /* [n_clusters] */
+const int32_t* ltr_cluster_result_members(const ltr_cluster_result* r, int32_t cluster, int32_t* n);
+void           ltr_cluster_result_free(ltr_cluster_result* r);
+/*
+ * ltr_build_haplotype for many loci WITH the clustering step (:376-472), in three phases: A (worker pool) everything
+ * ltr_build_haplotype does up to :372, and per sample with ignored > 0.25 * reads (:392) its unique unplaced sequences; B ONE
+ * ltr_edit_distances launch set over all those groups, cap 701; C (worker pool) per locus the samples in order (:398), each
+ * through ltr_cluster_sequences against the candidates so far (:457-458), then the sort (:475, the inexact flag travels with
+ * its sequence), trim and fuse as in ltr_build_haplotype.  The cluster centres are medoids (see above), flagged inexact
+ * (INEXACT_ALLELE=1).  A failed construction stays a text in the result; an error status leaves every out[l] NULL.
+ * unplaced_reads / samples_needing_clustering keep their meaning (what was found before clustering).  A locus where no sample
+ * needs clustering comes out byte-identical to ltr_build_haplotype.
+ *   ltr_hap_result_inexact            [alleles of the repeat block] 1 = a cluster centre (NULL for a failed construction)
+ *   ltr_hap_result_cluster_threshold  the sample's accepted T, -1 none passed, 0 clustering not needed
+ */
+typedef struct ltr_hap_build_locus {
+  const ltr_read_set* rs; int32_t n_samples, region_start, region_stop, period;
+  const uint8_t* chrom_seq; int64_t chrom_seq_start, chrom_seq_len, chrom_len;
+} ltr_hap_build_locus;
+int ltr_build_haplotypes_clustered(ltr_ctx* ctx, const ltr_hap_build_locus* loci, int64_t n_loci, int32_t indel_flank_len,
+                                   ltr_hap_result** out /* [n_loci] */);
+const uint8_t* ltr_hap_result_inexact(const ltr_hap_result* r);
+int32_t        ltr_hap_result_cluster_threshold(const ltr_hap_result* r, int32_t sample);
 
 /* ---- neighbour of the path: haplotype -> reference-haplotype alignment (GPU) -------- */
 /*

@@ -176,6 +176,20 @@ class LlBatch(C.Structure):
                 ("n_haps", C.POINTER(C.c_int32))]
 
 
+class SeqGroups(C.Structure):
+    """struct ltr_seq_groups."""
+
+    _fields_ = [("n_groups", C.c_int64), ("group_seq_off", C.POINTER(C.c_int64)), ("n_seqs", C.c_int64), ("seq_bytes", C.POINTER(C.c_uint8)),
+                ("seq_off", C.POINTER(C.c_int64))]
+
+
+class HapBuildLocus(C.Structure):
+    """struct ltr_hap_build_locus."""
+
+    _fields_ = [("rs", C.c_void_p), ("n_samples", C.c_int32), ("region_start", C.c_int32), ("region_stop", C.c_int32), ("period", C.c_int32),
+                ("chrom_seq", C.POINTER(C.c_uint8)), ("chrom_seq_start", C.c_int64), ("chrom_seq_len", C.c_int64), ("chrom_len", C.c_int64)]
+
+
 class LocusFields(C.Structure):
     """struct ltr_locus_fields."""
 

@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("LTR_GPU_LIB") or os.path.join(CSRC, "libltr_gpu.so")   # override: A/B builds only
 KERNEL_TUS = ["ltr_k_one.hip", "ltr_k_pack.hip", "ltr_k_plan.hip", "ltr_k_wg.hip", "ltr_k_wgt.hip", "ltr_k_exact.hip", "ltr_plan.cpp"]      # one family of DP kernels each
-SOURCES = ["ltr_ctx.hip", "ltr_plan_build.hip", "ltr_plan_run.hip", "ltr_posterior.hip", "ltr_plan_genotype.hip", "ltr_plan_fields.hip"] + KERNEL_TUS + ["ltr_short.hip", "ltr_nw.hip", "ltr_host.cpp", "ltr_genotype.cpp", "ltr_vcf.cpp", "ltr_prep.cpp", "ltr_io.cpp", "ltr_bam.cpp", "ltr_vcf_in.cpp"]
+SOURCES = ["ltr_ctx.hip", "ltr_plan_build.hip", "ltr_plan_run.hip", "ltr_posterior.hip", "ltr_plan_genotype.hip", "ltr_plan_fields.hip"] + KERNEL_TUS + ["ltr_short.hip", "ltr_nw.hip", "ltr_host.cpp", "ltr_genotype.cpp", "ltr_vcf.cpp", "ltr_prep.cpp", "ltr_io.cpp", "ltr_bam.cpp", "ltr_vcf_in.cpp", "ltr_editdist.hip", "ltr_cluster.cpp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-honor-nans", "-std=c++17", "-fPIC", "-shared", "-pthread", "-Wall"]
 LINK_LIBS = ["-lz"]                                         # BGZF blocks (ltr_bgzf.h: BAM, VCF writer, tabix-indexed VCF input)
 
@@ -48,6 +48,9 @@ EXPORTS = [
     "ltr_plan_genotype_fields", "ltr_genotype_result_fields", "ltr_genotype_result_vcf_records", "ltr_vcf_text_free",
     "ltr_vcf_fields", "ltr_vcf_field_set_view", "ltr_vcf_field_set_free", "ltr_vcf_record_from_fields", "ltr_ll_genotype",
     "ltr_plan_posteriors_ploidy", "ltr_plan_genotype_ploidy", "ltr_ll_genotype_ploidy", "ltr_genotype_result_haploid",
+    "ltr_edit_distances", "ltr_cluster_sequences", "ltr_cluster_result_threshold", "ltr_cluster_result_n_clusters", "ltr_cluster_result_centroids",
+    "ltr_cluster_result_new_allele", "ltr_cluster_result_counted", "ltr_cluster_result_members", "ltr_cluster_result_free",
+    "ltr_build_haplotypes_clustered", "ltr_hap_result_inexact", "ltr_hap_result_cluster_threshold",
 ]
 
 
@@ -434,6 +437,26 @@ class Context:
             lh = _locus_haploid(locus_haploid, len(packed["n_samples"]))
             self._check(L.ltr_ll_genotype_ploidy(self._h, C.byref(packed["lb"]), C.byref(packed["gb"]), pfr, _p(lh), C.byref(h)))
         return GenotypeResult(self, h, packed)
+
+    def edit_distances(self, groups, cap):
+        """ltr_edit_distances: groups = list of lists of bytes; per group the U x U int32 matrix min(levenshtein, cap)."""
+        return edit_distances(self, groups, cap)
+
+    def build_haplotypes_clustered(self, loci, indel_flank_len=5):
+        """ltr_build_haplotypes_clustered.  loci: list of dict(rs=ReadSet, region_start, region_stop, period, chrom_seq_start, chrom_len).
+        Per locus the dict of ReadSet.build_haplotype + inexact (per allele of the repeat block, None for a failed construction)
+        + cluster_threshold (per sample: accepted T, -1 none, 0 not needed)."""
+        L = lib()
+        L.ltr_build_haplotypes_clustered.argtypes = [C.c_void_p, C.POINTER(_abi.HapBuildLocus), C.c_int64, C.c_int32, C.POINTER(C.c_void_p)]
+        arr = (_abi.HapBuildLocus * max(len(loci), 1))()
+        for i, l in enumerate(loci):
+            rs = l["rs"]
+            arr[i].rs, arr[i].n_samples, arr[i].region_start, arr[i].region_stop, arr[i].period = rs._h, rs.n_samples, l["region_start"], l["region_stop"], l["period"]
+            arr[i].chrom_seq = rs.chrom.ctypes.data_as(C.POINTER(C.c_uint8))
+            arr[i].chrom_seq_start, arr[i].chrom_seq_len, arr[i].chrom_len = l["chrom_seq_start"], len(rs.chrom), l["chrom_len"]
+        out = (C.c_void_p * max(len(loci), 1))()
+        self._check(L.ltr_build_haplotypes_clustered(self._h, arr, len(loci), int(indel_flank_len), out))
+        return [_hap_result(C.c_void_p(out[i]), n_samples=l["rs"].n_samples) for i, l in enumerate(loci)]
 
     def close(self):
         if self._h:
@@ -1380,8 +1403,84 @@ def prune_hap_blocks(blocks, block, unused):
     return _hap_result(h)["blocks"]
 
 
-def _hap_result(h):
-    """An ltr_hap_result as dict(blocks=[...] or None, failure, unplaced_reads, samples_needing_clustering); frees it."""
+def pack_seq_groups(groups):
+    """ctypes image of an ltr_seq_groups for a list of lists of bytes (+ the offsets of the U x U matrices and their total size)."""
+    flat = [bytes(s) for g in groups for s in g]
+    seq_off = np.zeros(len(flat) + 1, dtype=np.int64)
+    seq_off[1:] = np.cumsum([len(s) for s in flat]) if flat else []
+    gso = np.zeros(len(groups) + 1, dtype=np.int64)
+    gso[1:] = np.cumsum([len(g) for g in groups]) if groups else []
+    raw = np.frombuffer(b"".join(flat) or b"\0", dtype=np.uint8).copy()
+    dist_off = np.zeros(len(groups) + 1, dtype=np.int64)
+    dist_off[1:] = np.cumsum([len(g) * len(g) for g in groups]) if groups else []
+    sg = _abi.SeqGroups()
+    sg.n_groups, sg.n_seqs = len(groups), len(flat)
+    sg.group_seq_off, sg.seq_off = gso.ctypes.data_as(C.POINTER(C.c_int64)), seq_off.ctypes.data_as(C.POINTER(C.c_int64))
+    sg.seq_bytes = raw.ctypes.data_as(C.POINTER(C.c_uint8))
+    return dict(sg=sg, dist_off=dist_off, keep=(raw, seq_off, gso))
+
+
+def edit_distances(ctx, groups, cap, dist=None, packed=None):
+    """ltr_edit_distances (ctx None: the call without a context, LTR_ERR_NO_DEVICE).  dist: optional int32 array the matrices are
+    written into (left as it is on an error).  Returns the list of U x U matrices (views of one array)."""
+    L = lib()
+    L.ltr_edit_distances.argtypes = [C.c_void_p, C.POINTER(_abi.SeqGroups), C.c_int32, C.c_void_p, C.c_void_p]
+    pk = packed or pack_seq_groups(groups)
+    off = pk["dist_off"]
+    if dist is None:
+        dist = np.full(max(int(off[-1]), 1), -1, dtype=np.int32)
+    rc = L.ltr_edit_distances(None if ctx is None else ctx._h, C.byref(pk["sg"]), int(cap), _p(dist), _p(off))
+    if rc != 0:
+        raise LtrError(rc, lib().ltr_last_error(ctx._h).decode() if ctx is not None else "ltr_edit_distances")
+    out = []
+    for g in range(len(off) - 1):
+        u = int(round((off[g + 1] - off[g]) ** 0.5))
+        out.append(dist[off[g]:off[g + 1]].reshape(u, u))
+    return out
+
+
+def cluster_sequences(seqs, counts, dist, candidates=()):
+    """ltr_cluster_sequences (host, no GPU): dict(threshold, clusters=[dict(centroid, members, counted, new_allele)...])."""
+    L = lib()
+    L.ltr_cluster_sequences.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
+    for f, rt in (("threshold", C.c_int32), ("n_clusters", C.c_int32), ("centroids", C.POINTER(C.c_int32)), ("new_allele", C.POINTER(C.c_uint8)),
+                  ("counted", C.POINTER(C.c_uint8))):
+        fn = getattr(L, "ltr_cluster_result_" + f)
+        fn.argtypes, fn.restype = [C.c_void_p], rt
+    L.ltr_cluster_result_members.argtypes, L.ltr_cluster_result_members.restype = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)], C.POINTER(C.c_int32)
+    L.ltr_cluster_result_free.argtypes, L.ltr_cluster_result_free.restype = [C.c_void_p], None
+
+    def pack(strings):
+        raw = [bytes(s) for s in strings]
+        off = np.zeros(len(raw) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(s) for s in raw]) if raw else []
+        return np.frombuffer(b"".join(raw) or b"\0", dtype=np.uint8).copy(), off
+    sb, so = pack(seqs)
+    cb, co = pack(candidates)
+    cnt = np.ascontiguousarray(counts, dtype=np.int32)
+    d = np.ascontiguousarray(dist, dtype=np.int32)
+    if len(cnt) != len(seqs) or d.size != len(seqs) ** 2:
+        raise LtrError(_abi.LTR_ERR_INVALID, "cluster_sequences: one count per sequence and a U x U matrix")
+    h = C.c_void_p()
+    rc = L.ltr_cluster_sequences(_p(sb), _p(so), _p(cnt), len(seqs), _p(d), _p(cb), _p(co), len(candidates), C.byref(h))
+    if rc != 0:
+        raise LtrError(rc, "ltr_cluster_sequences")
+    try:
+        n = L.ltr_cluster_result_n_clusters(h)
+        ce, nw, ct = L.ltr_cluster_result_centroids(h), L.ltr_cluster_result_new_allele(h), L.ltr_cluster_result_counted(h)
+        clusters = []
+        for c in range(n):
+            k = C.c_int32(0)
+            m = L.ltr_cluster_result_members(h, c, C.byref(k))
+            clusters.append(dict(centroid=ce[c], members=[m[i] for i in range(k.value)], counted=bool(ct[c]), new_allele=bool(nw[c])))
+        return dict(threshold=L.ltr_cluster_result_threshold(h), clusters=clusters)
+    finally:
+        L.ltr_cluster_result_free(h)
+
+
+def _hap_result(h, n_samples=None):
+    """An ltr_hap_result as dict(blocks=[...] or None, failure, unplaced_reads, samples_needing_clustering); frees it.
+    n_samples given (ltr_build_haplotypes_clustered): + inexact, cluster_threshold."""
     L = lib()
     L.ltr_hap_result_blocks.argtypes, L.ltr_hap_result_blocks.restype = [C.c_void_p], C.POINTER(_abi.HaplotypeBlocks)
     L.ltr_hap_result_failure.argtypes, L.ltr_hap_result_failure.restype = [C.c_void_p], C.c_char_p
@@ -1401,6 +1500,12 @@ def _hap_result(h):
                 k += 1
             blocks.append(dict(start=b.block_start[i], end=b.block_end[i], is_repeat=bool(b.is_repeat[i]), period=b.period[i], alleles=al))
         out["blocks"] = blocks
+    if n_samples is not None:
+        L.ltr_hap_result_inexact.argtypes, L.ltr_hap_result_inexact.restype = [C.c_void_p], C.POINTER(C.c_uint8)
+        L.ltr_hap_result_cluster_threshold.argtypes = [C.c_void_p, C.c_int32]
+        ip = L.ltr_hap_result_inexact(h)
+        out["inexact"] = [int(ip[i]) for i in range(len(out["blocks"][1]["alleles"]))] if (ip and out["blocks"]) else None
+        out["cluster_threshold"] = [L.ltr_hap_result_cluster_threshold(h, s) for s in range(n_samples)]
     L.ltr_hap_result_free(h)
     return out
 

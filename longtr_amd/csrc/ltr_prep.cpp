@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "ltr_internal.h"
+#include "ltr_prep.h"
 
 namespace {
 
@@ -144,8 +145,6 @@ bool extract_sequence(const PreparedRead& a, int32_t region_start, int32_t regio
   return false;
 }
 
-bool by_len_seq(const std::string& x, const std::string& y) { return x.size() != y.size() ? x.size() < y.size() : x.compare(y) < 0; }
-
 // HaplotypeGenerator::trim (:14-82): clip what all candidates share at either end, down to ideal_min_length
 void trim_candidates(int ideal_min_length, int left_pad, int right_pad, int32_t& region_start, int32_t& region_end, std::vector<std::string>& seqs) {
   int min_len = INT_MAX;
@@ -190,14 +189,123 @@ struct ltr_read_set {
   int32_t fail_count = 0;
 };
 
-struct ltr_hap_result {
-  std::vector<int32_t> bstart, bend, period, nall;
-  std::vector<uint8_t> is_rep, bytes, inexact;
-  std::vector<int64_t> off;
-  ltr_haplotype_blocks view;
-  std::string failure;
-  int32_t unplaced = 0, needs_clustering = 0;
-};
+namespace ltr {
+
+bool by_len_seq(const std::string& x, const std::string& y) { return x.size() != y.size() ? x.size() < y.size() : x.compare(y) < 0; }
+
+int hap_draft(const ltr_read_set* rs, int32_t n_samples, int32_t region_start, int32_t region_stop, int32_t period, const uint8_t* chrom_seq,
+              int64_t chrom_seq_start, int64_t chrom_seq_len, int64_t chrom_len, int32_t indel_flank_len, HapDraft* d) {
+  const Chrom chrom{chrom_seq, chrom_seq_start, chrom_seq_len};
+  const int kRefFlank = 35;                                    // HaplotypeGenerator.h:64-75
+  const double MIN_FRAC_READS = 0.05, MIN_FRAC_SAMPLES = 0.05, MIN_FRAC_STRONG_SAMPLE = 0.2, MIN_READS_STRONG_SAMPLE = 2, MIN_STRONG_SAMPLES = 1;
+  const int LEFT_PAD = indel_flank_len, RIGHT_PAD = indel_flank_len;
+  d->pad = indel_flank_len; d->period = period;
+  auto fail = [&](const char* msg) { d->failure = msg; return LTR_OK; };
+  int32_t min_aln_start = INT_MAX, max_aln_stop = INT_MIN;    // :421-426 over ALL reads
+  for (const PreparedRead& p : rs->reads) { min_aln_start = std::min(min_aln_start, p.start); max_aln_stop = std::max(max_aln_stop, p.stop); }
+  d->min_aln_start = min_aln_start; d->max_aln_stop = max_aln_stop;
+  // add_haplotype_block, :530-578
+  if (region_start < kRefFlank + LEFT_PAD || (int64_t)region_stop + kRefFlank + RIGHT_PAD > chrom_len) return fail("Haplotype blocks are too near to the chromosome ends");
+  int32_t gmin = INT_MAX, gmax = INT_MIN;                     // get_aln_bounds over the reads used for haplotype generation
+  for (const PreparedRead& p : rs->reads) if (p.use_for_hap_gen) { gmin = std::min(gmin, p.start); gmax = std::max(gmax, p.stop); }
+  const int32_t rstart = region_start - LEFT_PAD, rend = region_stop + RIGHT_PAD;
+  d->rstart = rstart; d->rend = rend;
+  const std::string ref_seq = chrom.sub_upper(rstart, rend - rstart);
+  if ((int64_t)gmin + 5 >= rstart || (int64_t)gmax - 5 <= rend) return fail("No spanning alignments");
+  d->ideal_min_length = 3 * period;
+  // gen_candidate_seqs, :295-373
+  std::map<std::string, double> sample_counts;
+  std::map<std::string, int> read_counts, must_inc;
+  int tot_reads = 0, tot_samples = 0;
+  std::vector<std::vector<std::string>>& per_sample = d->per_sample;
+  per_sample.assign((size_t)n_samples, {});
+  for (const PreparedRead& p : rs->reads) {
+    if (!p.use_for_hap_gen) continue;
+    if (p.sample < 0 || p.sample >= n_samples) return LTR_ERR_INVALID;
+    std::string sub; bool bad = false;
+    if (extract_sequence(p, rstart, rend, sub, &bad)) per_sample[(size_t)p.sample].push_back(sub);
+    else if (bad) return LTR_ERR_CIGAR;
+  }
+  for (int s = 0; s < n_samples; ++s) {
+    std::map<std::string, int> counts;
+    const int samp_reads = (int)per_sample[(size_t)s].size();
+    for (const std::string& sub : per_sample[(size_t)s]) { read_counts[sub] += 1; counts[sub] += 1; ++tot_reads; }
+    for (const auto& kv : counts) {                           // :318-322
+      if (kv.second >= MIN_READS_STRONG_SAMPLE && kv.second >= MIN_FRAC_STRONG_SAMPLE * samp_reads) must_inc[kv.first] += 1;
+      sample_counts[kv.first] += kv.second * 1.0 / samp_reads;
+    }
+    if (samp_reads > 0) ++tot_samples;
+  }
+  std::vector<std::string>& seqs = d->seqs;
+  int ref_index = -1;
+  for (const auto& kv : must_inc) {                           // :345-356 alleles with strong support in some sample
+    if (kv.second >= MIN_STRONG_SAMPLES) {
+      sample_counts.erase(kv.first); read_counts.erase(kv.first);
+      seqs.push_back(kv.first);
+      if (kv.first == ref_seq) ref_index = (int)seqs.size() - 1;
+    }
+  }
+  for (const auto& kv : sample_counts) {                      // :359-365 alleles above the global thresholds
+    if (kv.second > MIN_FRAC_SAMPLES * tot_samples * 2 || read_counts[kv.first] > MIN_FRAC_READS * tot_reads * 2) {
+      seqs.push_back(kv.first);
+      if (ref_index == -1 && kv.first == ref_seq) ref_index = (int)seqs.size() - 1;
+    }
+  }
+  if (ref_index == -1) seqs.insert(seqs.begin(), ref_seq);    // :368-373 reference first
+  else { seqs[(size_t)ref_index] = seqs[0]; seqs[0] = ref_seq; }
+  // :376-395: reads without a candidate, per sample
+  d->ignored.assign((size_t)n_samples, 0);
+  for (int s = 0; s < n_samples; ++s) {
+    int ignored = 0;
+    for (const std::string& sub : per_sample[(size_t)s]) if (std::find(seqs.begin(), seqs.end(), sub) == seqs.end()) ++ignored;
+    d->ignored[(size_t)s] = ignored;
+    d->unplaced += ignored;
+    if (ignored > (int)per_sample[(size_t)s].size() * 0.25) d->needs_clustering++;      // :392
+  }
+  return LTR_OK;
+}
+
+int hap_finish(const HapDraft& d, std::vector<std::string> seqs, std::vector<uint8_t> inexact, const uint8_t* chrom_seq, int64_t chrom_seq_start,
+               int64_t chrom_seq_len, int64_t chrom_len, ltr_hap_result** out) {
+  const Chrom chrom{chrom_seq, chrom_seq_start, chrom_seq_len};
+  const int kRefFlank = 35;
+  std::unique_ptr<ltr_hap_result> owner(new ltr_hap_result());   // released into *out on the LTR_OK paths only: an error or an exception leaves *out NULL
+  ltr_hap_result* res = owner.get();
+  auto fail = [&](const std::string& msg) { res->failure = msg; std::memset(&res->view, 0, sizeof(res->view)); *out = owner.release(); return LTR_OK; };
+  if (!d.failure.empty()) return fail(d.failure);
+  res->unplaced = d.unplaced; res->needs_clustering = d.needs_clustering;
+  int32_t rstart = d.rstart, rend = d.rend;
+  {                                                             // :475: the flag travels with its sequence
+    std::vector<size_t> order(seqs.size());
+    for (size_t i = 0; i < order.size(); ++i) order[i] = i;
+    std::sort(order.begin() + 1, order.end(), [&](size_t x, size_t y) { return by_len_seq(seqs[x], seqs[y]); });
+    std::vector<std::string> s2; std::vector<uint8_t> f2;
+    for (size_t i : order) { s2.push_back(std::move(seqs[i])); f2.push_back(inexact[i]); }
+    seqs.swap(s2); inexact.swap(f2);
+  }
+  trim_candidates(d.ideal_min_length, d.pad, d.pad, rstart, rend, seqs);   // :480 (positions, and with them the flags, stay)
+  // fuse_haplotype_blocks, :580-607
+  if (rstart < kRefFlank || (int64_t)rend + kRefFlank > chrom_len) return fail("Haplotype blocks are too near to the chromosome ends");
+  const int32_t min_start = std::min(rstart - 10, std::max(rstart - kRefFlank, d.min_aln_start));
+  const int32_t max_stop = std::max(rend + 10, std::min(rend + kRefFlank, d.max_aln_stop));
+  const std::string lflank = chrom.sub_upper(min_start, rstart - min_start), rflank = chrom.sub_upper(rend, max_stop - rend);
+  res->bstart = {min_start, rstart, rend}; res->bend = {rstart, rend, max_stop};
+  res->is_rep = {0, 1, 0}; res->period = {0, d.period, 0}; res->nall = {1, (int32_t)seqs.size(), 1};
+  res->off.push_back(0);
+  auto put = [&](const std::string& s) { res->bytes.insert(res->bytes.end(), s.begin(), s.end()); res->off.push_back((int64_t)res->bytes.size()); };
+  put(lflank);
+  for (const std::string& s : seqs) put(s);
+  put(rflank);
+  if (res->bytes.empty()) res->bytes.push_back(0);
+  res->inexact = inexact;
+  res->view.n_blocks = 3; res->view.block_start = res->bstart.data(); res->view.block_end = res->bend.data();
+  res->view.is_repeat = res->is_rep.data(); res->view.period = res->period.data(); res->view.n_alleles = res->nall.data();
+  res->view.allele_bytes = res->bytes.data(); res->view.allele_off = res->off.data();
+  *out = owner.release();
+  return LTR_OK;
+}
+
+}  // namespace ltr
 
 extern "C" {
 
@@ -304,7 +412,7 @@ int64_t ltr_extract_sequence(const ltr_read_set* rs, int32_t i, int32_t region_s
 
 // SeqStutterGenotyper::build_haplotype (seq_stutter_genotyper.cpp:416-482) for one region, alleles from the reads:
 // add_haplotype_block (gen_candidate_seqs' exact-allele rules, trim) + fuse_haplotype_blocks -> three blocks
-// [reference flank][repeat block with candidate alleles][reference flank].
+// [reference flank][repeat block with candidate alleles][reference flank].  (hap_draft + hap_finish: the two halves, above)
 int ltr_build_haplotype(ltr_ctx* ctx, const ltr_read_set* rs, int32_t n_samples, int32_t region_start, int32_t region_stop, int32_t period,
                         const uint8_t* chrom_seq, int64_t chrom_seq_start, int64_t chrom_seq_len, int64_t chrom_len,
                         int32_t indel_flank_len, ltr_hap_result** out) {
@@ -312,91 +420,11 @@ int ltr_build_haplotype(ltr_ctx* ctx, const ltr_read_set* rs, int32_t n_samples,
   *out = nullptr;
   ltr::TimedCall timed(ctx, ltr::kTimerHapBuild);              // total_hap_build_time_ (:417, :479-480); ctx may be NULL
   try {
-    const Chrom chrom{chrom_seq, chrom_seq_start, chrom_seq_len};
-    const int kRefFlank = 35, kMinFracReads_x100 = 5;          // HaplotypeGenerator.h:64-75
-    const double MIN_FRAC_READS = 0.05, MIN_FRAC_SAMPLES = 0.05, MIN_FRAC_STRONG_SAMPLE = 0.2, MIN_READS_STRONG_SAMPLE = 2, MIN_STRONG_SAMPLES = 1;
-    (void)kMinFracReads_x100;
-    const int LEFT_PAD = indel_flank_len, RIGHT_PAD = indel_flank_len;
-    std::unique_ptr<ltr_hap_result> owner(new ltr_hap_result());   // released into *out on the LTR_OK paths only: an error or an exception leaves *out NULL
-    ltr_hap_result* res = owner.get();
-    auto fail = [&](const char* msg) { res->failure = msg; std::memset(&res->view, 0, sizeof(res->view)); *out = owner.release(); return LTR_OK; };
-    int32_t min_aln_start = INT_MAX, max_aln_stop = INT_MIN;    // :421-426 over ALL reads
-    for (const PreparedRead& p : rs->reads) { min_aln_start = std::min(min_aln_start, p.start); max_aln_stop = std::max(max_aln_stop, p.stop); }
-    // add_haplotype_block, :530-578
-    if (region_start < kRefFlank + LEFT_PAD || (int64_t)region_stop + kRefFlank + RIGHT_PAD > chrom_len) return fail("Haplotype blocks are too near to the chromosome ends");
-    int32_t gmin = INT_MAX, gmax = INT_MIN;                     // get_aln_bounds over the reads used for haplotype generation
-    for (const PreparedRead& p : rs->reads) if (p.use_for_hap_gen) { gmin = std::min(gmin, p.start); gmax = std::max(gmax, p.stop); }
-    int32_t rstart = region_start - LEFT_PAD, rend = region_stop + RIGHT_PAD;
-    const std::string ref_seq = chrom.sub_upper(rstart, rend - rstart);
-    if ((int64_t)gmin + 5 >= rstart || (int64_t)gmax - 5 <= rend) return fail("No spanning alignments");
-    const int ideal_min_length = 3 * period;
-    // gen_candidate_seqs, :295-373
-    std::map<std::string, double> sample_counts;
-    std::map<std::string, int> read_counts, must_inc;
-    int tot_reads = 0, tot_samples = 0;
-    std::vector<std::vector<std::string>> per_sample((size_t)n_samples);     // extracted sequences per sample (reused below)
-    for (const PreparedRead& p : rs->reads) {
-      if (!p.use_for_hap_gen) continue;
-      if (p.sample < 0 || p.sample >= n_samples) return LTR_ERR_INVALID;
-      std::string sub; bool bad = false;
-      if (extract_sequence(p, rstart, rend, sub, &bad)) per_sample[(size_t)p.sample].push_back(sub);
-      else if (bad) return LTR_ERR_CIGAR;
-    }
-    for (int s = 0; s < n_samples; ++s) {
-      std::map<std::string, int> counts;
-      const int samp_reads = (int)per_sample[(size_t)s].size();
-      for (const std::string& sub : per_sample[(size_t)s]) { read_counts[sub] += 1; counts[sub] += 1; ++tot_reads; }
-      for (const auto& kv : counts) {                           // :318-322
-        if (kv.second >= MIN_READS_STRONG_SAMPLE && kv.second >= MIN_FRAC_STRONG_SAMPLE * samp_reads) must_inc[kv.first] += 1;
-        sample_counts[kv.first] += kv.second * 1.0 / samp_reads;
-      }
-      if (samp_reads > 0) ++tot_samples;
-    }
-    std::vector<std::string> seqs;
-    int ref_index = -1;
-    for (const auto& kv : must_inc) {                           // :345-356 alleles with strong support in some sample
-      if (kv.second >= MIN_STRONG_SAMPLES) {
-        sample_counts.erase(kv.first); read_counts.erase(kv.first);
-        seqs.push_back(kv.first);
-        if (kv.first == ref_seq) ref_index = (int)seqs.size() - 1;
-      }
-    }
-    for (const auto& kv : sample_counts) {                      // :359-365 alleles above the global thresholds
-      if (kv.second > MIN_FRAC_SAMPLES * tot_samples * 2 || read_counts[kv.first] > MIN_FRAC_READS * tot_reads * 2) {
-        seqs.push_back(kv.first);
-        if (ref_index == -1 && kv.first == ref_seq) ref_index = (int)seqs.size() - 1;
-      }
-    }
-    if (ref_index == -1) seqs.insert(seqs.begin(), ref_seq);    // :368-373 reference first
-    else { seqs[(size_t)ref_index] = seqs[0]; seqs[0] = ref_seq; }
-    // :376-400: reads without a candidate -- the reference clusters them (POA); reported, not done
-    for (int s = 0; s < n_samples; ++s) {
-      int ignored = 0;
-      for (const std::string& sub : per_sample[(size_t)s]) if (std::find(seqs.begin(), seqs.end(), sub) == seqs.end()) ++ignored;
-      res->unplaced += ignored;
-      if (ignored > (int)per_sample[(size_t)s].size() * 0.25) res->needs_clustering++;
-    }
-    std::sort(seqs.begin() + 1, seqs.end(), by_len_seq);        // :475
-    trim_candidates(ideal_min_length, LEFT_PAD, RIGHT_PAD, rstart, rend, seqs);   // :480
-    // fuse_haplotype_blocks, :580-607
-    if (rstart < kRefFlank || (int64_t)rend + kRefFlank > chrom_len) return fail("Haplotype blocks are too near to the chromosome ends");
-    const int32_t min_start = std::min(rstart - 10, std::max(rstart - kRefFlank, min_aln_start));
-    const int32_t max_stop = std::max(rend + 10, std::min(rend + kRefFlank, max_aln_stop));
-    const std::string lflank = chrom.sub_upper(min_start, rstart - min_start), rflank = chrom.sub_upper(rend, max_stop - rend);
-    res->bstart = {min_start, rstart, rend}; res->bend = {rstart, rend, max_stop};
-    res->is_rep = {0, 1, 0}; res->period = {0, period, 0}; res->nall = {1, (int32_t)seqs.size(), 1};
-    res->off.push_back(0);
-    auto put = [&](const std::string& s) { res->bytes.insert(res->bytes.end(), s.begin(), s.end()); res->off.push_back((int64_t)res->bytes.size()); };
-    put(lflank);
-    for (const std::string& s : seqs) put(s);
-    put(rflank);
-    if (res->bytes.empty()) res->bytes.push_back(0);
-    res->inexact.assign(seqs.size(), 0);
-    res->view.n_blocks = 3; res->view.block_start = res->bstart.data(); res->view.block_end = res->bend.data();
-    res->view.is_repeat = res->is_rep.data(); res->view.period = res->period.data(); res->view.n_alleles = res->nall.data();
-    res->view.allele_bytes = res->bytes.data(); res->view.allele_off = res->off.data();
-    *out = owner.release();
-    return LTR_OK;
+    ltr::HapDraft d;
+    const int rc = ltr::hap_draft(rs, n_samples, region_start, region_stop, period, chrom_seq, chrom_seq_start, chrom_seq_len, chrom_len, indel_flank_len, &d);
+    if (rc != LTR_OK) return rc;
+    // :376-400: reads without a candidate -- the reference clusters them; reported here, done by ltr_build_haplotypes_clustered
+    return ltr::hap_finish(d, d.seqs, std::vector<uint8_t>(d.seqs.size(), 0), chrom_seq, chrom_seq_start, chrom_seq_len, chrom_len, out);
   } catch (const std::bad_alloc&) { return LTR_ERR_NOMEM; } catch (...) { return LTR_ERR_INVALID; }
 }
 
