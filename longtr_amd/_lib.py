@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("LTR_GPU_LIB") or os.path.join(CSRC, "libltr_gpu.so")   # override: A/B builds only
 KERNEL_TUS = ["ltr_k_one.hip", "ltr_k_pack.hip", "ltr_k_plan.hip", "ltr_k_wg.hip", "ltr_k_wgt.hip", "ltr_k_exact.hip", "ltr_plan.cpp"]      # one family of DP kernels each
-SOURCES = ["ltr_ctx.hip", "ltr_plan_build.hip", "ltr_plan_run.hip", "ltr_posterior.hip", "ltr_plan_genotype.hip", "ltr_plan_fields.hip"] + KERNEL_TUS + ["ltr_short.hip", "ltr_nw.hip", "ltr_host.cpp", "ltr_genotype.cpp", "ltr_vcf.cpp", "ltr_prep.cpp", "ltr_io.cpp", "ltr_bam.cpp", "ltr_vcf_in.cpp", "ltr_editdist.hip", "ltr_cluster.cpp"]
+SOURCES = ["ltr_ctx.hip", "ltr_plan_build.hip", "ltr_plan_run.hip", "ltr_posterior.hip", "ltr_plan_genotype.hip", "ltr_plan_fields.hip"] + KERNEL_TUS + ["ltr_short.hip", "ltr_nw.hip", "ltr_host.cpp", "ltr_hap_aln.cpp", "ltr_genotype.cpp", "ltr_vcf.cpp", "ltr_prep.cpp", "ltr_io.cpp", "ltr_bam.cpp", "ltr_vcf_in.cpp", "ltr_editdist.hip", "ltr_cluster.cpp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-honor-nans", "-std=c++17", "-fPIC", "-shared", "-pthread", "-Wall"]
 LINK_LIBS = ["-lz"]                                         # BGZF blocks (ltr_bgzf.h: BAM, VCF writer, tabix-indexed VCF input)
 
@@ -751,6 +751,21 @@ def debug_plan_schedule(batch, grids, params=None, mode=-1, n_cu=256, plan_kerne
     ents = [dict(zip(("kind", "W", "first", "pairs", "queue_class", "first_wave"), (int(v) for v in entry[i]))) for i in range(int(out[2]))]
     return dict(launches=rows[:int(out[0])], by_class=rows[int(out[0]):], entries=ents, n_tabs=int(out[3]), use_plan=bool(out[4]),
                 max_grid=int(out[5]), max_grid_wide=int(out[6]), max_len=int(out[7]), xcand=out[8:8 + n_exact].copy(), class_first=out[8 + n_exact:].copy(), x_grid=x_grid)
+
+
+def debug_chunk_plan(n_loci, est_cells=0.0, budget=0, chunks=0, chunk_streams=0, chunk_growth=None, prep_ahead=0):
+    """Test hook ltr_debug_chunk_plan (csrc/ltr_internal.h): the chunk rule of ltr_calc_hap_aln_probs on made-up numbers, no GPU.
+    The keywords are the ltr_ctx_set_debug knobs of the same names (chunk_growth=None: not set); budget 0 = the process's.
+    dict(bounds, n_streams, prep_ahead, ahead_threads)."""
+    L = lib()
+    L.ltr_debug_chunk_plan.argtypes = [C.c_int64, C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    knobs = np.asarray([chunks, chunk_streams, chunk_growth or 0.0, chunk_growth is not None, prep_ahead], dtype=np.float64)
+    cap = max(int(chunks), 8) + 2
+    bounds, out = np.zeros(cap, dtype=np.int64), np.zeros(4, dtype=np.int32)
+    rc = L.ltr_debug_chunk_plan(int(n_loci), float(est_cells), _p(knobs), int(budget), _p(bounds), cap, _p(out))
+    if rc != 0:
+        raise LtrError(rc, "ltr_debug_chunk_plan")
+    return dict(bounds=[int(b) for b in bounds[:int(out[0]) + 1]], n_streams=int(out[1]), prep_ahead=bool(out[2]), ahead_threads=int(out[3]))
 
 
 def tbi_parse(tbi_path, max_refs=4096):

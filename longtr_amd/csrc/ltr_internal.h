@@ -1,4 +1,4 @@
-// ltr_internal.h -- shared between the HIP side (ltr_ctx.hip and the units around it, ltr_short.hip, ltr_nw.hip) and the host mirror (ltr_host.cpp).
+// ltr_internal.h -- shared between the HIP side (ltr_ctx.hip and the units around it, ltr_short.hip, ltr_nw.hip) and the host mirror (ltr_host.cpp, ltr_hap_aln.cpp).
 #ifndef LTR_INTERNAL_H_
 #define LTR_INTERNAL_H_
 
@@ -14,6 +14,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include <pthread.h>
@@ -45,7 +46,9 @@ inline int64_t hap_window(int64_t hap_len, int flank, int64_t* pos_out) {
 // 64-core host must not start 8 x 32 of them.  The budget of a PROCESS (the worker pools are per process):
 //   min(CPUs of the affinity mask, cgroup CPU quota rounded up, hardware threads) / ranks on this host, clamped to 1 .. 16.
 // Ranks on this host: the launcher's LOCAL_WORLD_SIZE (torch.distributed.run sets it) unless the caller names the number
-// (ltr_host_threads_rule) or the budget itself (ltr_ctx_set_host_threads).
+// (ltr_host_threads_rule) or the budget itself (ltr_ctx_set_host_threads, the only writer of the setting).  A call reads the budget
+// ONCE (ltr_calc_hap_aln_probs: HapAlnCall::budget) and hands that value to its loops, so a setting changed meanwhile by another
+// thread cannot make two decisions of one call disagree.
 constexpr int kMaxHostThreads = 16;
 constexpr int kPrepAheadMinThreads = 12;      // the chunk pipeline's helper thread pays from here on (profiles/r05/prep_ahead_ab.log: level at ~12)
 
@@ -88,6 +91,7 @@ inline int host_thread_budget() {
   static const int rule = host_threads_rule(0);
   return rule;
 }
+inline int host_thread_budget_or(int n) { return n > 0 ? std::min(n, kMaxHostThreads) : host_thread_budget(); }   // (test hooks: a budget named by the caller)
 
 // Host worker threads, started once per process and parked on a condition variable between jobs
 // (every parallel_for of a plan used to start and join its own 15 threads: ~0.5 ms each, ten times per
@@ -156,12 +160,12 @@ class WorkerPool {
   uint64_t generation_ = 0;
 };
 
-// f(i) for i in [0, n) on up to host_thread_budget() host threads (chunks of `grain` from a shared counter); serial when
-// the range is too short to pay for the hand-over.  (pool, max_threads: see WorkerPool)
+// f(i) for i in [0, n) on up to `threads` host threads (chunks of `grain` from a shared counter); serial when the range is too
+// short to pay for the hand-over.  The cap is the caller's: a call that must see ONE budget from its first loop to its last
+// (ltr_calc_hap_aln_probs) reads host_thread_budget() once and hands that value to every loop.  (which_pool: see WorkerPool)
 template <class F>
-inline void parallel_for(int64_t n, int64_t min_per_thread, F&& f, int64_t grain = 64, int which_pool = 0, int max_threads = kMaxHostThreads) {
-  const int hw = host_thread_budget();
-  const int64_t nt = std::min<int64_t>(std::min<int64_t>(hw, std::max(max_threads, 1)), n / std::max<int64_t>(min_per_thread, 1));
+inline void parallel_for_on(int threads, int64_t n, int64_t min_per_thread, F&& f, int64_t grain = 64, int which_pool = 0) {
+  const int64_t nt = std::min<int64_t>(std::max(threads, 1), n / std::max<int64_t>(min_per_thread, 1));
   if (nt <= 1) { for (int64_t i = 0; i < n; ++i) f(i); return; }
   std::atomic<int64_t> next(0);
   // an exception on a worker thread would end the process (std::terminate): the first one is kept
@@ -190,6 +194,11 @@ inline void parallel_for(int64_t n, int64_t min_per_thread, F&& f, int64_t grain
     for (std::thread& t : th) t.join();
   }
   if (failed.load()) std::rethrow_exception(first_error);
+}
+// ... on up to min(host_thread_budget(), max_threads) threads: the budget as it stands when the loop starts
+template <class F>
+inline void parallel_for(int64_t n, int64_t min_per_thread, F&& f, int64_t grain = 64, int which_pool = 0, int max_threads = kMaxHostThreads) {
+  parallel_for_on(std::min(host_thread_budget(), max_threads), n, min_per_thread, std::forward<F>(f), grain, which_pool);
 }
 
 // Entry points never let an exception cross the C-ABI: LTR_GUARD(ctx, body) maps bad_alloc to
@@ -280,6 +289,28 @@ int short_batch_run(ltr_ctx* ctx, ShortBatch* b);
 // Haplotype::next() order (reference Haplotype.cpp:123-196): allele index per block for
 // every combination, combination-major.
 int haplotype_counts(const ltr_haplotype_blocks* hap, std::vector<int32_t>* counts, int64_t* ncombs);
+
+// Per-locus primitives of ltr_host.cpp that ltr_process_reads and the many-locus call (ltr_hap_aln.cpp) share.
+int64_t allele_slot(const ltr_haplotype_blocks* hap, int block, int allele);
+int trim_alignment_into(const ltr_alignment* aln, int32_t repeat_start, int32_t repeat_end, int32_t padding, int32_t* rem /* n_cigar ints */,
+                        int32_t* ltrim_out, int32_t* rtrim_out);
+const char* trim_error_text(int rc);
+constexpr const char* kBadAlignmentRecord = "alignment with a negative length or a null sequence / CIGAR pointer";
+inline bool alignment_record_ok(const ltr_alignment& a) {
+  return a.seq_len >= 0 && (a.seq_len == 0 || a.seq) && a.n_cigar >= 0 && (a.n_cigar == 0 || (a.cigar_type && a.cigar_num));
+}
+// What stands in for a read whose trim is empty: the last 5 bp of the first block's reference allele + the first 5 bp of the last
+// block's (HapAligner.cpp:820-823).  Its length, -1 when the first block is shorter than 5 bp; its bytes to dst.
+constexpr const char* kShortLeftFlank = "left flank shorter than 5 bp (std::string::substr would throw in the reference)";
+int32_t empty_trim_len(const ltr_haplotype_blocks* hap);
+void write_empty_trim(const ltr_haplotype_blocks* hap, uint8_t* dst);
+// The haplotype strings of a locus in Haplotype::next() order: their number and total length (a status on a malformed block
+// list), and the strings themselves written to bytes + at one after the other, off[h] = where string h starts; returns where the
+// last one ends.  counts: scratch of haplotype_counts.
+int haplotype_sizes(const ltr_haplotype_blocks* hap, std::vector<int32_t>* counts, int64_t* n_haps, int64_t* n_bytes);
+int64_t write_haplotypes(const ltr_haplotype_blocks* hap, int64_t n_haps, std::vector<int32_t>* counts, uint8_t* bytes, int64_t at, int64_t* off);
+// Mate pairs share one row sum (seq_stutter_genotyper.cpp:546-559) in rows [n_reads x n_haps]; read 0 as a second mate: LTR_ERR_INVALID
+int sum_mate_rows(double* rows, int32_t n_reads, int64_t n_haps, const uint8_t* second_mate, const uint8_t* copy_read, const uint8_t* realign_to_hap);
 // ltr_vcf_record_from_fields into a string (ltr_vcf.cpp): the length of the text or a negative status
 int64_t vcf_record_string(const ltr_vcf_locus* v, const ltr_locus_fields* f, const ltr_vcf_options* opt, std::string* text, int32_t* pos);
 
@@ -302,5 +333,8 @@ int remap_haplotypes(const ltr_haplotype_blocks* old_hap, const ltr_haplotype_bl
                      std::vector<uint8_t>* realign);
 
 }  // namespace ltr
+
+// Test hooks of ltr_hap_aln.cpp's chunk rule (tests/test_abi_and_host.py; not part of the ABI of include/ltr_gpu.h): see there.
+extern "C" int ltr_debug_chunk_plan(int64_t n_loci, double est_cells, const double* knobs, int budget, int64_t* bounds, int bounds_cap, int32_t* out);
 
 #endif

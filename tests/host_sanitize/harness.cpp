@@ -1,5 +1,5 @@
 // tests/host_sanitize/harness.cpp -- TEST INFRASTRUCTURE.
-// Fuzzes the host-only entry points of the C-ABI library (ltr_host.cpp, ltr_genotype.cpp, the planning units of ltr_plan.cpp) under
+// Fuzzes the host-only entry points of the C-ABI library (ltr_host.cpp, ltr_hap_aln.cpp, ltr_genotype.cpp, the planning units of ltr_plan.cpp) under
 // AddressSanitizer + UBSan on the CPU: trimming, haplotype enumeration, pooling, scatter, genotype
 // fields, and ltr_process_reads' host half (trim + haplotype strings) up to the point where it
 // would hand the batch to the GPU.  The four library-internal symbols those files need from the HIP
@@ -22,7 +22,7 @@
 #include "../../longtr_amd/csrc/ltr_plan.h"
 
 struct ltr_ctx { ltr_align_params p; std::string err; std::vector<uint8_t> host_bytes[4]; std::mutex call_mu, err_mu; ltr::DebugKnobs knobs; bool fake_device = false; };
-struct ltr_plan { int64_t ll_size = 0, pairs = 0; };               // (the fake device's plan: sizes only)
+struct ltr_plan { int64_t ll_size = 0, pairs = 0; std::vector<double> ll; };   // (the fake device's plan: its "scores")
 namespace ltr {
 std::atomic<int> g_trace{0};                                      // (the trace switch and its clock live with the context, ltr_ctx.hip)
 double dbg_ms() { return 0.0; }
@@ -48,12 +48,13 @@ void* pinned_alloc(size_t) { return nullptr; }
 void pinned_free(void*) {}
 }
 static std::atomic<long> g_batches(0), g_pairs(0);                 // (the stub scorer is called from two threads at once below)
-// A context with fake_device set gets plans that "run": every row the library asks for comes back as its own index, so that the
-// whole chunk pipeline of ltr_calc_hap_aln_probs (staging ahead on a thread of its own, fetch, fan-out) runs under the sanitizers.
+// A context with fake_device set gets plans that "run": the score of a pair is a checksum of its read's and its haplotype's bytes
+// (the same however the loci are cut into chunks), so that the whole chunk pipeline of ltr_calc_hap_aln_probs (staging ahead on a
+// thread of its own, fetch, fan-out) runs under the sanitizers.
 extern "C" int ltr_plan_execute(ltr_plan* p, double*, void*) { return p ? LTR_OK : LTR_ERR_NO_DEVICE; }
 extern "C" int ltr_plan_fetch(ltr_plan* p, double* ll, int32_t*) {
   if (!p) return LTR_ERR_NO_DEVICE;
-  for (int64_t i = 0; i < p->ll_size; ++i) ll[i] = -(double)(i % 1000) - 1.0;
+  std::copy(p->ll.begin(), p->ll.end(), ll);
   return LTR_OK;
 }
 extern "C" int64_t ltr_plan_ll_size(const ltr_plan* p) { return p ? p->ll_size : 0; }
@@ -65,8 +66,12 @@ extern "C" int ltr_plan_create(ltr_ctx* ctx, const ltr_locus_batch* b, ltr_plan*
   const int rc = touch_batch(b);
   if (!ctx->fake_device) return rc;
   ltr_plan* p = new ltr_plan();
-  for (int64_t l = 0; l < b->n_loci; ++l) p->ll_size += (b->locus_read_off[l + 1] - b->locus_read_off[l]) * (b->locus_hap_off[l + 1] - b->locus_hap_off[l]);
-  p->pairs = p->ll_size;
+  auto checksum = [](const uint8_t* bytes, const int64_t* off, int64_t i) { uint64_t s = 0; for (int64_t k = off[i]; k < off[i + 1]; ++k) s = s * 31 + bytes[k]; return (long)(s & 0xffff); };
+  for (int64_t l = 0; l < b->n_loci; ++l)
+    for (int64_t r = b->locus_read_off[l]; r < b->locus_read_off[l + 1]; ++r)
+      for (int64_t h = b->locus_hap_off[l]; h < b->locus_hap_off[l + 1]; ++h)
+        p->ll.push_back(-1.0 - (double)((checksum(b->read_bytes, b->read_off, r) * 7 + checksum(b->hap_bytes, b->hap_off, h)) % 1000));
+  p->pairs = p->ll_size = (int64_t)p->ll.size();
   *out = p;
   return LTR_OK;
 }
@@ -85,6 +90,59 @@ static int touch_batch(const ltr_locus_batch* b) {
 static std::mt19937_64 rng(20250225);
 static int ri(int lo, int hi) { return lo + (int)(rng() % (uint64_t)(hi - lo + 1)); }
 static std::string rseq(int n) { std::string s((size_t)n, 'A'); for (auto& c : s) c = "ACGT"[rng() & 3]; return s; }
+
+// Loci for ltr_calc_hap_aln_probs: [flank][repeat][flank] blocks of block_len bp with up to max_alleles repeat alleles, n_reads
+// reads of up to read_len bases (dup_reads: a later read is a copy of the first every other time, so that reads pool) placed
+// start_off around the first block; masks: every few loci carry second_mate (never at read 0), realign_to_hap, realign_pool or copy_read.
+struct LocSpec { int block_len[2], max_alleles, n_reads[2], read_len, start_off[2]; bool dup_reads, masks; };
+struct Loc { std::vector<int32_t> bs, be, per, na; std::vector<uint8_t> rep, bytes; std::vector<int64_t> off;
+             std::vector<std::string> seqs, types; std::vector<std::vector<int32_t>> nums; std::vector<ltr_alignment> alns;
+             ltr_haplotype_blocks hb; std::vector<double> probs; std::vector<int32_t> seeds; std::vector<uint8_t> mate, to_hap, pool, copy; };
+struct LocSet {
+  std::vector<Loc> L; std::vector<ltr_locus> loci; std::vector<double*> pp; std::vector<int32_t*> sp;
+  LocSet(int NL, const LocSpec& s) : L((size_t)NL), loci((size_t)NL), pp((size_t)NL), sp((size_t)NL) {
+    for (int l = 0; l < NL; ++l) {
+      Loc& X = L[(size_t)l];
+      int pos = ri(100, 1000);
+      X.off.push_back(0);
+      for (int b = 0; b < 3; ++b) {
+        const bool is_rep = (b == 1);
+        const int len = ri(s.block_len[0], s.block_len[1]), nall = is_rep ? ri(1, s.max_alleles) : 1;
+        X.bs.push_back(pos); X.be.push_back(pos + len); pos += len;
+        X.rep.push_back(is_rep); X.per.push_back(is_rep ? ri(2, 6) : 0); X.na.push_back(nall);
+        for (int k = 0; k < nall; ++k) { const std::string a = rseq(k == 0 ? len : ri(1, 60)); X.bytes.insert(X.bytes.end(), a.begin(), a.end()); X.off.push_back((int64_t)X.bytes.size()); }
+      }
+      X.hb = {3, X.bs.data(), X.be.data(), X.rep.data(), X.per.data(), X.na.data(), X.bytes.data(), X.off.data()};
+      const int R = ri(s.n_reads[0], s.n_reads[1]);
+      for (int r = 0; r < R; ++r) {
+        X.seqs.push_back(s.dup_reads && r > 0 && (rng() & 1) ? X.seqs[0] : rseq(ri(1, s.read_len)));
+        X.types.push_back("="); X.nums.push_back({(int32_t)X.seqs.back().size()});
+      }
+      for (int r = 0; r < R; ++r) {
+        const int st = X.bs[0] + ri(s.start_off[0], s.start_off[1]);
+        X.alns.push_back({st, st + X.nums[(size_t)r][0] - 1, (const uint8_t*)X.seqs[(size_t)r].data(), (int32_t)X.seqs[(size_t)r].size(), 1,
+                          X.types[(size_t)r].data(), X.nums[(size_t)r].data(), nullptr});
+      }
+      const int64_t H = ltr_haplotype_num_combs(&X.hb);
+      X.probs.assign((size_t)std::max<int64_t>(1, R * H), 0.0); X.seeds.assign((size_t)std::max(1, R), 0);
+      loci[(size_t)l] = {&X.hb, X.alns.data(), R, nullptr, nullptr, nullptr, nullptr};
+      if (s.masks && R > 0) {
+        auto bits = [&](size_t n) { std::vector<uint8_t> m(n); for (auto& x : m) x = rng() & 1; return m; };
+        if (l % 3 == 0) { X.mate = bits((size_t)R); X.mate[0] = 0; loci[(size_t)l].second_mate = X.mate.data(); }
+        if (l % 4 == 1) { X.to_hap = bits((size_t)H); loci[(size_t)l].realign_to_hap = X.to_hap.data(); }
+        if (l % 5 == 2) { X.pool = bits((size_t)R); loci[(size_t)l].realign_pool = X.pool.data(); }      // (at most R pools)
+        if (l % 7 == 3) { X.copy = bits((size_t)R); loci[(size_t)l].copy_read = X.copy.data(); }
+      }
+      pp[(size_t)l] = X.probs.data(); sp[(size_t)l] = X.seeds.data();
+    }
+  }
+  void bad_cigar(int l, int r) {              // an invalid CIGAR operation in read r of locus l (if it has that many reads)
+    Loc& X = L[(size_t)l];
+    if ((int)X.alns.size() > r) { X.types[(size_t)r] = "Q"; X.alns[(size_t)r].cigar_type = X.types[(size_t)r].data(); }
+  }
+  void clear_outputs() { for (Loc& X : L) { std::fill(X.probs.begin(), X.probs.end(), 0.0); std::fill(X.seeds.begin(), X.seeds.end(), -7); } }
+};
+static ltr_ctx* init_ctx(ltr_ctx* ctx, bool fake_device) { std::memset(&ctx->p, 0, sizeof(ctx->p)); ctx->p.indel_flank_len = 5; ctx->fake_device = fake_device; return ctx; }
 
 int main(int argc, char** argv) {
   long checks = 0;
@@ -150,139 +208,70 @@ int main(int argc, char** argv) {
   // ---- ltr_calc_hap_aln_probs: threaded per-locus preparation + concatenation --------------------
   for (int it = 0; it < 6; ++it) {
     const int NL = 300 + 40 * it;
-    struct Loc { std::vector<int32_t> bs, be, per, na; std::vector<uint8_t> rep, bytes; std::vector<int64_t> off;
-                 std::vector<std::string> seqs, types; std::vector<std::vector<int32_t>> nums; std::vector<ltr_alignment> alns;
-                 ltr_haplotype_blocks hb; std::vector<double> probs; std::vector<int32_t> seeds; };
-    std::vector<Loc> L((size_t)NL);
-    std::vector<ltr_locus> loci((size_t)NL);
-    std::vector<double*> pp((size_t)NL); std::vector<int32_t*> sp((size_t)NL);
-    for (int l = 0; l < NL; ++l) {
-      Loc& X = L[(size_t)l];
-      int pos = ri(100, 1000);
-      X.off.push_back(0);
-      for (int b = 0; b < 3; ++b) {
-        const bool is_rep = (b == 1);
-        const int len = ri(5, 40), nall = is_rep ? ri(1, 4) : 1;
-        X.bs.push_back(pos); X.be.push_back(pos + len); pos += len;
-        X.rep.push_back(is_rep); X.per.push_back(is_rep ? ri(2, 6) : 0); X.na.push_back(nall);
-        for (int k = 0; k < nall; ++k) { const std::string s = rseq(k == 0 ? len : ri(1, 60)); X.bytes.insert(X.bytes.end(), s.begin(), s.end()); X.off.push_back((int64_t)X.bytes.size()); }
-      }
-      X.hb = {3, X.bs.data(), X.be.data(), X.rep.data(), X.per.data(), X.na.data(), X.bytes.data(), X.off.data()};
-      const int R = ri(0, 8);
-      for (int r = 0; r < R; ++r) {
-        const int len = ri(1, 200);
-        X.seqs.push_back(r > 0 && (rng() & 1) ? X.seqs[0] : rseq(len));            // duplicates: pools
-        X.types.push_back(std::string(1, (it == 5 && l == 123 && r == 1) ? 'Q' : '=')); X.nums.push_back({(int32_t)X.seqs.back().size()});
-      }
-      for (int r = 0; r < R; ++r) {
-        const int st = X.bs[0] + ri(-100, 40);
-        X.alns.push_back({st, st + X.nums[(size_t)r][0] - 1, (const uint8_t*)X.seqs[(size_t)r].data(), (int32_t)X.seqs[(size_t)r].size(), 1,
-                          X.types[(size_t)r].data(), X.nums[(size_t)r].data(), nullptr});
-      }
-      const int64_t H = ltr_haplotype_num_combs(&X.hb);
-      X.probs.assign((size_t)std::max<int64_t>(1, R * H), 0.0); X.seeds.assign((size_t)std::max(1, R), 0);
-      loci[(size_t)l] = {&X.hb, X.alns.data(), R, nullptr};
-      pp[(size_t)l] = X.probs.data(); sp[(size_t)l] = X.seeds.data();
-    }
-    ltr_ctx ctx; std::memset(&ctx.p, 0, sizeof(ctx.p)); ctx.p.indel_flank_len = 5;
-    const int rc = ltr_calc_hap_aln_probs(&ctx, loci.data(), NL, pp.data(), sp.data());
+    LocSet S(NL, {{5, 40}, 4, {0, 8}, 200, {-100, 40}, true, false});
+    if (it == 5) S.bad_cigar(123, 1);
+    ltr_ctx ctx;
+    const int rc = ltr_calc_hap_aln_probs(init_ctx(&ctx, false), S.loci.data(), NL, S.pp.data(), S.sp.data());
     if (rc != LTR_ERR_NO_DEVICE && rc != LTR_ERR_CIGAR && rc != LTR_ERR_INVALID) { std::printf("calc_hap_aln_probs rc %d\n", rc); return 1; }
     checks++;
   }
   // ---- the whole chunk pipeline on a fake device: five growing chunks, chunk c + 1 staged by the helper thread while the
   // calling thread "plans" chunk c; then the same one chunk after the other: the rows must be the same ----
   {
-    struct Loc { std::vector<int32_t> bs, be, per, na; std::vector<uint8_t> rep, bytes; std::vector<int64_t> off;
-                 std::vector<std::string> seqs, types; std::vector<std::vector<int32_t>> nums; std::vector<ltr_alignment> alns;
-                 ltr_haplotype_blocks hb; std::vector<double> probs; std::vector<int32_t> seeds; };
     const int NL = 2600;
-    std::vector<Loc> L((size_t)NL); std::vector<ltr_locus> loci((size_t)NL); std::vector<double*> pp((size_t)NL); std::vector<int32_t*> sp((size_t)NL);
-    for (int l = 0; l < NL; ++l) {
-      Loc& X = L[(size_t)l];
-      int pos = ri(100, 1000);
-      X.off.push_back(0);
-      for (int b = 0; b < 3; ++b) {
-        const bool is_rep = (b == 1);
-        const int len = ri(36, 60), nall = is_rep ? ri(1, 3) : 1;
-        X.bs.push_back(pos); X.be.push_back(pos + len); pos += len;
-        X.rep.push_back(is_rep); X.per.push_back(is_rep ? ri(2, 6) : 0); X.na.push_back(nall);
-        for (int k = 0; k < nall; ++k) { const std::string s2 = rseq(k == 0 ? len : ri(1, 60)); X.bytes.insert(X.bytes.end(), s2.begin(), s2.end()); X.off.push_back((int64_t)X.bytes.size()); }
-      }
-      X.hb = {3, X.bs.data(), X.be.data(), X.rep.data(), X.per.data(), X.na.data(), X.bytes.data(), X.off.data()};
-      const int R = ri(1, 6);
-      for (int r = 0; r < R; ++r) { X.seqs.push_back(r > 0 && (rng() & 1) ? X.seqs[0] : rseq(ri(1, 150))); X.types.push_back("="); X.nums.push_back({(int32_t)X.seqs.back().size()}); }
-      for (int r = 0; r < R; ++r) {
-        const int st = X.bs[0] + ri(-80, 30);
-        X.alns.push_back({st, st + X.nums[(size_t)r][0] - 1, (const uint8_t*)X.seqs[(size_t)r].data(), (int32_t)X.seqs[(size_t)r].size(), 1,
-                          X.types[(size_t)r].data(), X.nums[(size_t)r].data(), nullptr});
-      }
-      const int64_t H = ltr_haplotype_num_combs(&X.hb);
-      X.probs.assign((size_t)std::max<int64_t>(1, R * H), 0.0); X.seeds.assign((size_t)R, 0);
-      loci[(size_t)l] = {&X.hb, X.alns.data(), R, nullptr};
-      pp[(size_t)l] = X.probs.data(); sp[(size_t)l] = X.seeds.data();
-    }
+    LocSet S(NL, {{36, 60}, 3, {1, 6}, 150, {-80, 30}, true, false});
     std::vector<std::vector<double>> first;
     for (int mode = 0; mode < 3; ++mode) {
-      ltr_ctx ctx; std::memset(&ctx.p, 0, sizeof(ctx.p)); ctx.p.indel_flank_len = 5; ctx.fake_device = true;
+      ltr_ctx ctx; init_ctx(&ctx, true);
       ctx.knobs.chunks = 5; ctx.knobs.chunk_growth = 1.3; ctx.knobs.chunk_growth_set = true;
       ctx.knobs.prep_ahead = mode == 0 ? 0 : (mode == 1 ? 3 : -1);          // helper thread on 16 threads / on 3 / off
-      for (Loc& X : L) std::fill(X.probs.begin(), X.probs.end(), 0.0);
-      const int rc = ltr_calc_hap_aln_probs(&ctx, loci.data(), NL, pp.data(), sp.data());
+      for (Loc& X : S.L) std::fill(X.probs.begin(), X.probs.end(), 0.0);
+      const int rc = ltr_calc_hap_aln_probs(&ctx, S.loci.data(), NL, S.pp.data(), S.sp.data());
       if (rc != LTR_OK) { std::printf("chunked calc_hap_aln_probs on the fake device: rc %d (%s)\n", rc, ctx.err.c_str()); return 1; }
-      if (mode == 0) for (const Loc& X : L) first.push_back(X.probs);
-      else for (int l = 0; l < NL; ++l) if (first[(size_t)l] != L[(size_t)l].probs) { std::printf("chunk pipeline: mode %d differs at locus %d\n", mode, l); return 1; }
+      if (mode == 0) for (const Loc& X : S.L) first.push_back(X.probs);
+      else for (int l = 0; l < NL; ++l) if (first[(size_t)l] != S.L[(size_t)l].probs) { std::printf("chunk pipeline: mode %d differs at locus %d\n", mode, l); return 1; }
       checks++;
     }
     // a bad record in the fourth chunk: the call's error, whatever thread found it
     {
-      Loc& X = L[2000];
-      X.types[0] = "Q";
-      X.alns[0].cigar_type = X.types[0].data();
-      ltr_ctx ctx; std::memset(&ctx.p, 0, sizeof(ctx.p)); ctx.p.indel_flank_len = 5; ctx.fake_device = true;
+      S.bad_cigar(2000, 0);
+      ltr_ctx ctx; init_ctx(&ctx, true);
       ctx.knobs.chunks = 5; ctx.knobs.chunk_growth = 1.3; ctx.knobs.chunk_growth_set = true;
-      const int rc = ltr_calc_hap_aln_probs(&ctx, loci.data(), NL, pp.data(), sp.data());
+      const int rc = ltr_calc_hap_aln_probs(&ctx, S.loci.data(), NL, S.pp.data(), S.sp.data());
       if (rc != LTR_ERR_CIGAR) { std::printf("bad record in a late chunk: rc %d\n", rc); return 1; }
       checks++;
     }
   }
+  // ---- the same pipeline with mate pairs and the three masks of the realignment call: the helper thread on the whole budget / on
+  // 3 threads / off, then one chunk -- identical rows and seeds (cells and seeds a mask leaves alone keep what they held) ----
+  {
+    const int NL = 2600;
+    LocSet S(NL, {{36, 60}, 3, {1, 6}, 150, {-80, 30}, true, true});
+    std::vector<std::vector<double>> rows; std::vector<std::vector<int32_t>> seeds;
+    for (int mode = 0; mode < 4; ++mode) {
+      ltr_ctx ctx; init_ctx(&ctx, true);
+      ctx.knobs.chunks = mode == 3 ? 1 : 5; ctx.knobs.chunk_growth = 1.3; ctx.knobs.chunk_growth_set = true;
+      ctx.knobs.prep_ahead = mode == 1 ? 3 : (mode == 2 ? -1 : 0);
+      S.clear_outputs();
+      const int rc = ltr_calc_hap_aln_probs(&ctx, S.loci.data(), NL, S.pp.data(), S.sp.data());
+      if (rc != LTR_OK) { std::printf("masked calc_hap_aln_probs on the fake device: rc %d (%s)\n", rc, ctx.err.c_str()); return 1; }
+      if (mode == 0) for (const Loc& X : S.L) { rows.push_back(X.probs); seeds.push_back(X.seeds); }
+      else for (int l = 0; l < NL; ++l)
+        if (rows[(size_t)l] != S.L[(size_t)l].probs || seeds[(size_t)l] != S.L[(size_t)l].seeds) { std::printf("masked chunk pipeline: mode %d differs at locus %d\n", mode, l); return 1; }
+      checks++;
+    }
+    long written = 0, kept = 0;                                          // (the masks did mask, and did not mask everything)
+    for (const Loc& X : S.L) for (size_t r = 0; r < X.alns.size(); ++r) (X.seeds[r] == -7 ? kept : written)++;
+    if (!written || !kept) { std::printf("masked chunk pipeline: %ld reads written, %ld kept\n", written, kept); return 1; }
+  }
   // ---- two callers at once, own contexts: one gets the worker pool, the other finds it busy and falls back to
   // short-lived threads (ltr_internal.h) ----
   {
-    struct Loc { std::vector<int32_t> bs, be, per, na; std::vector<uint8_t> rep, bytes; std::vector<int64_t> off;
-                 std::vector<std::string> seqs, types; std::vector<std::vector<int32_t>> nums; std::vector<ltr_alignment> alns;
-                 ltr_haplotype_blocks hb; std::vector<double> probs; std::vector<int32_t> seeds; };
-    auto make = [&](int NL, std::vector<Loc>& L, std::vector<ltr_locus>& loci, std::vector<double*>& pp, std::vector<int32_t*>& sp) {
-      L.resize((size_t)NL); loci.resize((size_t)NL); pp.resize((size_t)NL); sp.resize((size_t)NL);
-      for (int l = 0; l < NL; ++l) {
-        Loc& X = L[(size_t)l];
-        int pos = ri(100, 1000);
-        X.off.push_back(0);
-        for (int b = 0; b < 3; ++b) {
-          const bool is_rep = (b == 1);
-          const int len = ri(5, 40), nall = is_rep ? ri(1, 3) : 1;
-          X.bs.push_back(pos); X.be.push_back(pos + len); pos += len;
-          X.rep.push_back(is_rep); X.per.push_back(is_rep ? ri(2, 6) : 0); X.na.push_back(nall);
-          for (int k = 0; k < nall; ++k) { const std::string s2 = rseq(k == 0 ? len : ri(1, 60)); X.bytes.insert(X.bytes.end(), s2.begin(), s2.end()); X.off.push_back((int64_t)X.bytes.size()); }
-        }
-        X.hb = {3, X.bs.data(), X.be.data(), X.rep.data(), X.per.data(), X.na.data(), X.bytes.data(), X.off.data()};
-        const int R = ri(1, 6);
-        for (int r = 0; r < R; ++r) { X.seqs.push_back(rseq(ri(1, 150))); X.types.push_back("="); X.nums.push_back({(int32_t)X.seqs.back().size()}); }
-        for (int r = 0; r < R; ++r) {
-          const int st = X.bs[0] + ri(-80, 30);
-          X.alns.push_back({st, st + X.nums[(size_t)r][0] - 1, (const uint8_t*)X.seqs[(size_t)r].data(), (int32_t)X.seqs[(size_t)r].size(), 1,
-                            X.types[(size_t)r].data(), X.nums[(size_t)r].data(), nullptr});
-        }
-        const int64_t H = ltr_haplotype_num_combs(&X.hb);
-        X.probs.assign((size_t)std::max<int64_t>(1, R * H), 0.0); X.seeds.assign((size_t)R, 0);
-        loci[(size_t)l] = {&X.hb, X.alns.data(), R, nullptr};
-        pp[(size_t)l] = X.probs.data(); sp[(size_t)l] = X.seeds.data();
-      }
-    };
-    std::vector<Loc> LA, LB; std::vector<ltr_locus> la, lb; std::vector<double*> pa, pb; std::vector<int32_t*> sa, sb;
-    make(700, LA, la, pa, sa); make(800, LB, lb, pb, sb);
+    const LocSpec spec = {{5, 40}, 3, {1, 6}, 150, {-80, 30}, false, false};
+    LocSet A(700, spec), B(800, spec);
     int rca = 0, rcb = 0;
-    std::thread ta([&]() { ltr_ctx c; std::memset(&c.p, 0, sizeof(c.p)); c.p.indel_flank_len = 5; for (int k = 0; k < 3; ++k) rca = ltr_calc_hap_aln_probs(&c, la.data(), 700, pa.data(), sa.data()); });
-    std::thread tb([&]() { ltr_ctx c; std::memset(&c.p, 0, sizeof(c.p)); c.p.indel_flank_len = 5; for (int k = 0; k < 3; ++k) rcb = ltr_calc_hap_aln_probs(&c, lb.data(), 800, pb.data(), sb.data()); });
+    std::thread ta([&]() { ltr_ctx c; init_ctx(&c, false); for (int k = 0; k < 3; ++k) rca = ltr_calc_hap_aln_probs(&c, A.loci.data(), 700, A.pp.data(), A.sp.data()); });
+    std::thread tb([&]() { ltr_ctx c; init_ctx(&c, false); for (int k = 0; k < 3; ++k) rcb = ltr_calc_hap_aln_probs(&c, B.loci.data(), 800, B.pp.data(), B.sp.data()); });
     ta.join(); tb.join();
     if (rca != LTR_ERR_NO_DEVICE || rcb != LTR_ERR_NO_DEVICE) { std::printf("concurrent calc_hap_aln_probs rc %d %d\n", rca, rcb); return 1; }
     checks++;

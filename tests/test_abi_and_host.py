@@ -179,7 +179,11 @@ def test_host_thread_budget_rule_and_parallel_loops():
     L = _lib.lib()
     full = L.ltr_host_threads_rule(1)
     assert 1 <= full <= 16
-    assert L.ltr_host_threads_rule(2) == max(1, min(16, full) // 2) or L.ltr_host_threads_rule(2) <= full
+    # the rule divides the CPUs by the ranks BEFORE it clamps to 16: below the clamp `full` is the CPU count itself
+    if full < 16:
+        assert L.ltr_host_threads_rule(2) == max(1, full // 2)
+    else:
+        assert full // 2 <= L.ltr_host_threads_rule(2) <= 16
     assert L.ltr_host_threads_rule(10 ** 6) == 1
     for budget in (1, 2, 3, 5):
         for pool in (0, 1):
@@ -202,4 +206,44 @@ def test_host_thread_budget_rule_and_parallel_loops():
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     rule, ahead, used = map(int, out.stdout.split())
-    assert rule == max(1, full // 4) and ahead == 0 and used <= rule
+    want = L.ltr_host_threads_rule(4)                     # the library's own rule for four ranks, under this process's affinity
+    assert rule == want and ahead == (1 if want >= 12 else 0) and used <= rule
+
+
+def test_chunk_plan_rule():
+    """The chunk rule of ltr_calc_hap_aln_probs (ltr_hap_aln.cpp: plan_chunks) on made-up numbers.  Chunk k of n begins at
+    int(n_loci * cum[k] / cum[n]), cum = running sum of the weights 1, g, g^2, .. (growth g > 0), 1, 2, 3, .. (g = 0) or
+    1, 2, .., 2, 1 (g < 0); the last one ends at n_loci."""
+    plan = _lib.debug_chunk_plan
+    # below 1500 loci: one chunk; no second chunk, no helper thread
+    assert plan(1499, budget=16) == dict(bounds=[0, 1499], n_streams=2, prep_ahead=False, ahead_threads=16)
+    # from 1500 loci: two chunks 1 : 3 -> cum 0, 1, 4 -> 1600 * 1 / 4 = 400
+    assert plan(1600, budget=16) == dict(bounds=[0, 400, 1600], n_streams=2, prep_ahead=True, ahead_threads=16)
+    assert plan(1600, budget=11)["prep_ahead"] is False
+    # chunks=5, growth 0: weights 1 .. 5, cum 0, 1, 3, 6, 10, 15 -> 1600 * (1, 3, 6, 10) / 15 = 106.67, 320, 640, 1066.67
+    assert plan(1600, budget=16, chunks=5, chunk_growth=0.0)["bounds"] == [0, 106, 320, 640, 1066, 1600]
+    # a negative growth: the hill 1, 2, 3, 2, 1, cum 0, 1, 3, 6, 8, 9 -> 1800 * (1, 3, 6, 8) / 9
+    assert plan(1800, budget=16, chunks=5, chunk_growth=-1.0)["bounds"] == [0, 200, 600, 1200, 1600, 1800]
+    # more chunks than loci: clamped to one chunk per locus (equal weights: 3 * k / 3; the rule's growth of 3: cum 0, 1, 4, 13 ->
+    # int(3 / 13) = 0, int(12 / 13) = 0); chunk_streams is handed through
+    assert plan(3, budget=16, chunks=50, chunk_growth=1.0, chunk_streams=3) == dict(bounds=[0, 1, 2, 3], n_streams=3, prep_ahead=True, ahead_threads=16)
+    assert plan(3, budget=16, chunks=50)["bounds"] == [0, 0, 0, 3]
+    assert plan(0, budget=16, chunks=4)["bounds"] == [0, 0]
+    # 30 000 loci, host-bound: GPU seconds = cells / 2.5e12 below 1.5 x host seconds = 1.5 * 30 000 * 0.8e-6 = 0.036, i.e. cells
+    # < 9e10.  With the helper (budget 16 >= 12): growth 1.3 and chunks while 2400 * (1.3^n - 1) / 0.3 < 30 000, from n = 3:
+    # n = 3: 9576, n = 4: 14 848.8, n = 5: 21 703.4, n = 6: 30 614.5 -> 6 chunks, weights 1.3^k
+    host_bound, gpu_bound = 1e10, 1e12
+    got = plan(30000, host_bound, budget=16)
+    # cum 0, 1, 2.3, 3.99, 6.187, 9.0431, 12.75603 -> 30 000 * cum[k] / 12.75603 = 2351.8, 5409.2, 9383.8, 14 550.8, 21 267.8
+    assert got == dict(bounds=[0, 2351, 5409, 9383, 14550, 21267, 30000], n_streams=2, prep_ahead=True, ahead_threads=16)
+    # ... without the helper (budget 8, or switched off): three equal chunks
+    assert plan(30000, host_bound, budget=8) == dict(bounds=[0, 10000, 20000, 30000], n_streams=2, prep_ahead=False, ahead_threads=8)
+    assert plan(30000, host_bound, budget=16, prep_ahead=-1) == dict(bounds=[0, 10000, 20000, 30000], n_streams=2, prep_ahead=False, ahead_threads=16)
+    # ... prep_ahead=3: the helper whatever the budget, on 3 threads of its own
+    got = plan(30000, host_bound, budget=8, prep_ahead=3)
+    assert len(got["bounds"]) == 7 and got["prep_ahead"] is True and got["ahead_threads"] == 3
+    # GPU-bound (cells / 2.5e12 = 0.4 s against 0.036): two chunks 1 : 3
+    assert plan(30000, gpu_bound, budget=16) == dict(bounds=[0, 7500, 30000], n_streams=2, prep_ahead=True, ahead_threads=16)
+    # below 6000 loci the estimate is not read
+    assert plan(5999, host_bound, budget=16)["bounds"] == [0, 1499, 5999]
+    assert [_lib.lib().ltr_debug_prep_ahead_rule(n) for n in (11, 12)] == [0, 1]

@@ -154,7 +154,7 @@ def test_bench_end_to_end_ranks_dry_run():
     array per rank, a stand-in fills it, the gather must put every locus at its global place; the line names every rank's
     host-thread budget = the library's rule under the launcher's LOCAL_WORLD_SIZE (8 ranks share the host's cores)."""
     from longtr_amd import _lib
-    full = _lib.lib().ltr_host_threads_rule(1)
+    rule = _lib.lib().ltr_host_threads_rule
     for n in (2, 8):
         rc, lines, err = _run_bench(["--gpus", str(n), "--dry-run", "--end-to-end", "--loci", "48", "--steps", "2", "--warmup", "1"], timeout=600)
         assert rc == 0, err[-2000:]
@@ -163,7 +163,7 @@ def test_bench_end_to_end_ranks_dry_run():
         assert ln["n_gpus"] == n and ln["end_to_end"] is True and ln["dry_run"] is True and ln["value"] is None
         assert ln["gather_check"] == {"gathered_loci": 48, "misplaced_loci": 0, "order_ok": True}
         assert ln["config"]["total_loci"] == 48
-        assert ln["host_threads_per_rank"] == [max(1, full // n)] * n, (ln["host_threads_per_rank"], full)
+        assert ln["host_threads_per_rank"] == [rule(n)] * n, (ln["host_threads_per_rank"], rule(n))       # (this process's affinity is the ranks')
         assert len(ln["rank_ms_per_step"]) == n
 
 
