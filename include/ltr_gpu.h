@@ -175,6 +175,14 @@ int ltr_plan_kernel_stats(ltr_plan* plan, int k, int* strip_width, int64_t* n_pa
 int ltr_plan_kernel_ranges(ltr_plan* plan, int k, int32_t* lanes_per_pair, int32_t* strip_width, int64_t* n_pairs);
 /* The class the plan kernel's launch is reported under by ltr_plan_kernel_stats / _ranges (-1: this plan runs a launch per class). */
 int ltr_plan_kernel_class(const ltr_plan* plan);
+/* Haplotype families (csrc/ltr_dp_family.hpp): in automatic mode, under a symmetric indel model, the pairs of one pooled read of
+ * 641 .. 1280 columns against several haplotypes of its locus are scored by a launch of their own, listed under a class of its own
+ * (family 2 in ltr_kernel_family), that runs the rows the haplotype windows share once per read; a member it cannot prove
+ * bit-identical to the unshared DP is scored again by the exact body.  ltr_ctx_set_debug "families" (-1 never, 0 by rule, 1 whenever
+ * one can be formed) and "family_min_rows" (fewest shared rows; 0: the rule's 64) act on the plans created afterwards.
+ * out5 = families, member pairs of the plan; of its last execute: families whose stem certificate failed (all members to the exact
+ * body), members the acceptance rule sent there, members whose tail certificate failed. */
+int ltr_plan_family_stats(ltr_plan* plan, int64_t* out5);
 /* Measurement aid: with ltr_ctx_set_debug(ctx, "wave_clock", 1) set when the plan was created, the plan kernel records the wall
  * clock (100 MHz) at which every one of its wavefronts started and left, and what it spent in the exact body: out = {first, last,
  * pairs scored with the exact body, ticks spent there} per wavefront of the last execute, then 4096 words: a count and

@@ -15,7 +15,7 @@ from . import _abi
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("LTR_GPU_LIB") or os.path.join(CSRC, "libltr_gpu.so")   # override: A/B builds only
-KERNEL_TUS = ["ltr_k_one.hip", "ltr_k_pack.hip", "ltr_k_plan.hip", "ltr_k_wg.hip", "ltr_k_wgt.hip", "ltr_k_exact.hip", "ltr_plan.cpp"]      # one family of DP kernels each
+KERNEL_TUS = ["ltr_k_one.hip", "ltr_k_pack.hip", "ltr_k_plan.hip", "ltr_k_wg.hip", "ltr_k_wgt.hip", "ltr_k_exact.hip", "ltr_k_family.hip", "ltr_plan.cpp"]      # one family of DP kernels each
 SOURCES = ["ltr_ctx.hip", "ltr_plan_build.hip", "ltr_plan_run.hip", "ltr_posterior.hip", "ltr_plan_genotype.hip", "ltr_plan_fields.hip"] + KERNEL_TUS + ["ltr_short.hip", "ltr_nw.hip", "ltr_host.cpp", "ltr_hap_aln.cpp", "ltr_genotype.cpp", "ltr_vcf.cpp", "ltr_prep.cpp", "ltr_io.cpp", "ltr_bam.cpp", "ltr_vcf_in.cpp", "ltr_editdist.hip", "ltr_cluster.cpp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-honor-nans", "-std=c++17", "-fPIC", "-shared", "-pthread", "-Wall"]
 LINK_LIBS = ["-lz"]                                         # BGZF blocks (ltr_bgzf.h: BAM, VCF writer, tabix-indexed VCF input)
@@ -25,7 +25,7 @@ EXPORTS = [
     "ltr_default_params", "ltr_default_stutter_params", "ltr_ctx_set_stutter_params", "ltr_ctx_set_pair_packing", "ltr_ctx_set_debug", "ltr_ctx_wg_first_pass", "ltr_ctx_create", "ltr_ctx_destroy", "ltr_ctx_set_params", "ltr_last_error",
     "ltr_ctx_device_info", "ltr_align_batch", "ltr_plan_create", "ltr_plan_destroy", "ltr_plan_num_pairs",
     "ltr_plan_ll_size", "ltr_plan_cells", "ltr_plan_input_bytes", "ltr_plan_execute", "ltr_plan_fetch",
-    "ltr_plan_last_kernel_ms", "ltr_num_kernels", "ltr_kernel_lanes_per_pair", "ltr_kernel_family", "ltr_plan_set_timing", "ltr_plan_kernel_stats", "ltr_plan_kernel_ranges", "ltr_plan_debug_wave_clocks", "ltr_plan_debug_entries", "ltr_plan_kernel_class", "ltr_process_reads", "ltr_calc_hap_aln_probs", "ltr_haplotype_num_combs", "ltr_haplotype_seq",
+    "ltr_plan_last_kernel_ms", "ltr_num_kernels", "ltr_kernel_lanes_per_pair", "ltr_kernel_family", "ltr_plan_set_timing", "ltr_plan_kernel_stats", "ltr_plan_kernel_ranges", "ltr_plan_debug_wave_clocks", "ltr_plan_debug_entries", "ltr_plan_kernel_class", "ltr_plan_family_stats", "ltr_process_reads", "ltr_calc_hap_aln_probs", "ltr_haplotype_num_combs", "ltr_haplotype_seq",
     "ltr_trim_alignment", "ltr_pool_reads", "ltr_scatter_pool_probs", "ltr_posteriors", "ltr_plan_posteriors", "ltr_extract_genotypes", "ltr_ctx_timers", "ltr_haps_to_alleles", "ltr_unused_alleles", "ltr_remap_haplotypes",
     "ltr_remap_aln_probs", "ltr_default_vcf_options", "ltr_get_alleles", "ltr_vcf_record", "ltr_vcf_header", "ltr_haplotype_aln_info_capacity",
     "ltr_haplotype_align_to_ref", "ltr_left_align_reads", "ltr_phasing_priors", "ltr_read_set_size", "ltr_read_set_alignments",
@@ -716,7 +716,7 @@ def debug_threshold_groups(class_first, merge=True, keep_waves=False):
     return nw, w, npairs
 
 
-LAUNCH_KINDS = ("one-wave", "packed", "multi", "packed-multi", "plan", "workgroup")      # ltrp::LaunchKind
+LAUNCH_KINDS = ("one-wave", "packed", "multi", "packed-multi", "plan", "workgroup", "family")      # ltrp::LaunchKind
 
 
 def debug_plan_schedule(batch, grids, params=None, mode=-1, n_cu=256, plan_kernel=0, no_multi=0, chain=0, chain_min_w=0, chain_max_w=0,
@@ -751,6 +751,31 @@ def debug_plan_schedule(batch, grids, params=None, mode=-1, n_cu=256, plan_kerne
     ents = [dict(zip(("kind", "W", "first", "pairs", "queue_class", "first_wave"), (int(v) for v in entry[i]))) for i in range(int(out[2]))]
     return dict(launches=rows[:int(out[0])], by_class=rows[int(out[0]):], entries=ents, n_tabs=int(out[3]), use_plan=bool(out[4]),
                 max_grid=int(out[5]), max_grid_wide=int(out[6]), max_len=int(out[7]), xcand=out[8:8 + n_exact].copy(), class_first=out[8 + n_exact:].copy(), x_grid=x_grid)
+
+
+def debug_plan_families(batch, params=None, mode=-1, n_cu=256, families=0, family_min_rows=0):
+    """Test hook ltr_debug_plan_families (csrc/ltr_plan.h): describe_batch on a _abi.PackedBatch, no GPU; families / family_min_rows
+    are the ltr_ctx_set_debug knobs of the same names.  dict(families: list of dict(first, count, p, W, dd_min, dd_max, U, n: window
+    lengths of the members, out_idx: their LL indices), members, n_pairs)."""
+    L = lib()
+    L.ltr_debug_plan_families.argtypes = [C.POINTER(_abi.AlignParams), C.c_int, C.c_int, C.POINTER(_abi.LocusBatch), C.c_void_p, C.c_void_p,
+                                          C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    prm = params or _abi.default_params()
+    knobs = np.asarray([families, family_min_rows], dtype=np.int32)
+    out = np.zeros(4, dtype=np.int64)
+    cap = max(int(batch.ll_size), 1)
+    fam, U = np.zeros((cap, 6), np.int32), np.zeros(cap)
+    mem_n, mem_out = np.zeros(cap, np.int32), np.zeros(cap, np.int64)
+    rc = L.ltr_debug_plan_families(C.byref(prm), int(mode), int(n_cu), C.byref(batch.struct), _p(knobs), _p(out), cap, _p(fam), _p(U), cap, _p(mem_n), _p(mem_out))
+    if rc != 0:
+        raise LtrError(rc, "ltr_debug_plan_families")
+    rows = []
+    for i in range(int(out[0])):
+        d = dict(zip(("first", "count", "p", "W", "dd_min", "dd_max"), (int(v) for v in fam[i])))
+        a = d["first"] - int(out[2])
+        d.update(U=float(U[i]), n=[int(v) for v in mem_n[a:a + d["count"]]], out_idx=[int(v) for v in mem_out[a:a + d["count"]]])
+        rows.append(d)
+    return dict(families=rows, members=int(out[1]), n_pairs=int(out[3]))
 
 
 def debug_chunk_plan(n_loci, est_cells=0.0, budget=0, chunks=0, chunk_streams=0, chunk_growth=None, prep_ahead=0):
@@ -1057,6 +1082,15 @@ class Plan:
         self.redo_log = [(int(v >> np.uint64(32)), int(v & np.uint64(0xffffffff))) for v in buf[4 * n + 1:4 * n + 1 + k]]   # (n, m) of the pairs that took the exact body
         self.entry_ticks = buf[4 * n + 4096:4 * n + 4096 + 256].copy()       # per entry of the plan kernel's table: ticks of all wavefronts together
         return buf[:4 * n].reshape(n, 4)
+
+    def family_stats(self):
+        """ltr_plan_family_stats: dict(families, members) of the plan and, of its last execute, stem_failures (families whose stem
+        certificate failed: every member to the exact body), rule_failures / tail_failures (members the acceptance rule / a tail
+        certificate sent there)."""
+        lib().ltr_plan_family_stats.argtypes = [C.c_void_p, C.c_void_p]
+        out = np.zeros(5, dtype=np.int64)
+        self.ctx._check(lib().ltr_plan_family_stats(self._h, _p(out)))
+        return dict(zip(("families", "members", "stem_failures", "rule_failures", "tail_failures"), (int(v) for v in out)))
 
     def plan_entries(self):
         """The plan kernel's table in walk order: dicts (kind, strip_width, pairs, cells)."""

@@ -167,7 +167,8 @@ int ltr_kernel_lanes_per_pair(int k) {
 }
 int ltr_kernel_family(int k) {
   if (k < 0 || k >= kNumKernels) return -1;
-  return k >= kNumFast ? 3 : class_info(k).family;
+  if (k >= kNumFast) return 3;
+  return class_info(k).family == kFamShare ? (int)kFamWg : class_info(k).family;     // (the family class: a launch of its own beside the plan kernel)
 }
 
 void ltr_default_params(ltr_align_params* p) {
@@ -216,6 +217,8 @@ int ltr_ctx_set_debug(ltr_ctx* ctx, const char* key, double value) {
   else if (k == "wgt_keep_waves") ctx->dbg.wgt_keep_waves = (int)value;
   else if (k == "plan_kernel") ctx->dbg.plan_kernel = (int)value;
   else if (k == "plan_share") ctx->dbg.plan_share = (int)value;
+  else if (k == "families") ctx->dbg.families = (int)value;
+  else if (k == "family_min_rows") ctx->dbg.family_min_rows = (int)value;
   else if (k == "chain") ctx->dbg.chain = (int)value;
   else if (k == "chain_min_w") ctx->dbg.chain_min_w = (int)value;
   else if (k == "chain_max_w") ctx->dbg.chain_max_w = (int)value;

@@ -106,6 +106,25 @@ struct KernelArgs {
 #define LTR_WMAX 20
 #endif
 constexpr int kWMax = LTR_WMAX;      // widest strip (1281-base reads in ONE column block: nothing parked in scratch strips); wider reads use more column blocks
+// Haplotype families (ltr_dp_family.hpp; formed on the host, ltrp::form_families): the pairs of one read against several
+// haplotypes of its locus, contiguous in the sorted pair list, whose windows share their first p rows.
+struct FamilyDesc {
+  int32_t first, count;    // member pairs [first, first + count) of the sorted pair list
+  int32_t p;               // fork row: the members' windows are the same bytes in rows 0 .. p-1, and p <= every member's n - 1
+  int32_t W;               // strip width (the read's: one column block)
+  int32_t dd_min, dd_max;  // smallest and largest n - m of a member
+};
+struct FamilyArgs {        // the family kernel's second argument (KernelArgs stays what the other kernels were built against)
+  const FamilyDesc* fams;  // sorted by modelled cost, largest first
+  int32_t n_fams;
+  int32_t reserved;
+  double* park;            // per wavefront of the launch: kFamilyParkDoubles (the stem's last row: X, Y of every column)
+  uint32_t* stats;         // [0] families whose stem certificate failed, [1] members the acceptance rule sent to the exact body, [2] members whose tail certificate failed
+};
+constexpr int kFamilyMaxMembers = 32;            // members of a family (the wave's note list)
+constexpr int kFamilyMinC = 641, kFamilyMaxC = 64 * LTR_WMAX;   // read columns of a family: one wavefront, one column block, strips of 11 .. 20
+constexpr int kFamilyParkDoubles = 2 * LTR_WMAX * 64;
+constexpr int kFamilyArgsOffset = (int)((sizeof(KernelArgs) + alignof(FamilyArgs) - 1) / alignof(FamilyArgs) * alignof(FamilyArgs));   // where FamilyArgs sits in the kernel's argument segment
 constexpr int kInlineCountOff = 8;                // xcount[kInlineCountOff + c]: pairs of exact class c the plan kernel scored in line (statistics)
 constexpr int kWgStatOff = 16;                    // xcount[kWgStatOff]: pairs the FIRST pass of the workgroup classes could not finish (certificate pass: sent to an exact list; threshold pass: aborted, -700); [+ 1]: pairs it scored -- what the context learns its first pass from
 constexpr int kPackMultiMinW = 13;                // ... of the multi-width packed launch: 13 .. 20

@@ -33,6 +33,10 @@ void launch_pack_multi(bool sym, dim3 grid, hipStream_t st, const KernelArgs& A)
 hipError_t occ_plan(bool sym, int* per_cu);
 void launch_plan(bool sym, dim3 grid, hipStream_t st, const KernelArgs& A);
 
+// the family kernel (ltr_dp_family.hpp): one read against several haplotypes, shared rows once; symmetric models only
+hipError_t occ_family(int* per_cu);
+void launch_family(dim3 grid, hipStream_t st, const KernelArgs& A, const FamilyArgs& F);
+
 // one pair per workgroup of NW = 1 / 4 / 8 wavefronts (ltr_dp_wg.hpp; symmetric models only)
 hipError_t occ_wg(int NW, int W, int* per_cu);
 void launch_wg(int NW, int W, dim3 grid, hipStream_t st, const KernelArgs& A);

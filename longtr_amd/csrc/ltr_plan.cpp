@@ -401,6 +401,130 @@ void build_threshold_table(float c32, double* out) {
   }
 }
 
+// ---- haplotype families (ltr_plan.h) -------------------------------------------------------------------------------------------
+
+static int32_t common_prefix(const uint8_t* a, const uint8_t* b2, int32_t len) {
+  int32_t k = 0;
+  for (; k + 8 <= len; k += 8) {
+    uint64_t x, y;
+    std::memcpy(&x, a + k, 8); std::memcpy(&y, b2 + k, 8);
+    if (x != y) return k + (__builtin_ctzll(x ^ y) >> 3);
+  }
+  for (; k < len && a[k] == b2[k]; ++k) {}
+  return k;
+}
+
+void form_families(const ltr_locus_batch* b, const ModelConsts& mc, const int F, const int n_cu, const int knob, const int min_rows_in,
+                   const std::vector<int64_t>& pair_base, const BatchScratch& w, std::vector<FamilyRec>* out) {
+  RawBuf<PairDesc>& pairs = w.pairs; RawBuf<int16_t>& key = w.key; RawBuf<int16_t>& bin = w.bin;
+  const int min_rows = std::max(min_rows_in, 2);                 // (the stem has a row of its own)
+  // lpc as the device table holds it (ltr_ctx.hip, build_tables): lpc[1] = 0, lpc[j+1] = lpc[j] + c
+  // (as far as a fork row can reach: p <= n - 1 and a member's n <= m + 600 <= kFamilyMaxC + 601)
+  std::vector<double> lpc((size_t)kFamilyMaxC + 600 + 4, 0.0);
+  for (size_t j = 1; j + 1 < lpc.size(); ++j) lpc[j + 1] = lpc[j] + (double)mc.c;
+  const double cg = (double)mc.g, cd = (double)mc.d, ca = (double)mc.a, cc = (double)mc.c, cf = (double)mc.f, MATCH = (double)mc.match;
+  constexpr int kMaxH = 64;
+  std::vector<std::vector<FamilyRec>> per_locus((size_t)b->n_loci);
+  ltr::parallel_for(b->n_loci, 64, [&](int64_t l) {
+    const int64_t r0 = b->locus_read_off[l], r1 = b->locus_read_off[l + 1];
+    const int64_t h0 = b->locus_hap_off[l], h1 = b->locus_hap_off[l + 1];
+    const int64_t H = h1 - h0;
+    if (H < 2 || H > kMaxH) return;
+    const uint8_t* win[kMaxH]; int32_t wn[kMaxH];
+    int32_t lcp[kMaxH][kMaxH];                                   // longest common prefix of two windows, -1: not formed yet
+    bool have_windows = false;
+    int64_t at = pair_base[(size_t)l];
+    for (int64_t r = r0; r < r1; ++r) {
+      if (b->realign_read && !b->realign_read[r]) continue;
+      const int64_t row_at = at;
+      int64_t n_here = 0;
+      for (int64_t h = h0; h < h1; ++h) if (!b->realign_hap || b->realign_hap[h]) ++n_here;
+      at += n_here;
+      const int64_t m = b->read_off[r + 1] - b->read_off[r];
+      const int C = (int)m - 1;
+      if (C < kFamilyMinC || C > kFamilyMaxC) continue;
+      const int W = (C + 63) / 64, L = (C + W - 1) / W;
+      // candidates: what the class rule left in the one-wave class of the read's own strip width, with a DP to run
+      int cand_h[kMaxH]; int64_t cand_i[kMaxH]; int nc = 0;
+      {
+        int64_t i = row_at;
+        for (int64_t h = h0; h < h1; ++h) {
+          if (b->realign_hap && !b->realign_hap[h]) continue;
+          if (bin[(size_t)i] == W - 1 && key[(size_t)i] > 0 && pairs[(size_t)i].generic == 0 && pairs[(size_t)i].n >= 2) { cand_h[nc] = (int)(h - h0); cand_i[nc] = i; ++nc; }
+          ++i;
+        }
+      }
+      if (nc < 2) continue;
+      if (!have_windows) {
+        for (int64_t h = h0; h < h1; ++h) {
+          const int64_t hl = b->hap_off[h + 1] - b->hap_off[h];
+          int64_t pos = 0;
+          const int64_t n = hl > 60 ? ltr::hap_window(hl, F, &pos) : 0;
+          win[h - h0] = b->hap_bytes + b->hap_off[h] + pos; wn[h - h0] = (int32_t)std::max<int64_t>(n, 0);
+          for (int64_t h2 = h0; h2 < h1; ++h2) lcp[h - h0][h2 - h0] = -1;
+        }
+        have_windows = true;
+      }
+      auto lcp_of = [&](int x, int y) {
+        if (lcp[x][y] < 0) lcp[x][y] = lcp[y][x] = common_prefix(win[x], win[y], std::min(wn[x], wn[y]));
+        return lcp[x][y];
+      };
+      // the fork of the candidates, then -- once -- of those whose score has a chance against its bound (fewer members: p can only
+      // grow and U only fall, so whoever passes the first bound passes the second)
+      int p = 0; double U = 0.0;
+      for (int pass = 0; pass < 2 && nc >= 2; ++pass) {
+        p = 0x7fffffff;
+        for (int k = 0; k < nc; ++k) p = std::min(p, std::min(k ? lcp_of(cand_h[0], cand_h[k]) : 0x7fffffff, wn[cand_h[k]] - 1));
+        if (p < min_rows) { nc = 0; break; }
+        if ((size_t)p >= lpc.size()) { nc = 0; break; }               // (cannot happen: see the table's size)
+        U = ((cg + lpc[(size_t)p - 1]) + cd) + MATCH;
+        if (pass) break;
+        int kept = 0;
+        for (int k = 0; k < nc; ++k) {
+          const int dd = wn[cand_h[k]] - (int)m;
+          // (the haplotype window longer than the read is the insertion state, the read longer the deletion state: make_rules)
+          const double gap = dd > 0 ? cf + (double)(dd - 1) * ca : (dd < 0 ? cg + (double)(-dd - 1) * cc : 0.0);
+          if (gap > U) { cand_h[kept] = cand_h[k]; cand_i[kept] = cand_i[k]; ++kept; }
+        }
+        if (kept == nc) break;
+        nc = kept;
+      }
+      if (nc < 2 || nc > kFamilyMaxMembers) continue;
+      int64_t fam_steps = (p - 1) + (L - 1), own_steps = 0;
+      int dd_min = 0x7fffffff, dd_max = -0x7fffffff;
+      for (int k = 0; k < nc; ++k) {
+        const int n = wn[cand_h[k]];
+        fam_steps += (n - p) + (L - 1); own_steps += (n - 1) + (L - 1);
+        dd_min = std::min(dd_min, n - (int)m); dd_max = std::max(dd_max, n - (int)m);
+      }
+      if (knob <= 0 && fam_steps >= own_steps) continue;
+      const double c = (double)fam_steps * (W + kStepOverhead);
+      const int16_t fkey = (int16_t)std::min(511, std::max(1, (c > 1.0 ? (int)(std::log2(c) * 16.0) : 0) - 16));
+      FamilyRec rec;
+      rec.first_pair = cand_i[0]; rec.U = U; rec.row_at = row_at; rec.members = 0; rec.key = fkey;
+      for (int k = 0; k < nc; ++k) rec.members |= 1ull << (cand_i[k] - row_at);
+      rec.f.first = 0; rec.f.count = nc; rec.f.p = p; rec.f.W = W; rec.f.dd_min = dd_min; rec.f.dd_max = dd_max;
+      per_locus[(size_t)l].push_back(rec);
+    }
+  });
+  out->clear();
+  for (const std::vector<FamilyRec>& v : per_locus) out->insert(out->end(), v.begin(), v.end());     // (ascending first_pair: loci, then reads, in batch order)
+  // A launch of its own pays once the batch fills the GPU: one wavefront runs a family's stem and all its tails one after the other, so
+  // a family lasts as long as ~H pairs on one wave slot, and the families are dealt out statically.  Measured on MI355X (config-3 loci,
+  // families on request against none, kernel ms per pass): 16 families 1.52 against 0.38, 272 families 2.37 against 1.07, 533 families
+  // (4311 pairs) 2.04 against 1.40 -- the pass stays one family long while the plan kernel spreads the same pairs over idle wave slots.
+  // By rule: from a family for every wavefront of a full grid up (kFamPerCu per CU: three workgroups of four); knob 1: whenever one can
+  // be formed.
+  if (knob <= 0 && (int64_t)out->size() < (int64_t)kFamPerCu * std::max(n_cu, 1)) out->clear();
+  ltr::parallel_for((int64_t)out->size(), 256, [&](int64_t i) {
+    const FamilyRec& r = (*out)[(size_t)i];
+    for (uint64_t rest = r.members; rest; rest &= rest - 1) {
+      const size_t at = (size_t)(r.row_at + __builtin_ctzll(rest));
+      bin[at] = (int16_t)kFamClass; key[at] = r.key;
+    }
+  });
+}
+
 // ---- describe_batch: the host half of ltr_plan_create ------------------------------------------------------------------------
 
 // What the batch as a whole decides is decided from these: pairs (upper bound), pairs of reads beyond one wavefront's widest
@@ -483,7 +607,7 @@ static int scan_sequences(const ltr_locus_batch* b, const BatchScratch& w, std::
 
 // One descriptor, launch class and launch-order key per pair (w.pairs, w.bin, w.key, batch order); the per-locus and whole-batch
 // figures of *d.
-static int enumerate_pairs(const ltr_locus_batch* b, const Rules& rules, const int F, const BatchScratch& w, BatchPlan* d, std::string* err) {
+static int enumerate_pairs(const ltr_locus_batch* b, const Rules& rules, const int F, const BatchScratch& w, BatchPlan* d, std::vector<int64_t>* pair_base_out, std::string* err) {
   RawBuf<PairDesc>& pairs = w.pairs;
   RawBuf<int16_t>& key = w.key;      // launch-order key of every pair
   RawBuf<int16_t>& bin = w.bin;      // launch class of every pair
@@ -493,7 +617,8 @@ static int enumerate_pairs(const ltr_locus_batch* b, const Rules& rules, const i
   d->seed.assign((size_t)b->n_reads, -1);
   double in_bytes = 0.0, cells = 0.0;
   // ---- pass 1 (serial, cheap): per-locus output offsets and pair counts -> where every locus' pairs go ----
-  std::vector<int64_t> pair_base((size_t)b->n_loci + 1, 0);
+  std::vector<int64_t>& pair_base = *pair_base_out;
+  pair_base.assign((size_t)b->n_loci + 1, 0);
   d->locus_P.reserve((size_t)b->n_loci); d->locus_H.reserve((size_t)b->n_loci); d->locus_ll_off.reserve((size_t)b->n_loci);
   for (int64_t l = 0; l < b->n_loci; ++l) {
     const int64_t r0 = b->locus_read_off[l], r1 = b->locus_read_off[l + 1];
@@ -613,9 +738,14 @@ int describe_batch(const ltr_locus_batch* b, const ModelConsts& mc, const int F,
   // the general-model instance; ltrp::make_rules; ltr_ctx_set_debug "plan_kernel": 1 = never).  Measured on MI355X, cost shards of
   // config 3 (tests/manual/gpu_plan_ab.py), plan kernel against round 4's launches: profiles/r05/plan_kernel/.
   d->use_plan = rules.plan_kernel;
-  if ((rc = scan_sequences(b, w, err)) != LTR_OK || (rc = enumerate_pairs(b, rules, F, w, d, err)) != LTR_OK) return rc;
+  std::vector<int64_t> pair_base;
+  if ((rc = scan_sequences(b, w, err)) != LTR_OK || (rc = enumerate_pairs(b, rules, F, w, d, &pair_base, err)) != LTR_OK) return rc;
   RawBuf<PairDesc>& pairs = w.pairs; RawBuf<int16_t>& bin = w.bin;
   const int64_t n_pairs_total = d->n_pairs;
+  // haplotype families: their members leave the one-wave classes (the plan kernel never sees them) for a class of their own
+  std::vector<FamilyRec> fam_recs;
+  if (d->use_plan && rules.sym_model && dbg.families >= 0)
+    form_families(b, mc, F, n_cu, dbg.families, dbg.family_min_rows > 0 ? dbg.family_min_rows : kFamMinRows, pair_base, w, &fam_recs);
 
   // Whole rounds of four-wave workgroups for the reads of 3.6 - 5.1 kb, the rest of them on eight waves (make_rules): the
   // pairs beyond the quota -- the last ones in batch order -- move to the eight-wave class of their length.
@@ -656,6 +786,21 @@ int describe_batch(const ltr_locus_batch* b, const ModelConsts& mc, const int F,
     for (size_t i = (size_t)c * kPlanBlock; i < std::min(pairs.size(), ((size_t)c + 1) * kPlanBlock); ++i) sorted[i] = pairs[(size_t)order[i]];
   }, 1);
   LTR_DBG("plan: gathered");
+  // the families in the order the sort left their members in: a family's members are one run of the family class, its first
+  // member first (input order inside a key)
+  d->fams.clear(); d->fam_U.clear(); d->fam_members = 0;
+  for (int i = d->bin_first[kFamClass]; i < d->bin_first[kFamClass + 1];) {
+    const int64_t orig = order[(size_t)i];
+    const auto it = std::lower_bound(fam_recs.begin(), fam_recs.end(), orig, [](const FamilyRec& r, int64_t v) { return r.first_pair < v; });
+    bool ok = it != fam_recs.end() && it->first_pair == orig && i + it->f.count <= d->bin_first[kFamClass + 1];
+    for (int k = 0; ok && k < it->f.count; ++k)
+      ok = sorted[(size_t)(i + k)].read_off == sorted[(size_t)i].read_off && sorted[(size_t)(i + k)].m == sorted[(size_t)i].m && sorted[(size_t)(i + k)].n - 1 >= it->f.p;
+    if (!ok) { *err = "internal error: a haplotype family's members are not contiguous in the sorted pair list"; return LTR_ERR_INVALID; }
+    FamilyDesc f = it->f;
+    f.first = i;
+    d->fams.push_back(f); d->fam_U.push_back(it->U); d->fam_members += f.count;
+    i += f.count;
+  }
   return LTR_OK;
 }
 
@@ -717,7 +862,7 @@ int Schedule::ranges(const Launch& L, const int* bin_first, int32_t* lanes_per_p
 
 void Schedule::cap_grids(const int cap) {
   for (std::vector<Launch>* list : {&launches, &by_class})
-    for (Launch& L : *list) if (L.kind == kLaunchOne || L.kind == kLaunchMulti || L.kind == kLaunchPlan) L.grid = std::min(L.grid, cap);
+    for (Launch& L : *list) if (L.kind == kLaunchOne || L.kind == kLaunchMulti || L.kind == kLaunchPlan || L.kind == kLaunchFamily) L.grid = std::min(L.grid, cap);
   for (int c = 0; c <= kXLong; ++c) x_grid[c] = std::min(x_grid[c], cap);
   max_grid = std::min(max_grid, cap);
 }
@@ -815,7 +960,8 @@ void build_schedule(BatchPlan* d, const ClassStats& st, const OccupancyGrids& oc
       size_launch(&L, blocks_of(waves), occ.cls[k]);
     } else {
       L.pairs = bf[k + 1] - bf[k]; L.cells = st.bin_cells[k]; L.cmax = st.cls_cmax[k];
-      if (ci.family == kFamWg) { L.kind = kLaunchWg; size_launch(&L, counts[k], occ.cls[k]); }      // one pair per workgroup, no scratch strips
+      if (ci.family == kFamShare) { L.kind = kLaunchFamily; L.W = 0; size_launch(&L, blocks_of((int)d->fams.size()), occ.cls[k]); }   // one family per wavefront at a time
+      else if (ci.family == kFamWg) { L.kind = kLaunchWg; size_launch(&L, counts[k], occ.cls[k]); }      // one pair per workgroup, no scratch strips
       else { L.kind = kLaunchOne; L.n_one = 1; size_launch(&L, blocks_of(counts[k]), occ.cls[k]); }
     }
     S->by_class.push_back(L);
@@ -888,15 +1034,21 @@ void build_schedule(BatchPlan* d, const ClassStats& st, const OccupancyGrids& oc
   // lists' launches -- a handful of pairs, each as long as its longest pair -- run beside the remaining certificate launches
   // instead of behind the last one); a launch over several classes is as long as the longest read of any of them
   for (const Launch& L : S->by_class) {
-    const Launch* G = d->use_plan ? (L.kind == kLaunchWg ? nullptr : &P) : group_of(L);
+    const Launch* G = d->use_plan ? ((L.kind == kLaunchWg || L.kind == kLaunchFamily) ? nullptr : &P) : group_of(L);
     if (!G) S->launches.push_back(L);
     else if (G->cls == L.cls) S->launches.push_back(*G);
   }
   auto longer = [](const Launch& x, const Launch& y) { return x.cmax > y.cmax; };
   std::stable_sort(S->launches.begin(), S->launches.end(), longer);
   std::stable_sort(S->by_class.begin(), S->by_class.end(), longer);
+  // the family launch first: it deals its families out statically, so what its last wavefronts still hold is filled by the plan
+  // kernel's first pairs behind it, not by nothing
+  for (std::vector<Launch>* list : {&S->launches, &S->by_class}) {
+    const auto it = std::find_if(list->begin(), list->end(), [](const Launch& L) { return L.kind == kLaunchFamily; });
+    if (it != list->end()) std::rotate(list->begin(), it, it + 1);
+  }
   for (const std::vector<Launch>* list : {&S->launches, &S->by_class})
-    for (const Launch& L : *list) if (L.kind == kLaunchOne || L.kind == kLaunchPlan) S->max_grid = std::max(S->max_grid, L.grid);
+    for (const Launch& L : *list) if (L.kind == kLaunchOne || L.kind == kLaunchPlan || L.kind == kLaunchFamily) S->max_grid = std::max(S->max_grid, L.grid);   // (the family launch: its exact bodies index the strips by workgroup)
   // exact kernels: launched only when some pair of the plan can land in their list
   for (int c = 0; c < kNumExact; ++c) {
     if (d->xcand[c] <= 0) continue;
@@ -969,7 +1121,7 @@ int ltr_debug_class_info(int k, int* family, int* strip_width, int* waves_per_pa
     return LTR_OK;
   }
   const ltrp::ClassInfo ci = ltrp::class_info(k);
-  if (family) *family = ci.family;
+  if (family) *family = ci.family == ltrp::kFamShare ? (int)ltrp::kFamWg : ci.family;
   if (strip_width) *strip_width = ci.W;
   if (waves_per_pair) *waves_per_pair = ci.waves;
   if (lanes_per_pair) *lanes_per_pair = ci.family == ltrp::kFamPack ? (1 << ci.lp_shift) : 64 * ci.waves;
@@ -1108,6 +1260,36 @@ int ltr_debug_plan_schedule(const ltr_align_params* p, int mode, int n_cu, const
       const int32_t v[6] = {e.kind, e.W, e.first, e.n_pairs, e.queue_class, e.first_wave};
       std::memcpy(entry + (size_t)i * 6, v, sizeof(v));
     }
+    return LTR_OK;
+  } catch (...) { return LTR_ERR_NOMEM; }
+}
+
+int ltr_debug_plan_families(const ltr_align_params* p, int mode, int n_cu, const ltr_locus_batch* b, const int32_t* knobs, int64_t* out,
+                            int fam_cap, int32_t* fam, double* U, int member_cap, int32_t* member_n, int64_t* member_out) {
+  if (!p || !b || !knobs || !out || n_cu <= 0 || mode < -1 || mode > 8 || fam_cap < 0 || member_cap < 0) return LTR_ERR_INVALID;
+  if ((fam_cap > 0 && (!fam || !U)) || (member_cap > 0 && (!member_n || !member_out))) return LTR_ERR_INVALID;
+  ModelConsts mc;
+  mc.a = p->log_ins_to_ins; mc.b = p->log_ins_to_match; mc.c = p->log_del_to_del; mc.d = p->log_del_to_match;
+  mc.e = p->log_match_to_match; mc.f = p->log_match_to_ins; mc.g = p->log_match_to_del;
+  mc.match = (float)(-0.000100005); mc.mismatch = (float)(-9.0); mc.match_plus_f = 0.f;     // (HapAligner.cpp:260-261; the bound U holds MATCH)
+  try {
+    RawBuf<PairDesc> pairs, sorted; RawBuf<int16_t> key, bin; RawBuf<int32_t> order; RawBuf<uint8_t> read_acgt, hap_acgt;
+    const ltrp::BatchScratch w{pairs, sorted, key, bin, order, read_acgt, hap_acgt};
+    ltr::DebugKnobs dbg;
+    dbg.families = knobs[0]; dbg.family_min_rows = knobs[1];
+    ltrp::BatchPlan d;
+    std::string why;
+    const int rc = ltrp::describe_batch(b, mc, p->indel_flank_len, mode, n_cu, dbg, w, &d, &why);
+    if (rc != LTR_OK) return rc;
+    const int f0 = d.bin_first[ltrp::kFamClass], f1 = d.bin_first[ltrp::kFamClass + 1];
+    out[0] = (int64_t)d.fams.size(); out[1] = d.fam_members; out[2] = f0; out[3] = d.n_pairs;
+    for (int i = 0; i < std::min((int)d.fams.size(), fam_cap); ++i) {
+      const FamilyDesc& f = d.fams[(size_t)i];
+      const int32_t v[6] = {f.first, f.count, f.p, f.W, f.dd_min, f.dd_max};
+      std::memcpy(fam + (size_t)i * 6, v, sizeof(v));
+      U[i] = d.fam_U[(size_t)i];
+    }
+    for (int i = f0; i < f1 && i - f0 < member_cap; ++i) { member_n[i - f0] = sorted[(size_t)i].n; member_out[i - f0] = sorted[(size_t)i].out_idx; }
     return LTR_OK;
   } catch (...) { return LTR_ERR_NOMEM; }
 }

@@ -72,6 +72,7 @@ namespace ltrp {
 //   [kWg4First, +kNumWg4)     one pair per 4-wave workgroup, W = kWg4MinW+j (reads of 1282 .. 5121 bases), LDS hand-off
 //   [kWg8First, +kNumWg8)     one pair per 8-wave workgroup, W = kWg8MinW+j (reads of 5122 .. 10241 bases)
 //   [kWg1First, +kNumWg1)     one pair per 1-wave workgroup, W = j+1: the latency variant for small batches
+//   kFamClass                 members of haplotype families (ltr_dp_family.hpp): a launch of its own, the rows a read's haplotypes share scored once
 // then the exact (redo) kernels, classes kNumFast + kXGeneric .. kXWg8.
 constexpr int kNumBins = kWMax;
 constexpr int kNumPack = kNumPackLp * kPackWMax;
@@ -80,7 +81,8 @@ constexpr int kNumWg1 = kWg1MaxW;
 constexpr int kWg4First = kPackFirst + kNumPack;
 constexpr int kWg8First = kWg4First + kNumWg4;
 constexpr int kWg1First = kWg8First + kNumWg8;
-constexpr int kNumFast = kWg1First + kNumWg1;   // certificate kernel classes
+constexpr int kFamClass = kWg1First + kNumWg1;
+constexpr int kNumFast = kFamClass + 1;         // certificate kernel classes
 constexpr int kNumKernels = kNumFast + kNumExact;
 // control words of a plan: [0, kNumKernels + 1] work queues (the last two: the W = 20 exact launch, the eight-wave list's narrow launch), [kRedoCountSlot, +kNumExact) exact list lengths
 constexpr int kCtrlWords = 256;
@@ -95,13 +97,14 @@ static_assert(kWgStatOff >= kInlineCountOff + kNumExact && kRedoCountSlot + kWgS
 constexpr size_t kPlanBlock = 16384;
 constexpr int kWg4WideMinW = 15;               // (ltr_plan.cpp, make_rules)
 constexpr int kFoldRounds = 6;                 // automatic mode: classes below 6 x 4 x (pairs per wave) x CUs pairs are folded (tests/manual/gpu_fold_sweep.py)
-enum { kFamOne = 0, kFamPack = 1, kFamWg = 2, kFamExact = 3 };
+enum { kFamOne = 0, kFamPack = 1, kFamWg = 2, kFamExact = 3, kFamShare = 4 };   // (kFamShare: kFamClass; the C-ABI lists it with the workgroup family -- a launch beside the plan kernel)
 struct ClassInfo { int family; int W; int waves; int lp_shift; };   // waves per pair (workgroup kernels); lanes per pair = 1 << lp_shift (pack)
 inline ClassInfo class_info(int k) {
   if (k < kPackFirst) return {kFamOne, k + 1, 1, 6};
   if (k < kWg4First) { const int j = k - kPackFirst; return {kFamPack, j % kPackWMax + 1, 1, kPackMinShift + j / kPackWMax}; }
   if (k < kWg8First) return {kFamWg, k - kWg4First + kWg4MinW, 4, 6};
   if (k < kWg1First) return {kFamWg, k - kWg8First + kWg8MinW, 8, 6};
+  if (k == kFamClass) return {kFamShare, 0, 1, 6};              // (strip width per family: the read's)
   return {kFamWg, k - kWg1First + 1, 1, 6};
 }
 inline int pack_class(int lp_shift, int W) { return kPackFirst + (lp_shift - kPackMinShift) * kPackWMax + (W - 1); }
@@ -205,7 +208,30 @@ struct __attribute__((visibility("hidden"))) BatchPlan {
   bool uses_wg = false;                 // some pairs sit in workgroup-kernel classes (symmetric models only)
   bool use_plan = false;                // the plan kernel (ltr_dp_plan.hpp) scores the one-wave and packed classes
   bool use_multi = false;               // ... or the multi-width launches do
+  // haplotype families (form_families), in the order of their members in the sorted pair list: by modelled cost, largest first
+  std::vector<FamilyDesc> fams;
+  std::vector<double> fam_U;            // per family: the acceptance bound the host filtered its members with (the device forms its own)
+  int64_t fam_members = 0;
 };
+constexpr int kFamPerCu = 12;           // by rule a batch forms families from this many per CU up: one for every wavefront of the family launch's full grid (form_families)
+constexpr int kFamMinRows = 64;         // fewest shared rows a family is formed for (ltr_ctx_set_debug "family_min_rows")
+// Haplotype families (ltr_dp_family.hpp).  A family is the pairs of one pooled read against two or more haplotypes of its locus whose
+// windows share their first rows; its fork row p = min(longest common prefix of the members' WINDOWS, smallest n - 1), so that every
+// tail has a row.  A pair is a member only as a one-wave pair of ONE column block (641 .. 1280 read columns) that the class rule
+// left in the one-wave class of its own strip width -- no constant score, pure ACGT, not on a risky_dd list -- under the plan kernel
+// and a symmetric model, and only if its score has a chance against the bound U of the fork: the gap its length difference forces,
+// open + (|n - m| - 1) x extend in exact doubles, must be > U = ((g + lpc[p-1]) + d) + MATCH, or the device's acceptance rule is
+// certain to send it to the exact body.  A family is formed when p >= min_rows and its modelled steps, (p-1 + L-1) + sum(n_h - p +
+// L-1), are fewer than the members' own, sum(n_h - 1 + L-1) (L lanes; both x the same strip cost), and when the batch holds at least
+// kFamPerCu families per CU (below that the plan kernel, which spreads the pairs over idle wave slots, is faster: measured); knob 1: whenever p allows.
+// Members move to kFamClass with ONE launch-order key per family (its modelled cost): the class sort keeps the input order inside
+// a key, so a family's members stay side by side, and lists the families largest first.
+struct FamilyRec {
+  int64_t first_pair; FamilyDesc f; double U;        // (first_pair: in batch order, before the sort)
+  int64_t row_at; uint64_t members; int16_t key;     // the read's first pair in batch order, its member pairs from there as bits, their launch-order key
+};
+void form_families(const ltr_locus_batch* b, const ModelConsts& mc, int F, int n_cu, int knob, int min_rows, const std::vector<int64_t>& pair_base,
+                   const BatchScratch& w, std::vector<FamilyRec>* out) __attribute__((visibility("hidden")));
 // Validates the batch, gives every pair its descriptor, class and key, sorts them (w.sorted, w.order, w.key stay valid for the
 // caller) and fills *d.  mode: ltr_ctx_set_pair_packing.  LTR_OK, or LTR_ERR_INVALID with the reason in *err.
 int describe_batch(const ltr_locus_batch* b, const ModelConsts& mc, int indel_flank_len, int mode, int n_cu, const ltr::DebugKnobs& dbg,
@@ -220,7 +246,7 @@ void class_stats(const BatchPlan& d, const BatchScratch& w, ClassStats* st) __at
 // One first-pass launch.  Launches that take several classes -- a packed launch takes every lanes-per-pair class of its strip
 // width; the multi-width launches and the plan kernel take whole families -- use the queue word, the statistics slot and the
 // pair range of ONE of their classes, cls: the widest that has pairs.
-enum LaunchKind { kLaunchOne = 0, kLaunchPack, kLaunchMulti, kLaunchPackMulti, kLaunchPlan, kLaunchWg };
+enum LaunchKind { kLaunchOne = 0, kLaunchPack, kLaunchMulti, kLaunchPackMulti, kLaunchPlan, kLaunchWg, kLaunchFamily };
 struct Launch {
   int kind = kLaunchOne;
   int cls = 0;                 // the class it is launched, timed and reported under
@@ -302,6 +328,12 @@ int ltr_debug_describe_batch(const ltr_align_params* p, int mode, int n_cu, cons
                              int32_t* class_first, int64_t pair_cap, int32_t* pair_n, int32_t* pair_m, int64_t* pair_out_idx, int16_t* pair_key,
                              char* err, int err_cap);
 int ltr_debug_threshold_groups(const int32_t* class_first, int merge, int keep_waves, int32_t* nw, int32_t* w, int32_t* np);
+// ltr_debug_plan_families: describe_batch with knobs[2] = families (-1 never, 0 by rule, 1 whenever one can be formed), family_min_rows
+// (0: the rule's).  out[4] = families, members, first sorted pair of the family class, pairs of the batch; per family 6 words in
+// fam[fam_cap][6] = first member (sorted pair), members, p, strip width, dd_min, dd_max, and its bound in U[]; per sorted pair of the
+// family class (from out[2] on) its window length in member_n[member_cap] and its LL index in member_out[].
+int ltr_debug_plan_families(const ltr_align_params* p, int mode, int n_cu, const ltr_locus_batch* b, const int32_t* knobs, int64_t* out,
+                            int fam_cap, int32_t* fam, double* U, int member_cap, int32_t* member_n, int64_t* member_out);
 }
 
 #endif

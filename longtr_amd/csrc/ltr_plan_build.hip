@@ -38,12 +38,13 @@ void release_plan_buffers(ltr_plan* plan, ltr_ctx* ctx) {
   plan->streams.clear();
   void** bufs[] = {(void**)&plan->d_reads, (void**)&plan->d_haps, (void**)&plan->d_hap_codes, (void**)&plan->d_pairs,
                    (void**)&plan->d_ll, (void**)&plan->d_queue, (void**)&plan->d_scratch, (void**)&plan->d_redo_list,
-                   (void**)&plan->d_ctrl_init, (void**)&plan->d_redo_init, (void**)&plan->d_pk_tabs, (void**)&plan->d_pl_entries, (void**)&plan->d_wave_clock};
+                   (void**)&plan->d_ctrl_init, (void**)&plan->d_redo_init, (void**)&plan->d_pk_tabs, (void**)&plan->d_pl_entries, (void**)&plan->d_wave_clock,
+                   (void**)&plan->d_fams, (void**)&plan->d_fam_park, (void**)&plan->d_fam_stats};
   if (plan->d_block || plan->h_ll) {
-    // a compact plan: one block holds every array but the scratch strips; the scores are a pinned block of the context
-    void* const scr = plan->d_scratch;
+    // a compact plan: one block holds every array but the scratch strips and the family launch's; the scores are a pinned block of the context
+    void* const scr = plan->d_scratch; void* const fm = plan->d_fams; void* const fp = plan->d_fam_park; void* const fs = plan->d_fam_stats;
     for (void** p : bufs) *p = nullptr;
-    plan->d_scratch = (double*)scr;
+    plan->d_scratch = (double*)scr; plan->d_fams = (FamilyDesc*)fm; plan->d_fam_park = (double*)fp; plan->d_fam_stats = (uint32_t*)fs;
     if (ctx) ctx->pool.release(plan->d_block); else if (plan->d_block) (void)hipFree(plan->d_block);
     plan->d_block = nullptr;
     ctx_give_pinned(ctx, plan->h_ll);
@@ -81,7 +82,8 @@ static hipError_t ctx_query_grids(ltr_ctx* ctx) {
   for (int k = 0; k < kNumFast; ++k) {
     const ClassInfo ci = class_info(k);
     int per_cu = 0;
-    GRID_TRY(ci.family == kFamOne ? ltrk::occ_onewave(ci.W, &per_cu) : (ci.family == kFamPack ? ltrk::occ_pack(ci.W, &per_cu) : ltrk::occ_wg(ci.waves, ci.W, &per_cu)));
+    GRID_TRY(ci.family == kFamOne ? ltrk::occ_onewave(ci.W, &per_cu) : (ci.family == kFamPack ? ltrk::occ_pack(ci.W, &per_cu)
+             : (ci.family == kFamShare ? ltrk::occ_family(&per_cu) : ltrk::occ_wg(ci.waves, ci.W, &per_cu))));
     ctx->full_grid[k] = std::max(per_cu, 1) * ctx->n_cu;
   }
   {
@@ -356,6 +358,17 @@ int PlanBuild::size_scratch_and_fan() {
     plan->sched.cap_grids(cap);
     plan->scratch_lane_stride = (size_t)plan->sched.max_grid * kBlockWaves * 6 * (size_t)plan->scratch_stride;
     PLAN_TRY(ctx->pool.alloc((void**)&plan->d_scratch, plan->scratch_lane_stride * sizeof(double) * ((size_t)plan->fan_lanes + 1)));   // (+ 1: the kXLong exact launch, see ltr_plan_execute)
+    // the family launch: its list, a parking block per wavefront of ITS grid (as capped above), its counters
+    if (!plan->fams.empty()) {
+      int fam_grid = 1;
+      for (const Launch& L : plan->sched.launches) if (L.kind == kLaunchFamily) fam_grid = std::max(fam_grid, L.grid);
+      for (const Launch& L : plan->sched.by_class) if (L.kind == kLaunchFamily) fam_grid = std::max(fam_grid, L.grid);
+      PLAN_TRY(ctx->pool.alloc((void**)&plan->d_fams, plan->fams.size() * sizeof(FamilyDesc)));
+      PLAN_TRY(hipMemcpy(plan->d_fams, plan->fams.data(), plan->fams.size() * sizeof(FamilyDesc), hipMemcpyHostToDevice));
+      PLAN_TRY(ctx->pool.alloc((void**)&plan->d_fam_park, (size_t)fam_grid * kBlockWaves * kFamilyParkDoubles * sizeof(double)));
+      PLAN_TRY(ctx->pool.alloc((void**)&plan->d_fam_stats, 4 * sizeof(uint32_t)));
+      PLAN_TRY(hipMemset(plan->d_fam_stats, 0, 4 * sizeof(uint32_t)));
+    }
     if (plan->fan_lanes > 1) {
       PLAN_TRY(hipEventCreateWithFlags(&plan->ev_fork, hipEventDisableTiming));
       for (int k = 0; k < 3; ++k) PLAN_TRY(hipEventCreateWithFlags(&plan->ev_join[k], hipEventDisableTiming));

@@ -119,7 +119,7 @@ int Execute::snapshot_tables() {
   for (int r = 0; r < 5; ++r) { A.pk_shift[r] = kPackMaxShift; A.pk_first[r] = 0; A.pk_end[r] = 0; A.pk_grp_end[r] = 0; }
   // symmetric indel model (ins->match == del->match, match->ins == match->del): 11-op cell body
   sym = (A.mc.b == A.mc.d) && (A.mc.f == A.mc.g);
-  if (plan->uses_wg && !sym) {
+  if ((plan->uses_wg || !plan->fams.empty()) && !sym) {
     ltr::set_error(ctx, "the alignment parameters changed from a symmetric to an asymmetric indel model after this plan was created: create it again");
     return LTR_ERR_INVALID;
   }
@@ -152,6 +152,7 @@ int Execute::reset_control_words() {
       HIP_TRY(ctx, hipMemcpyAsync(A.xlist[c] + at, plan->d_redo_init + (plan->bin_first[kNumFast + c] - plan->bin_first[kNumFast]),
                                   (size_t)plan->x_seed[c] * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     }
+  if (plan->d_fam_stats) HIP_TRY(ctx, hipMemsetAsync(plan->d_fam_stats, 0, 4 * sizeof(uint32_t), st));
   if (!A.xlut) {
     // ... and the generic list's length is the sum of the seeds (one word, rewritten after the control block reset)
     uint32_t tot = 0;
@@ -293,6 +294,12 @@ int Execute::launch_class(const Launch& L, int li) {
       ltrk::launch_multi(sym, grid, ls, A);
       break;
     case kLaunchOne: ltrk::launch_onewave(L.W, sym, grid, ls, A); break;
+    case kLaunchFamily: {
+      FamilyArgs FA;
+      FA.fams = plan->d_fams; FA.n_fams = (int32_t)plan->fams.size(); FA.reserved = 0; FA.park = plan->d_fam_park; FA.stats = plan->d_fam_stats;
+      ltrk::launch_family(grid, ls, A, FA);
+      break;
+    }
     case kLaunchPack:
       ltrp::pack_ranges(plan->bin_first, L.W, A.pk_shift, A.pk_first, A.pk_end, A.pk_grp_end);
       ltrk::launch_pack(L.W, sym, grid, ls, A);
@@ -361,9 +368,13 @@ int Execute::run() {
         }
     }
   }
+  size_t rr = 0;
   for (size_t p = 0; p < big.size(); ++p) {
     // (round-robin; giving every launch to the stream with less work queued so far measured 0.4 % slower)
-    const int rc2 = launch_class(*big[p], (int)(p % (size_t)nb));
+    // (the family launch and the launch behind it -- the plan kernel -- share a stream: two persistent launches side by side would
+    // halve each other's wave slots from the start)
+    const int rc2 = launch_class(*big[p], (int)(rr % (size_t)nb));
+    if (big[p]->kind != kLaunchFamily) ++rr;
     if (rc2 != LTR_OK) return rc2;
     if (plan->timing) HIP_TRY(ctx, hipEventRecord(plan->bin_ev[++o], st));
     // exact lists nothing still to come can feed: the next class holds only shorter reads than the list takes
@@ -498,6 +509,7 @@ int ltr_plan_kernel_stats(ltr_plan* plan, int k, int* strip_width, int64_t* n_pa
   if (!ctx) return LTR_ERR_INVALID;                          // the context was destroyed before this plan
   const bool redo = (k >= kNumFast);
   const int xc = k - kNumFast;
+  static_assert(kNumKernels == kNumFast + kNumExact, "the classes behind the certificate classes are the exact lists");
   static const int kXW[kNumExact] = {kExactW, kXShortW, kXMidW, kXLongW, 0, 0};     // (workgroup exact kernels pick the width per pair)
   if (strip_width) *strip_width = redo ? kXW[xc] : class_info(k).W;
   // a launch that scores several classes -- every lanes-per-pair block of a packed strip width, a multi-width launch, the plan
@@ -530,6 +542,21 @@ int ltr_plan_kernel_ranges(ltr_plan* plan, int k, int32_t* lanes_per_pair, int32
   const std::vector<Launch>& list = plan->sched.at_level(plan->timed);
   const int o = Schedule::find(list, k);
   return o < 0 ? 0 : plan->sched.ranges(list[(size_t)o], plan->bin_first, lanes_per_pair, strip_width, n_pairs);
+}
+
+int ltr_plan_family_stats(ltr_plan* plan, int64_t* out5) {
+  if (!plan || !out5) return LTR_ERR_INVALID;
+  ltr_ctx* ctx = plan->ctx;
+  if (!ctx) return LTR_ERR_INVALID;                          // the context was destroyed before this plan
+  out5[0] = (int64_t)plan->fams.size(); out5[1] = plan->fam_members; out5[2] = out5[3] = out5[4] = 0;
+  if (plan->executed && plan->d_fam_stats) {
+    uint32_t c[4] = {0};
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(plan->last_stream));
+    HIP_TRY(ctx, hipMemcpy(c, plan->d_fam_stats, sizeof(c), hipMemcpyDeviceToHost));
+    out5[2] = c[0]; out5[3] = c[1]; out5[4] = c[2];
+  }
+  return LTR_OK;
 }
 
 int ltr_plan_kernel_class(const ltr_plan* plan) {
