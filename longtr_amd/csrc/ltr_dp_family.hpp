@@ -5,10 +5,13 @@
 // read against every candidate haplotype of its locus (:840-852), and the windows of a locus are the same bytes from their first
 // base -- left flank, pad, the repeat up to the shortest allele -- to the row where the alleles fork.
 //
-// Geometry.  A family (FamilyDesc, built on the host: ltrp::form_families) is one read of 641 .. 1280 columns -- ONE column block
-// of one wavefront, strips of W = ceil(C / 64) columns -- and its member pairs, contiguous in the sorted pair list, with the fork
-// row p <= every member's n - 1.  The wavefront runs the STEM, rows 1 .. p-1, once; parks the carried state of row p-1 (X and Y
-// of every column: 2W doubles a lane) in a block of its own; and runs one TAIL per member, rows p .. n_h - 1, from that state.
+// Geometry.  A family (FamilyDesc, built on the host: ltrp::form_families) is one read of 321 .. 1280 columns -- ONE column block
+// of one wavefront, strips of W = ceil(C / 64) columns on L = ceil(C / W) <= 64 lanes -- and its member pairs, contiguous in the
+// sorted pair list, with the fork row p <= every member's n - 1.  Two bands of read length, one geometry: 641 .. 1280 columns
+// (W 11 .. 20: pairs that were one-wave pairs of the same strips) and 321 .. 640 columns (W 6 .. 10: pairs that were packed two to a
+// wavefront on strips of 11 .. 20, which as a family trade half a wavefront each for the shared rows).
+// The wavefront runs the STEM, rows 1 .. p-1, once; parks the carried state of row p-1 (X and Y of every column: 2W doubles a
+// lane) in a block of its own; and runs one TAIL per member, rows p .. n_h - 1, from that state.
 // The body is column_block<W, true, kModeCert, true, true> (ltr_dp_kernel.hpp) with a row base: same cell, same operation order.
 //
 // Exactness.  Row 0 is NOT shared: the reference indexes the haplotype with the READ index there (:268), so M(0, j) for j >= p
@@ -21,6 +24,9 @@
 //     (lpc decreases), and any path through one ends <= U.
 // A member whose shared score S > U (strictly), with every certificate passed, therefore has the reference's score bit for bit;
 // any other member is scored again, unshared, by the exact body (redo_dispatch, from the kernel).
+// Nothing in this argument depends on W: the narrow band (W 6 .. 10) is exact by the same three facts -- the lowered row-0 cells,
+// the acceptance rule S > U, the stem certificate against the member furthest from the diagonal -- and redo_dispatch takes every
+// C <= 1280.
 //
 // The stem's certificate must hold for every member: thr(k) grows with |k|, k = dd - i + j, and |k| over dd_min .. dd_max is
 // largest at an end, so the stem tests against max(|k(dd_min)|, |k(dd_max)|).
@@ -233,7 +239,7 @@ __device__ __forceinline__ int family_walk(const KernelArgs& A, const FamilyArgs
 // come from the kernel's own argument segment, the LDS tables travel as LDS addresses); a leaf: the exact bodies of the members
 // it notes are called from the kernel (ltr_dp_plan.hpp's reasons).
 template <int W>
-__device__ __attribute__((noinline)) int family_walk_call(int64_t kernarg_v, int fi_v, unsigned emit_lds_v, unsigned note_lds_v) {
+__device__ __forceinline__ int family_walk_from_kernarg(int64_t kernarg_v, int fi_v, unsigned emit_lds_v, unsigned note_lds_v) {
   const KernelArgs& A = *(const KernelArgs*)(KernArgPtr)(uintptr_t)uni64(kernarg_v);
   const FamilyArgs& F = *(const FamilyArgs*)(FamArgPtr)(uintptr_t)(uni64(kernarg_v) + (int64_t)kFamilyArgsOffset);
   const int lane = threadIdx.x & 63;
@@ -242,6 +248,14 @@ __device__ __attribute__((noinline)) int family_walk_call(int64_t kernarg_v, int
   int* note = (int*)(LdsInts)(uintptr_t)(unsigned)uni((int)note_lds_v);
   double* park = F.park + ((size_t)blockIdx.x * kBlockWaves + wave) * (size_t)kFamilyParkDoubles;
   return family_walk<W>(A, F, uni(fi_v), lane, emit_tab, note, park);
+}
+template <int W>                                               // the wide band: W 11 .. 20
+__device__ __attribute__((noinline)) int family_walk_call(int64_t kernarg_v, int fi_v, unsigned emit_lds_v, unsigned note_lds_v) {
+  return family_walk_from_kernarg<W>(kernarg_v, fi_v, emit_lds_v, note_lds_v);
+}
+template <int W>                                               // the narrow band: W 6 .. 10, the same walk ([2W][64] of the same park block)
+__device__ __attribute__((noinline)) int family_narrow_call(int64_t kernarg_v, int fi_v, unsigned emit_lds_v, unsigned note_lds_v) {
+  return family_walk_from_kernarg<W>(kernarg_v, fi_v, emit_lds_v, note_lds_v);
 }
 
 // Persistent: the families are dealt STATICALLY, wavefront w of G takes families w, 2G-1-w, 2G+w, .. of the list (sorted by
@@ -270,6 +284,11 @@ __global__ __launch_bounds__(64 * kBlockWaves, 3) void ltr_dp_family_kernel(Kern
     const int w = uni(F.fams[fi].W);
     int noted;
     switch (w) {
+      case 6: noted = family_narrow_call<6>(kargs, fi, emit_lds, note_lds); break;
+      case 7: noted = family_narrow_call<7>(kargs, fi, emit_lds, note_lds); break;
+      case 8: noted = family_narrow_call<8>(kargs, fi, emit_lds, note_lds); break;
+      case 9: noted = family_narrow_call<9>(kargs, fi, emit_lds, note_lds); break;
+      case 10: noted = family_narrow_call<10>(kargs, fi, emit_lds, note_lds); break;
       case 11: noted = family_walk_call<11>(kargs, fi, emit_lds, note_lds); break;
       case 12: noted = family_walk_call<12>(kargs, fi, emit_lds, note_lds); break;
       case 13: noted = family_walk_call<13>(kargs, fi, emit_lds, note_lds); break;

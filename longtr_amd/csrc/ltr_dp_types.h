@@ -122,7 +122,8 @@ struct FamilyArgs {        // the family kernel's second argument (KernelArgs st
   uint32_t* stats;         // [0] families whose stem certificate failed, [1] members the acceptance rule sent to the exact body, [2] members whose tail certificate failed
 };
 constexpr int kFamilyMaxMembers = 32;            // members of a family (the wave's note list)
-constexpr int kFamilyMinC = 641, kFamilyMaxC = 64 * LTR_WMAX;   // read columns of a family: one wavefront, one column block, strips of 11 .. 20
+constexpr int kFamilyMinC = 641, kFamilyMaxC = 64 * LTR_WMAX;   // read columns of a family of the wide band: one wavefront, one column block, strips of 11 .. 20
+constexpr int kFamilyNarrowMinC = 321, kFamilyNarrowMaxC = 640; // ... and of the narrow band: the same geometry with strips of 6 .. 10 -- reads the class rule packs two to a wavefront
 constexpr int kFamilyParkDoubles = 2 * LTR_WMAX * 64;
 constexpr int kFamilyArgsOffset = (int)((sizeof(KernelArgs) + alignof(FamilyArgs) - 1) / alignof(FamilyArgs) * alignof(FamilyArgs));   // where FamilyArgs sits in the kernel's argument segment
 constexpr int kInlineCountOff = 8;                // xcount[kInlineCountOff + c]: pairs of exact class c the plan kernel scored in line (statistics)

@@ -254,7 +254,7 @@ struct DebugKnobs {
   int prep_ahead = 0;           // ltr_calc_hap_aln_probs: -1 = chunk c + 1 is pooled, trimmed and laid out only after chunk c's launches are queued (as before round 5); n > 0: the helper thread on, with n threads of its own; rule: on from a host-thread budget of kPrepAheadMinThreads, with the whole budget
   int trace = 0;                // ltr_calc_hap_aln_probs prints a timestamped phase profile to stderr
   int64_t ll_chunk_loci = 0;    // ltr_ll_genotype: loci per upload chunk (rule: as many as fit 8 MB of staging)
-  int families = 0;             // haplotype families (ltr_dp_family.hpp): -1 = never, 0 = by rule (where modelled cheaper), 1 = whenever one can be formed
+  int families = 0;             // haplotype families (ltr_dp_family.hpp): -1 = never, 0 = by rule (where modelled cheaper), 1 = whenever one can be formed from reads of 641 .. 1280 columns, 2 = ... of 321 .. 1280
   int family_min_rows = 0;      // ... fewest shared rows (0: ltrp::kFamMinRows)
 };
 DebugKnobs ctx_debug(const ltr_ctx* ctx);

@@ -442,15 +442,21 @@ void form_families(const ltr_locus_batch* b, const ModelConsts& mc, const int F,
       at += n_here;
       const int64_t m = b->read_off[r + 1] - b->read_off[r];
       const int C = (int)m - 1;
-      if (C < kFamilyMinC || C > kFamilyMaxC) continue;
+      // the narrow band: by rule and on request 2 (knob 1 keeps to the wide band)
+      const bool narrow = C >= kFamilyNarrowMinC && C <= kFamilyNarrowMaxC && (knob == 0 || knob >= 2);
+      if (!narrow && (C < kFamilyMinC || C > kFamilyMaxC)) continue;
       const int W = (C + 63) / 64, L = (C + W - 1) / W;
-      // candidates: what the class rule left in the one-wave class of the read's own strip width, with a DP to run
+      // (the narrow band's pairs as the class rule packs them: two to a wavefront, 32 lanes of Wp columns)
+      const int Wp = (C + (1 << kPackMaxShift) - 1) >> kPackMaxShift, Lp = (C + Wp - 1) / Wp;
+      const int own_cls = narrow ? pack_class(kPackMaxShift, Wp) : W - 1;
+      // candidates: what the class rule left in the one-wave class of the read's own strip width -- the narrow band: in the packed
+      // class of 32 lanes; on request 2 also in the one-wave class, where a batch too small to pack leaves them --, with a DP to run
       int cand_h[kMaxH]; int64_t cand_i[kMaxH]; int nc = 0;
       {
         int64_t i = row_at;
         for (int64_t h = h0; h < h1; ++h) {
           if (b->realign_hap && !b->realign_hap[h]) continue;
-          if (bin[(size_t)i] == W - 1 && key[(size_t)i] > 0 && pairs[(size_t)i].generic == 0 && pairs[(size_t)i].n >= 2) { cand_h[nc] = (int)(h - h0); cand_i[nc] = i; ++nc; }
+          if ((bin[(size_t)i] == own_cls || (narrow && knob >= 2 && bin[(size_t)i] == W - 1)) && key[(size_t)i] > 0 && pairs[(size_t)i].generic == 0 && pairs[(size_t)i].n >= 2) { cand_h[nc] = (int)(h - h0); cand_i[nc] = i; ++nc; }
           ++i;
         }
       }
@@ -497,7 +503,16 @@ void form_families(const ltr_locus_batch* b, const ModelConsts& mc, const int F,
         fam_steps += (n - p) + (L - 1); own_steps += (n - 1) + (L - 1);
         dd_min = std::min(dd_min, n - (int)m); dd_max = std::max(dd_max, n - (int)m);
       }
-      if (knob <= 0 && fam_steps >= own_steps) continue;
+      if (!narrow) {
+        if (knob <= 0 && fam_steps >= own_steps) continue;
+      } else if (knob <= 0) {
+        // the geometries differ, so modelled WORK is compared, not steps: the family's steps on a whole wavefront of strips of W
+        // against the members' own steps on half a wavefront of strips of Wp (formed here rather than read back from the pairs'
+        // launch-order keys, which hold the packed cost only to 1/16 octave)
+        double own_work = 0.0;
+        for (int k = 0; k < nc; ++k) own_work += (double)((wn[cand_h[k]] - 1) + (Lp - 1)) * ((double)Wp + kStepOverhead) * (double)(1 << kPackMaxShift) / 64.0;
+        if ((double)fam_steps * ((double)W + kStepOverhead) >= own_work) continue;
+      }
       const double c = (double)fam_steps * (W + kStepOverhead);
       const int16_t fkey = (int16_t)std::min(511, std::max(1, (c > 1.0 ? (int)(std::log2(c) * 16.0) : 0) - 16));
       FamilyRec rec;
@@ -513,9 +528,17 @@ void form_families(const ltr_locus_batch* b, const ModelConsts& mc, const int F,
   // a family lasts as long as ~H pairs on one wave slot, and the families are dealt out statically.  Measured on MI355X (config-3 loci,
   // families on request against none, kernel ms per pass): 16 families 1.52 against 0.38, 272 families 2.37 against 1.07, 533 families
   // (4311 pairs) 2.04 against 1.40 -- the pass stays one family long while the plan kernel spreads the same pairs over idle wave slots.
-  // By rule: from a family for every wavefront of a full grid up (kFamPerCu per CU: three workgroups of four); knob 1: whenever one can
-  // be formed.
-  if (knob <= 0 && (int64_t)out->size() < (int64_t)kFamPerCu * std::max(n_cu, 1)) out->clear();
+  // By rule: from a family for every wavefront of a full grid up (kFamPerCu per CU: three workgroups of four); knobs 1 and 2: whenever
+  // one can be formed.  The narrow band by rule only when its families ALONE are a full grid's worth: below that a plan keeps the
+  // launches it had -- its packed pairs stay with the plan kernel, its wide families are counted as before -- so that a plan of a few
+  // hundred loci runs exactly as it did without the band (a 300-locus plain run of config 3 on 256 CUs: 2271 narrow families, not
+  // formed; 625 loci: 4571, formed).  Then both bands together against the same count.
+  if (knob <= 0) {
+    const int64_t want = (int64_t)kFamPerCu * std::max(n_cu, 1);
+    const auto is_narrow = [](const FamilyRec& r) { return r.f.W * 64 <= kFamilyNarrowMaxC; };
+    if ((int64_t)std::count_if(out->begin(), out->end(), is_narrow) < want) out->erase(std::remove_if(out->begin(), out->end(), is_narrow), out->end());
+    if ((int64_t)out->size() < want) out->clear();
+  }
   ltr::parallel_for((int64_t)out->size(), 256, [&](int64_t i) {
     const FamilyRec& r = (*out)[(size_t)i];
     for (uint64_t rest = r.members; rest; rest &= rest - 1) {

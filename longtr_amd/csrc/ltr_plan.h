@@ -226,6 +226,14 @@ constexpr int kFamMinRows = 64;         // fewest shared rows a family is formed
 // kFamPerCu families per CU (below that the plan kernel, which spreads the pairs over idle wave slots, is faster: measured); knob 1: whenever p allows.
 // Members move to kFamClass with ONE launch-order key per family (its modelled cost): the class sort keeps the input order inside
 // a key, so a family's members stay side by side, and lists the families largest first.
+// The NARROW band is the same family on the same geometry -- strips of W = ceil(C / 64) = 6 .. 10 on ceil(C / W) <= 64 lanes of one
+// wavefront -- for reads of 321 .. 640 columns (what is said above describes the WIDE band, 641 .. 1280).  By rule its members are the pairs the
+// class rule put into the packed class of 32 lanes (a batch too small to pack forms none), and since a packed pair holds half a
+// wavefront of strips of Wp = ceil(C / 32) columns the cost rule compares modelled work, not steps: fam_steps x (W + 1.5) against
+// sum((n_h - 1) + (Lp - 1)) x (Wp + 1.5) x 32/64, Lp = ceil(C / Wp).  The count rule: narrow families are formed only when they alone number
+// kFamPerCu per CU (a smaller plan keeps the launches it had); then both bands together are held against the same count, as before.  Knob 1 forms no
+// narrow family; knob 2 is "on request" in both bands: no cost rule, no count rule, and narrow candidates also from the one-wave
+// class of their strip width (where a batch that does not pack leaves them).
 struct FamilyRec {
   int64_t first_pair; FamilyDesc f; double U;        // (first_pair: in batch order, before the sort)
   int64_t row_at; uint64_t members; int16_t key;     // the read's first pair in batch order, its member pairs from there as bits, their launch-order key
@@ -328,7 +336,7 @@ int ltr_debug_describe_batch(const ltr_align_params* p, int mode, int n_cu, cons
                              int32_t* class_first, int64_t pair_cap, int32_t* pair_n, int32_t* pair_m, int64_t* pair_out_idx, int16_t* pair_key,
                              char* err, int err_cap);
 int ltr_debug_threshold_groups(const int32_t* class_first, int merge, int keep_waves, int32_t* nw, int32_t* w, int32_t* np);
-// ltr_debug_plan_families: describe_batch with knobs[2] = families (-1 never, 0 by rule, 1 whenever one can be formed), family_min_rows
+// ltr_debug_plan_families: describe_batch with knobs[2] = families (-1 never, 0 by rule, 1 whenever one can be formed in the wide band, 2 ... in both bands), family_min_rows
 // (0: the rule's).  out[4] = families, members, first sorted pair of the family class, pairs of the batch; per family 6 words in
 // fam[fam_cap][6] = first member (sorted pair), members, p, strip width, dd_min, dd_max, and its bound in U[]; per sorted pair of the
 // family class (from out[2] on) its window length in member_n[member_cap] and its LL index in member_out[].
