@@ -196,7 +196,7 @@ int ltr_plan_debug_entries(const ltr_plan* plan, int32_t* kind, int32_t* strip_w
 
 /* ---- planning units (host only, no GPU needed): which kernel scores a pair, in what order ------------------
  * ltr_plan_create = validate -> one launch class + launch-order key per pair -> counting sort by class, longest
- * first inside a class -> upload.  The rule and the sort are plain host functions (csrc/ltr_plan.cpp); these entry
+ * first inside a class -> upload.  The rule and the sort are plain host functions (csrc/ltr_plan_rules.cpp, ltr_plan_sort.cpp); these entry
  * points expose them to the CPU tests.  They decide scheduling only: every kernel returns the reference's bits
  * (HapAligner.cpp:236-343).
  *   ltr_debug_class_info   family (ltr_kernel_family), strip width, waves per pair, lanes per pair of class k
@@ -295,7 +295,8 @@ int  ltr_ctx_set_stutter_params(ltr_ctx* ctx, const ltr_stutter_params* p);
  *                to 20 columns (else the next wider segment; beyond 641 bases one pair per wavefront)
  * Workgroup kernels exist for symmetric indel models (ins->match == del->match, match->ins ==
  * match->del: the defaults); a plan that uses them must be re-created if ltr_ctx_set_params switches
- * to an asymmetric model (ltr_plan_execute reports LTR_ERR_INVALID otherwise). */
+ * to an asymmetric model (ltr_plan_execute reports LTR_ERR_INVALID otherwise); so must a plan with
+ * haplotype families or, under ltr_ctx_set_debug "chain", with entries of the chained walk. */
 int  ltr_ctx_set_pair_packing(ltr_ctx* ctx, int mode);
 /* Measurement switches (A/B runs, profile collection); results never depend on them; value 0 = the library's rule.
  *   "fan_lanes"      streams the certificate launches of a plan are dealt over (1 .. 4; rule: 2) -- profiles/collect.sh

@@ -65,8 +65,7 @@ void* ctx_side_stream(const ltr_ctx* ctx, int k) { k %= (ltr_ctx::kAux + 1); ret
 
 
 static void fill_model_consts(const ltr_align_params& p, ModelConsts* mc) {
-  mc->a = p.log_ins_to_ins; mc->b = p.log_ins_to_match; mc->c = p.log_del_to_del; mc->d = p.log_del_to_match;
-  mc->e = p.log_match_to_match; mc->f = p.log_match_to_ins; mc->g = p.log_match_to_del;
+  *mc = ltrp::model_consts_from(p);
   mc->match = (float)(-0.000100005);     // float MATCH = -0.000100005;  HapAligner.cpp:261
   mc->mismatch = (float)(-9.0);          // float MISMATCH = -9.0;       HapAligner.cpp:260
   volatile float mf = mc->match + mc->f; // float + float, evaluated in float (HapAligner.cpp:277)

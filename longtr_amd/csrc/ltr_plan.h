@@ -1,12 +1,20 @@
-// ltr_plan.h -- host-side planning of a batch (no HIP in here): the table of launch classes, the rule that
-// gives every (read, haplotype) pair its class and launch-order key, and the sort that lays the pairs out
-// class by class, longest first, and describe_batch, the host half of ltr_plan_create that strings them together
-// and build_schedule, which turns the description into the list of launches (ltr_plan_build.hip adds the grid query and the
-// uploads, ltr_plan_run.hip walks the list); tests/test_plan_units.py exercises them on the CPU through the ltr_debug_* entry points.
+// ltr_plan.h -- host-side planning of a batch (no HIP in here), the one header of these units:
+//   ltr_plan_rules.cpp     what the batch as a whole decides (make_rules), the cost model (pack_cost), the rule that gives every
+//                          (read, haplotype) pair its launch class and launch-order key (classify_pair), build_threshold_table
+//   ltr_plan_sort.cpp      sort_by_class: the pairs class by class, longest first; the fold walk of the under-filled classes
+//   ltr_plan_families.cpp  form_families: haplotype families
+//   ltr_plan_describe.cpp  describe_batch, the host half of ltr_plan_create that strings those together: validation, byte scan,
+//                          one descriptor per pair
+//   ltr_plan_schedule.cpp  class_stats, and build_schedule, which turns the description into the list of launches
+//                          (ltr_plan_build.hip adds the grid query and the uploads, ltr_plan_run.hip walks the list);
+//                          threshold_groups, pack_ranges
+//   ltr_plan_hooks.cpp     the ltr_debug_* entry points tests/test_plan_units.py exercises all of this through, on the CPU
+// A rule that more than one of them states -- or the execute path, or the C-ABI -- is an inline function here.
 #ifndef LTR_PLAN_H_
 #define LTR_PLAN_H_
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <new>
@@ -95,7 +103,7 @@ static_assert(kWgStatOff >= kInlineCountOff + kNumExact && kRedoCountSlot + kWgS
 // pairs per block of the host loops over a plan's pairs (counting sort, gather, class statistics): a 10 000-locus chunk of a
 // catalogue is 235 k pairs -- four blocks of 64 k kept four of the host's cores busy
 constexpr size_t kPlanBlock = 16384;
-constexpr int kWg4WideMinW = 15;               // (ltr_plan.cpp, make_rules)
+constexpr int kWg4WideMinW = 15;               // (ltr_plan_rules.cpp, make_rules)
 constexpr int kFoldRounds = 6;                 // automatic mode: classes below 6 x 4 x (pairs per wave) x CUs pairs are folded (tests/manual/gpu_fold_sweep.py)
 enum { kFamOne = 0, kFamPack = 1, kFamWg = 2, kFamExact = 3, kFamShare = 4 };   // (kFamShare: kFamClass; the C-ABI lists it with the workgroup family -- a launch beside the plan kernel)
 struct ClassInfo { int family; int W; int waves; int lp_shift; };   // waves per pair (workgroup kernels); lanes per pair = 1 << lp_shift (pack)
@@ -125,6 +133,31 @@ inline int length_bucket(int C) {               // quarter octaves of the read's
   const int b = 4 * e + ((C >> (e - 2)) & 3);
   return b < kLengthBuckets ? b : kLengthBuckets - 1;
 }
+
+// ---- rules with more than one user ----------------------------------------------------------------------------------------
+// The seven transitions of a parameter set (the emission constants stay 0: no class rule reads them; ltr_ctx.hip adds them).
+inline ModelConsts model_consts_from(const ltr_align_params& p) {
+  ModelConsts mc;
+  mc.a = p.log_ins_to_ins; mc.b = p.log_ins_to_match; mc.c = p.log_del_to_del; mc.d = p.log_del_to_match;
+  mc.e = p.log_match_to_match; mc.f = p.log_match_to_ins; mc.g = p.log_match_to_del;
+  mc.match = mc.mismatch = mc.match_plus_f = 0.f;
+  return mc;
+}
+// symmetric indel model (ins->match == del->match, match->ins == match->del): the 11-operation cell, every kernel but the generic ones
+inline bool symmetric_model(const ModelConsts& mc) { return (mc.b == mc.d) && (mc.f == mc.g); }
+// Band-penalty bound: the first |k| from which the band penalty (float)|k| * c alone is below -600, in float as the kernels form
+// it (ltr_dp_kernel.hpp, ltr_dp_wg.hpp); kNoK600 where c is too small for any.  The penalty table, the threshold table and the
+// length-sorted exact lists (Rules::xlut, Rules::thr_lists, KernelArgs::xlut, KernelArgs::thr_ok) need it within kPenKMax.
+constexpr int kNoK600 = 0x3fffffff;
+inline int band_k600(float c) { const float cabs = std::fabs(c); return (cabs * 1.0e9f > 600.0f) ? (int)(600.0f / cabs) + 2 : kNoK600; }
+inline bool band_in_table(float c) { return band_k600(c) <= kPenKMax; }
+// per-step overhead of a strip, in cells: steps x (cells of a step + this) is the modelled cost of a pair (classify_pair, form_families)
+constexpr double kStepOverhead = 1.5;
+// launch-order key of a modelled cost: steps of 1/16 octave (4.4 %), 1 .. 511 (a pair that is scored always has a key >= 1 -- key 0
+// marks the constant-score pairs -- however small its cost)
+inline int16_t launch_key(double cost) { return (int16_t)std::min(511, std::max(1, (cost > 1.0 ? (int)(std::log2(cost) * 16.0) : 0) - 16)); }
+// strip width of every exact list's kernel (0: the workgroup exact kernels pick the width per pair)
+constexpr int kXW[kNumExact] = {kExactW, kXShortW, kXMidW, kXLongW, 0, 0};
 
 // What a batch as a whole decides (ltr_ctx_set_pair_packing mode, size of the batch, the indel model).
 struct Rules {

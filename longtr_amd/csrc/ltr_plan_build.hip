@@ -1,4 +1,4 @@
-// ltr_plan_build.hip -- ltr_plan_create / ltr_plan_destroy: what ltrp::describe_batch (ltr_plan.cpp) decided about a batch
+// ltr_plan_build.hip -- ltr_plan_create / ltr_plan_destroy: what ltrp::describe_batch (ltr_plan_describe.cpp) decided about a batch
 // becomes a plan on the device -- the grid query, the launch schedule (ltrp::build_schedule), the upload (one block for a compact
 // plan, separate buffers otherwise), scratch strips and events.  Running a plan: ltr_plan_run.hip.
 
@@ -74,7 +74,7 @@ static void destroy_plan(ltr_plan* plan, const bool ctx_locked) {
   delete plan;
 }
 
-// ---- units of ltr_plan_create (the class rule, the sort, the class statistics and the launch schedule live in ltr_plan.cpp) ----
+// ---- units of ltr_plan_create (the class rule, the sort, the class statistics and the launch schedule live in the ltr_plan_*.cpp units, ltr_plan.h) ----
 
 #define GRID_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return e_; } while (0)
 // Resident workgroups of every launch class (occupancy x CUs), asked from the runtime once per context.

@@ -117,15 +117,17 @@ int Execute::snapshot_tables() {
   A.pl_entries = nullptr; A.pl_n = 0; A.wave_clock = plan->d_wave_clock;
   for (int r = 0; r < kMultiMax; ++r) { A.mk_w[r] = kWMax; A.mk_first[r] = 0; A.mk_np[r] = 0; A.mk_class[r] = 0; }
   for (int r = 0; r < 5; ++r) { A.pk_shift[r] = kPackMaxShift; A.pk_first[r] = 0; A.pk_end[r] = 0; A.pk_grp_end[r] = 0; }
-  // symmetric indel model (ins->match == del->match, match->ins == match->del): 11-op cell body
-  sym = (A.mc.b == A.mc.d) && (A.mc.f == A.mc.g);
-  if ((plan->uses_wg || !plan->fams.empty()) && !sym) {
+  sym = ltrp::symmetric_model(A.mc);
+  // (what only the symmetric instances score: the workgroup classes, the families and the chained walk's entries, which the
+  // general-model plan kernel would drain without scoring)
+  const auto& ents = plan->sched.plan_entries;
+  const bool chained = std::any_of(ents.begin(), ents.end(), [](const PlanEntry& e) { return e.kind == 3; });
+  if ((plan->uses_wg || !plan->fams.empty() || chained) && !sym) {
     ltr::set_error(ctx, "the alignment parameters changed from a symmetric to an asymmetric indel model after this plan was created: create it again");
     return LTR_ERR_INVALID;
   }
   {
-    const float cabs = std::fabs(A.mc.c);
-    const bool pen_ok = (cabs * 1.0e9f > 600.0f) && ((int64_t)(600.0f / cabs) + 2 <= kPenKMax);
+    const bool pen_ok = ltrp::band_in_table(A.mc.c);
     A.xlut = (plan->xlut && sym && pen_ok) ? 1 : 0;           // (parameters may have changed since the plan was binned: then everything goes to the generic exact kernel)
     A.thr_ok = pen_ok ? 1 : 0;                                 // (the threshold table is rebuilt with every parameter set: valid whenever it fits)
     if (!A.xlut) for (int c = 1; c < kNumExact; ++c) A.xlist[c] = A.xlist[kXGeneric];
@@ -510,7 +512,6 @@ int ltr_plan_kernel_stats(ltr_plan* plan, int k, int* strip_width, int64_t* n_pa
   const bool redo = (k >= kNumFast);
   const int xc = k - kNumFast;
   static_assert(kNumKernels == kNumFast + kNumExact, "the classes behind the certificate classes are the exact lists");
-  static const int kXW[kNumExact] = {kExactW, kXShortW, kXMidW, kXLongW, 0, 0};     // (workgroup exact kernels pick the width per pair)
   if (strip_width) *strip_width = redo ? kXW[xc] : class_info(k).W;
   // a launch that scores several classes -- every lanes-per-pair block of a packed strip width, a multi-width launch, the plan
   // kernel -- reports its pairs, cells and time under the class it is listed under (ltr_plan_kernel_ranges names the classes),

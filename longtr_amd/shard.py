@@ -98,7 +98,7 @@ def gather_ll(ll_local, sizes_local, locus_ids_local, group=None, dst=0):
 
 def pair_time_cost(n, C, pairs_in_batch=1 << 21, n_cu=256, params=None):
     """The plan's launch-time model of one pair, asked from the library itself (ltr_debug_pair_costs = ltrp::classify_pair's
-    cost, csrc/ltr_plan.cpp): wavefront steps x (strip width + per-step overhead) x the share of the wavefront the pair holds --
+    cost, csrc/ltr_plan_rules.cpp): wavefront steps x (strip width + per-step overhead) x the share of the wavefront the pair holds --
     the cheapest of one pair per wave, the packed geometries of 2 .. 32 lanes per pair and, for reads beyond 1280 columns, the
     four- / eight-wave workgroup kernels -- for a batch of `pairs_in_batch` pairs on `n_cu` CUs in automatic mode.
     n: haplotype window, C: read columns (read length - 1); numpy arrays broadcast."""

@@ -1,5 +1,5 @@
 // tests/host_sanitize/harness.cpp -- TEST INFRASTRUCTURE.
-// Fuzzes the host-only entry points of the C-ABI library (ltr_host.cpp, ltr_hap_aln.cpp, ltr_genotype.cpp, the planning units of ltr_plan.cpp) under
+// Fuzzes the host-only entry points of the C-ABI library (ltr_host.cpp, ltr_hap_aln.cpp, ltr_genotype.cpp, the planning units of ltr_plan_*.cpp) under
 // AddressSanitizer + UBSan on the CPU: trimming, haplotype enumeration, pooling, scatter, genotype
 // fields, and ltr_process_reads' host half (trim + haplotype strings) up to the point where it
 // would hand the batch to the GPU.  The four library-internal symbols those files need from the HIP

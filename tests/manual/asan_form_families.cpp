@@ -1,7 +1,7 @@
-// Stand-alone host program: ltrp::describe_batch with haplotype families (form_families, csrc/ltr_plan.cpp) on loci whose fork row lies
+// Stand-alone host program: ltrp::describe_batch with haplotype families (form_families, csrc/ltr_plan_families.cpp) on loci whose fork row lies
 // beyond the read -- p up to m + 599 -- for a run under AddressSanitizer / UBSan.  No GPU, no HIP runtime call.
 //   hipcc -x c++ -std=c++17 -O1 -g -fsanitize=address,undefined -pthread -I include tests/manual/asan_form_families.cpp \
-//         longtr_amd/csrc/ltr_plan.cpp -o asan_form_families && ./asan_form_families
+//         longtr_amd/csrc/ltr_plan_*.cpp -o asan_form_families && ./asan_form_families
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -11,7 +11,7 @@
 #include "../../longtr_amd/csrc/ltr_internal.h"
 #include "../../longtr_amd/csrc/ltr_plan.h"
 
-// what ltr_plan.cpp takes from the library's other units
+// what the planning units (ltr_plan_*.cpp) take from the library's other units
 namespace ltrp {
 void* pinned_alloc(size_t) { return nullptr; }
 void pinned_free(void*) {}

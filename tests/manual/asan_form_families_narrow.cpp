@@ -1,9 +1,9 @@
-// Stand-alone host program: ltrp::describe_batch with haplotype families of the narrow band (form_families, csrc/ltr_plan.cpp: reads
+// Stand-alone host program: ltrp::describe_batch with haplotype families of the narrow band (form_families, csrc/ltr_plan_families.cpp: reads
 // of 321 .. 640 columns) by rule (knob 0) and on request (knob 2), on batches large enough to pack -- C = 321 and C = 640, a fork at
 // n - 1, a locus of 64 haplotypes, 33 candidates (one more than a family holds) -- for a run under AddressSanitizer / UBSan.
 // No GPU, no HIP runtime call.
 //   hipcc -x c++ -std=c++17 -O1 -g -fsanitize=address,undefined -pthread -I include tests/manual/asan_form_families_narrow.cpp \
-//         longtr_amd/csrc/ltr_plan.cpp -o asan_form_families_narrow && ./asan_form_families_narrow
+//         longtr_amd/csrc/ltr_plan_*.cpp -o asan_form_families_narrow && ./asan_form_families_narrow
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -13,7 +13,7 @@
 #include "../../longtr_amd/csrc/ltr_internal.h"
 #include "../../longtr_amd/csrc/ltr_plan.h"
 
-// what ltr_plan.cpp takes from the library's other units
+// what the planning units (ltr_plan_*.cpp) take from the library's other units
 namespace ltrp {
 void* pinned_alloc(size_t) { return nullptr; }
 void pinned_free(void*) {}

@@ -21,7 +21,7 @@ def sub_batch(batch, loci_ids, reads_per_locus=None):
 
 
 def read_class(m):
-    """Launch class of a read of length m as the plan bins it (ltrp::describe_batch, ltr_plan.cpp): (lanes per pair, strip width)."""
+    """Launch class of a read of length m as the plan bins it (ltrp::describe_batch, ltr_plan_describe.cpp): (lanes per pair, strip width)."""
     C = max(m - 1, 1)
     if C <= 16 * 8:
         return (16, (C + 15) // 16)

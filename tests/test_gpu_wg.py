@@ -176,6 +176,38 @@ def test_fallbacks_asymmetric_model_and_param_change(gpu_ctx):
     assert np.array_equal(ll.view(np.uint64), want.view(np.uint64))
 
 
+def test_param_change_to_an_asymmetric_model_is_refused_for_a_chained_plan(gpu_ctx):
+    """A plan whose schedule holds entries of the chained walk (ltr_ctx_set_debug "chain"; symmetric models only) is refused under an
+    asymmetric model like a plan with workgroup classes: the general-model plan kernel would drain those entries without scoring
+    their pairs.  One locus, four reads of ~720 bases (strip width 12) against two haplotypes."""
+    rng = np.random.default_rng(37)
+    r0, h0 = _near_pair(rng, 720)
+    reads = [r0] + [_near_pair(rng, 720)[0] for _ in range(3)]
+    haps = [h0, h0[:400] + synth._rand_seq(rng, 9).tobytes() + h0[400:]]
+    b = _abi.PackedBatch([(reads, haps)])
+    asym = _abi.make_params((-1.0, -0.458675, -1.0, -0.458675, -0.00005800168, -10.448214728, -6.0))
+    nk = _lib.lib().ltr_debug_num_classes()
+    sched = _lib.debug_plan_schedule(b, np.full(nk + 3, 1000, dtype=np.int32), n_cu=gpu_ctx.device_info()["n_cu"], chain=1)
+    assert [e["W"] for e in sched["entries"] if e["kind"] == 3] == [12]            # the batch does reach the chained walk
+    gpu_ctx.set_debug("chain", 1)
+    try:
+        plan = gpu_ctx.plan(b)
+    finally:
+        gpu_ctx.set_debug("reset", 0)
+    gpu_ctx.set_params(asym)
+    try:
+        with pytest.raises(_lib.LtrError) as e:
+            plan.execute()
+        assert e.value.code == -1 and "create it again" in str(e.value)
+    finally:
+        gpu_ctx.set_params(_abi.default_params())
+    plan.execute()                               # symmetric again: fine
+    ll, _ = plan.fetch()
+    plan.close()
+    want = np.asarray([ol.oracle_align_long(h, r, gpu_ctx.params, rolling=True) for r in reads for h in haps])
+    assert np.array_equal(ll.view(np.uint64), want.view(np.uint64))
+
+
 def test_two_per_wave_partner_with_a_much_shorter_haplotype_at_the_buffer_end(gpu_ctx):
     """Two pairs of one strip class whose haplotypes differ by several hundred rows share a wavefront
     and run in lock step: the shorter one's row stream runs on past its haplotype -- the LAST one of

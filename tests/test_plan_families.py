@@ -1,4 +1,4 @@
-"""CPU: haplotype families (csrc/ltr_plan.cpp, form_families) on hand-built loci, through ltr_debug_plan_families -- which pairs
+"""CPU: haplotype families (csrc/ltr_plan_families.cpp, form_families) on hand-built loci, through ltr_debug_plan_families -- which pairs
 of a read become members, the fork row p, the acceptance bound U the host filters with.  What a family decides is HOW its members
 are scored (shared rows once, ltr_dp_family.hpp), never the score: tests/test_gpu_families.py pins that to the oracle."""
 import numpy as np

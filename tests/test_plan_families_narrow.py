@@ -1,4 +1,4 @@
-"""CPU: haplotype families of reads of 321 .. 640 columns (csrc/ltr_plan.cpp, form_families: the narrow band, strips of 6 .. 10 on one
+"""CPU: haplotype families of reads of 321 .. 640 columns (csrc/ltr_plan_families.cpp, form_families: the narrow band, strips of 6 .. 10 on one
 wavefront) on hand-built loci, through ltr_debug_plan_families.  By rule only pairs a 32-lane packed class holds become members, and
 a family is formed when its modelled work, steps x (W + 1.5), is less than its members' packed work, and when the batch holds twelve
 narrow families per CU; knob 2 forms them on request,

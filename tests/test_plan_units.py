@@ -1,4 +1,4 @@
-"""CPU: the planning units of ltr_plan_create (csrc/ltr_plan.cpp) through their ltr_debug_* entry points -- the table of
+"""CPU: the planning units of ltr_plan_create (csrc/ltr_plan_*.cpp, one header: csrc/ltr_plan.h) through their ltr_debug_* entry points -- the table of
 launch classes, the rule that gives a pair its class and launch-order key, the class sort with folding.  They decide
 WHICH kernel scores a pair and in what order, never the score (the GPU tests run every case in ten scheduling modes)."""
 import ctypes as C
@@ -185,6 +185,119 @@ def test_folding_of_the_workgroup_families():
     cls = np.array([last4] * 10 + [last4 + 1] * 10, dtype=np.int16)              # the widest four-wave class next to the narrowest eight-wave one
     _, first = _sort(cls, np.ones(len(cls), dtype=np.int16), fold=True)
     assert first[last4 + 1] - first[last4] == 10
+
+
+# The fold walk, family by family: hand-made class counts as ((family, strip width, lanes per pair), pairs).  256 CUs, kFoldRounds 6:
+# a one-wave or packed width folds below 6144 wavefronts, a workgroup class below 1536 pairs.
+ONE, PK, WG4, WG8 = (lambda W: (0, W, 64)), (lambda W, lanes: (1, W, lanes)), (lambda W: (2, W, 256)), (lambda W: (2, W, 512))
+FOLD_CASES = {
+    # a chain of three under-filled neighbours folds twice (below and inside the widths of the multi-width launch, which fold 2 leaves alone)
+    "one-wave chain": [(ONE(6), 50), (ONE(7), 60), (ONE(8), 70), (ONE(12), 50), (ONE(13), 60), (ONE(14), 70)],
+    # 6 -> 7 -> 8 fold; 9 is more than 4/3 of 6: the group ends at 8, and 9 is a lone class behind it
+    "one-wave ratio": [(ONE(6), 50), (ONE(7), 60), (ONE(8), 70), (ONE(9), 80)],
+    "one-wave small": [(ONE(1), 10), (ONE(2), 20), (ONE(3), 30), (ONE(4), 40), (ONE(5), 50)],      # the <= 4 exception; 5 is not within 4/3 of 1
+    "one-wave lone": [(ONE(10), 50)],                                                              # no target: keeps its strip width
+    "one-wave full": [(ONE(6), 7000), (ONE(7), 60), (ONE(8), 70)],                                 # a class that fills the GPU stays
+    # every lanes-per-pair class of a width moves together, each into its own lanes' class of the next width
+    "packed chain": [(PK(6, 32), 50), (PK(6, 16), 30), (PK(7, 32), 60), (PK(8, 16), 70), (PK(14, 32), 50), (PK(15, 32), 60), (PK(16, 8), 70)],
+    "packed ratio": [(PK(6, 32), 50), (PK(7, 16), 60), (PK(8, 32), 70), (PK(9, 32), 80)],
+    "packed small": [(PK(1, 2), 10), (PK(2, 4), 20), (PK(3, 2), 30), (PK(4, 32), 40), (PK(5, 32), 50)],
+    "packed lone": [(PK(10, 8), 50)],
+    # the fill is wavefronts: 40 000 pairs at 8 lanes are 5000 wavefronts (folds), 13 000 at 32 lanes are 6500 (stays)
+    "packed full": [(PK(6, 8), 40000), (PK(7, 32), 13000), (PK(8, 32), 70)],
+    "four-wave chain": [(WG4(15), 100), (WG4(16), 200), (WG4(17), 300)],
+    "four-wave ratio": [(WG4(6), 50), (WG4(7), 60), (WG4(8), 70), (WG4(9), 80)],                   # (no <= 4 exception: no such width)
+    "four-wave lone": [(WG4(20), 50), (WG8(8), 50)],                                               # the widest four-wave class: never into the eight-wave family
+    "four-wave full": [(WG4(15), 1600), (WG4(16), 200), (WG4(17), 300)],
+    "eight-wave chain": [(WG8(12), 100), (WG8(13), 200), (WG8(14), 300)],
+    "eight-wave ratio": [(WG8(9), 50), (WG8(10), 60), (WG8(11), 70), (WG8(12), 80), (WG8(13), 90)],
+    "eight-wave lone": [(WG8(20), 50)],
+    "eight-wave full": [(WG8(12), 1600), (WG8(13), 200), (WG8(14), 300)],
+}
+# (case, fold) -> pairs of every non-empty class after the sort: class_first is their running sum.  Recorded from the library of the
+# commit BEFORE the four fold loops became one walk (tests/manual/plan_units_ab.py --fold-literals), not from the code under test.
+FOLD_EXPECTED = {
+    ('one-wave chain', 1): {7: 180, 13: 180},
+    ('one-wave chain', 2): {7: 180, 11: 50, 12: 60, 13: 70},
+    ('one-wave chain', 3): {5: 50, 6: 60, 7: 70, 11: 50, 12: 60, 13: 70},
+    ('one-wave ratio', 1): {7: 180, 8: 80},
+    ('one-wave ratio', 2): {7: 180, 8: 80},
+    ('one-wave ratio', 3): {5: 50, 6: 60, 7: 70, 8: 80},
+    ('one-wave small', 1): {3: 100, 4: 50},
+    ('one-wave small', 2): {3: 100, 4: 50},
+    ('one-wave small', 3): {0: 10, 1: 20, 2: 30, 3: 40, 4: 50},
+    ('one-wave lone', 1): {9: 50},
+    ('one-wave lone', 2): {9: 50},
+    ('one-wave lone', 3): {9: 50},
+    ('one-wave full', 1): {5: 7000, 7: 130},
+    ('one-wave full', 2): {5: 7000, 7: 130},
+    ('one-wave full', 3): {5: 7000, 6: 60, 7: 70},
+    ('packed chain', 1): {75: 70, 87: 100, 107: 110, 115: 110},
+    ('packed chain', 2): {75: 70, 87: 100, 107: 110, 113: 50, 114: 60},
+    ('packed chain', 3): {75: 70, 85: 30, 87: 70, 105: 50, 106: 60, 113: 50, 114: 60},
+    ('packed ratio', 1): {87: 60, 107: 120, 108: 80},
+    ('packed ratio', 2): {87: 60, 107: 120, 108: 80},
+    ('packed ratio', 3): {86: 60, 105: 50, 107: 70, 108: 80},
+    ('packed small', 1): {23: 40, 43: 20, 103: 40, 104: 50},
+    ('packed small', 2): {23: 40, 43: 20, 103: 40, 104: 50},
+    ('packed small', 3): {20: 10, 22: 30, 41: 20, 103: 40, 104: 50},
+    ('packed lone', 1): {69: 50},
+    ('packed lone', 2): {69: 50},
+    ('packed lone', 3): {69: 50},
+    ('packed full', 1): {66: 40000, 106: 13000, 107: 70},
+    ('packed full', 2): {66: 40000, 106: 13000, 107: 70},
+    ('packed full', 3): {65: 40000, 106: 13000, 107: 70},
+    ('four-wave chain', 1): {132: 600},
+    ('four-wave chain', 2): {132: 600},
+    ('four-wave chain', 3): {132: 600},
+    ('four-wave ratio', 1): {123: 180, 124: 80},
+    ('four-wave ratio', 2): {123: 180, 124: 80},
+    ('four-wave ratio', 3): {123: 180, 124: 80},
+    ('four-wave lone', 1): {135: 50, 136: 50},
+    ('four-wave lone', 2): {135: 50, 136: 50},
+    ('four-wave lone', 3): {135: 50, 136: 50},
+    ('four-wave full', 1): {130: 1600, 132: 500},
+    ('four-wave full', 2): {130: 1600, 132: 500},
+    ('four-wave full', 3): {130: 1600, 132: 500},
+    ('eight-wave chain', 1): {142: 600},
+    ('eight-wave chain', 2): {142: 600},
+    ('eight-wave chain', 3): {142: 600},
+    ('eight-wave ratio', 1): {140: 260, 141: 90},
+    ('eight-wave ratio', 2): {140: 260, 141: 90},
+    ('eight-wave ratio', 3): {140: 260, 141: 90},
+    ('eight-wave lone', 1): {148: 50},
+    ('eight-wave lone', 2): {148: 50},
+    ('eight-wave lone', 3): {148: 50},
+    ('eight-wave full', 1): {140: 1600, 142: 500},
+    ('eight-wave full', 2): {140: 1600, 142: 500},
+    ('eight-wave full', 3): {140: 1600, 142: 500},
+}
+
+
+def fold_case_arrays(case):
+    """Launch classes and launch-order keys of the pairs of one fold case."""
+    cls = np.concatenate([np.full(n, _class(*c), dtype=np.int16) for c, n in case])
+    return cls, (np.arange(len(cls)) % 500 + 1).astype(np.int16)
+
+
+@pytest.mark.parametrize("fold", [1, 2, 3])
+@pytest.mark.parametrize("family", ["one-wave", "packed", "four-wave", "eight-wave"])
+def test_fold_walk_of_every_family(family, fold):
+    """One walk for the four families (fold 1: a launch per class; 2: the multi-width launches leave the one-wave widths from 11 and
+    the packed widths from 13 alone; 3: the plan kernel leaves both families alone): class_first against the recorded arrays, and
+    every pair in a class of its own family no narrower than its own."""
+    cases = [name for name in FOLD_CASES if name.startswith(family)]
+    assert len(cases) >= 4
+    for name in cases:
+        cls, key = fold_case_arrays(FOLD_CASES[name])
+        order, first = _sort(cls, key, fold)
+        sizes = np.zeros(NK, dtype=np.int64)
+        for k, n in FOLD_EXPECTED[(name, fold)].items():
+            sizes[k] = n
+        assert first.tolist() == [0] + np.cumsum(sizes).tolist(), (name, fold)
+        for k in np.flatnonzero(sizes):
+            src = cls[order[first[k]:first[k + 1]]]
+            assert (src <= k).all() and all(class_info(int(s))["lanes"] == class_info(int(k))["lanes"] for s in set(src.tolist())), (name, fold, k)
 
 
 def test_shard_costs_are_the_plans_own_model():
