@@ -183,6 +183,12 @@ int ltr_plan_kernel_class(const ltr_plan* plan);
  * out5 = families, member pairs of the plan; of its last execute: families whose stem certificate failed (all members to the exact
  * body), members the acceptance rule sent there, members whose tail certificate failed. */
 int ltr_plan_family_stats(ltr_plan* plan, int64_t* out5);
+/* Families run along a SPINE (csrc/ltr_dp_family.hpp, spine_walk): where members fork from each other beyond the family's fork row,
+ * the stream follows one member's window to its end and the others leave it at the row where they leave that member, so the rows
+ * longer alleles share are scored once as well.  ltr_ctx_set_debug "family_spine": -1 never (plain families), 0 by rule (plans that form
+ * at least 24 families per CU), 1 in any plan.
+ * out2 = families of the plan that run along a spine, modelled wavefront steps that saves against plain families. */
+int ltr_plan_family_spine_stats(const ltr_plan* plan, int64_t* out2);
 /* Measurement aid: with ltr_ctx_set_debug(ctx, "wave_clock", 1) set when the plan was created, the plan kernel records the wall
  * clock (100 MHz) at which every one of its wavefronts started and left, and what it spent in the exact body: out = {first, last,
  * pairs scored with the exact body, ticks spent there} per wavefront of the last execute, then 4096 words: a count and

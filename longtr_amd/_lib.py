@@ -26,7 +26,7 @@ EXPORTS = [
     "ltr_default_params", "ltr_default_stutter_params", "ltr_ctx_set_stutter_params", "ltr_ctx_set_pair_packing", "ltr_ctx_set_debug", "ltr_ctx_wg_first_pass", "ltr_ctx_create", "ltr_ctx_destroy", "ltr_ctx_set_params", "ltr_last_error",
     "ltr_ctx_device_info", "ltr_align_batch", "ltr_plan_create", "ltr_plan_destroy", "ltr_plan_num_pairs",
     "ltr_plan_ll_size", "ltr_plan_cells", "ltr_plan_input_bytes", "ltr_plan_execute", "ltr_plan_fetch",
-    "ltr_plan_last_kernel_ms", "ltr_num_kernels", "ltr_kernel_lanes_per_pair", "ltr_kernel_family", "ltr_plan_set_timing", "ltr_plan_kernel_stats", "ltr_plan_kernel_ranges", "ltr_plan_debug_wave_clocks", "ltr_plan_debug_entries", "ltr_plan_kernel_class", "ltr_plan_family_stats", "ltr_process_reads", "ltr_calc_hap_aln_probs", "ltr_haplotype_num_combs", "ltr_haplotype_seq",
+    "ltr_plan_last_kernel_ms", "ltr_num_kernels", "ltr_kernel_lanes_per_pair", "ltr_kernel_family", "ltr_plan_set_timing", "ltr_plan_kernel_stats", "ltr_plan_kernel_ranges", "ltr_plan_debug_wave_clocks", "ltr_plan_debug_entries", "ltr_plan_kernel_class", "ltr_plan_family_stats", "ltr_plan_family_spine_stats", "ltr_process_reads", "ltr_calc_hap_aln_probs", "ltr_haplotype_num_combs", "ltr_haplotype_seq",
     "ltr_trim_alignment", "ltr_pool_reads", "ltr_scatter_pool_probs", "ltr_posteriors", "ltr_plan_posteriors", "ltr_extract_genotypes", "ltr_ctx_timers", "ltr_haps_to_alleles", "ltr_unused_alleles", "ltr_remap_haplotypes",
     "ltr_remap_aln_probs", "ltr_default_vcf_options", "ltr_get_alleles", "ltr_vcf_record", "ltr_vcf_header", "ltr_haplotype_aln_info_capacity",
     "ltr_haplotype_align_to_ref", "ltr_left_align_reads", "ltr_phasing_priors", "ltr_read_set_size", "ltr_read_set_alignments",
@@ -779,6 +779,36 @@ def debug_plan_families(batch, params=None, mode=-1, n_cu=256, families=0, famil
     return dict(families=rows, members=int(out[1]), n_pairs=int(out[3]))
 
 
+def debug_plan_family_forks(batch, params=None, mode=-1, n_cu=256, families=0, family_min_rows=0, family_spine=0):
+    """Test hook ltr_debug_plan_family_forks (csrc/ltr_plan.h): describe_batch on a _abi.PackedBatch, no GPU, for the spines of its
+    families; family_spine is the ltr_ctx_set_debug knob of that name.  dict(families: list of dict(spine: member or -1, slots, steps,
+    slot_rows, first, count, p, W, dd_min, dd_max, fork: per member, slot: per member, out_idx: per member), members, with_spine,
+    steps_saved, park_slots)."""
+    L = lib()
+    L.ltr_debug_plan_family_forks.argtypes = [C.POINTER(_abi.AlignParams), C.c_int, C.c_int, C.POINTER(_abi.LocusBatch), C.c_void_p, C.c_void_p,
+                                              C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    prm = params or _abi.default_params()
+    knobs = np.asarray([families, family_min_rows, family_spine], dtype=np.int32)
+    out = np.zeros(4, dtype=np.int64)
+    cap = max(int(batch.ll_size), 1)
+    fam, slot_row = np.zeros((cap, 10), np.int32), np.zeros(cap * 16, np.int32)
+    fork, slot, mem_out = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.int64)
+    rc = L.ltr_debug_plan_family_forks(C.byref(prm), int(mode), int(n_cu), C.byref(batch.struct), _p(knobs), _p(out), cap, _p(fam), _p(slot_row),
+                                       cap, _p(fork), _p(slot), _p(mem_out))
+    if rc != 0:
+        raise LtrError(rc, "ltr_debug_plan_family_forks")
+    n_slots = int(fam[0, 3]) if out[0] else 0
+    assert n_slots <= 16
+    rows, at = [], 0
+    for i in range(int(out[0])):
+        d = dict(zip(("spine", "slots", "steps", "park_slots", "first", "count", "p", "W", "dd_min", "dd_max"), (int(v) for v in fam[i])))
+        d.update(slot_rows=[int(v) for v in slot_row[i * n_slots:i * n_slots + d["slots"]]], fork=[int(v) for v in fork[at:at + d["count"]]],
+                 slot=[int(v) for v in slot[at:at + d["count"]]], out_idx=[int(v) for v in mem_out[at:at + d["count"]]])
+        at += d["count"]
+        rows.append(d)
+    return dict(families=rows, members=int(out[1]), with_spine=int(out[2]), steps_saved=int(out[3]), park_slots=n_slots)
+
+
 def debug_chunk_plan(n_loci, est_cells=0.0, budget=0, chunks=0, chunk_streams=0, chunk_growth=None, prep_ahead=0):
     """Test hook ltr_debug_chunk_plan (csrc/ltr_internal.h): the chunk rule of ltr_calc_hap_aln_probs on made-up numbers, no GPU.
     The keywords are the ltr_ctx_set_debug knobs of the same names (chunk_growth=None: not set); budget 0 = the process's.
@@ -1083,6 +1113,14 @@ class Plan:
         self.redo_log = [(int(v >> np.uint64(32)), int(v & np.uint64(0xffffffff))) for v in buf[4 * n + 1:4 * n + 1 + k]]   # (n, m) of the pairs that took the exact body
         self.entry_ticks = buf[4 * n + 4096:4 * n + 4096 + 256].copy()       # per entry of the plan kernel's table: ticks of all wavefronts together
         return buf[:4 * n].reshape(n, 4)
+
+    def family_spine_stats(self):
+        """ltr_plan_family_spine_stats: dict(with_spine: families of the plan run along a spine, steps_saved: modelled wavefront
+        steps that saves against plain families)."""
+        lib().ltr_plan_family_spine_stats.argtypes = [C.c_void_p, C.c_void_p]
+        out = np.zeros(2, dtype=np.int64)
+        self.ctx._check(lib().ltr_plan_family_spine_stats(self._h, _p(out)))
+        return dict(with_spine=int(out[0]), steps_saved=int(out[1]))
 
     def family_stats(self):
         """ltr_plan_family_stats: dict(families, members) of the plan and, of its last execute, stem_failures (families whose stem

@@ -131,7 +131,8 @@ struct ltr_plan : ltrp::BatchPlan {     // (what ltrp::describe_batch decided: s
   PlanEntry* d_pl_entries = nullptr;    // sched.plan_entries
   unsigned long long* d_wave_clock = nullptr;   // (debug) two wall-clock words per wavefront of the plan kernel
   FamilyDesc* d_fams = nullptr;         // fams (BatchPlan): the family launch's list
-  double* d_fam_park = nullptr;         // ... per wavefront of its grid: kFamilyParkDoubles (the stem's last row)
+  FamilySpine* d_fam_spines = nullptr;  // fam_spines (BatchPlan): per family, beside d_fams
+  double* d_fam_park = nullptr;         // ... per wavefront of its grid: kFamilyParkDoubles (the park rows: the stem's last row, the spine's fork rows)
   uint32_t* d_fam_stats = nullptr;      // ... 4 words, zeroed by every execute (FamilyArgs::stats)
   hipEvent_t bin_ev[ltrp::kNumKernels + 1] = {nullptr};   // bracket every DP launch on the launch stream
   uint32_t* d_ctrl_init = nullptr;      // image of the control words (queues = 0, redo count = n_generic)

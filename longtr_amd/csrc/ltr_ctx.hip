@@ -218,6 +218,7 @@ int ltr_ctx_set_debug(ltr_ctx* ctx, const char* key, double value) {
   else if (k == "plan_share") ctx->dbg.plan_share = (int)value;
   else if (k == "families") ctx->dbg.families = (int)value;
   else if (k == "family_min_rows") ctx->dbg.family_min_rows = (int)value;
+  else if (k == "family_spine") ctx->dbg.family_spine = (int)value;
   else if (k == "chain") ctx->dbg.chain = (int)value;
   else if (k == "chain_min_w") ctx->dbg.chain_min_w = (int)value;
   else if (k == "chain_max_w") ctx->dbg.chain_max_w = (int)value;

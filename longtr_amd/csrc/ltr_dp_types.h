@@ -114,17 +114,34 @@ struct FamilyDesc {
   int32_t W;               // strip width (the read's: one column block)
   int32_t dd_min, dd_max;  // smallest and largest n - m of a member
 };
+// A family's SPINE (ltr_dp_family.hpp, spine_walk; chosen on the host, ltrp::choose_spine): one member whose window the stream runs
+// along beyond the fork row p, the others leaving it at a PARK ROW of their own -- slot 0 is row p, slots 1 .. n_slots-1 the kept rows
+// beyond it, ascending.  A slot holds the carried state of the row BEFORE its row.  spine < 0: a plain family (family_walk).
+#ifndef LTR_FAMILY_PARK_SLOTS
+#define LTR_FAMILY_PARK_SLOTS 8
+#endif
+constexpr int kFamilyParkSlots = LTR_FAMILY_PARK_SLOTS;   // park rows of a family, p included (measured at 3, 5, 8 and 11: DESIGN.md section 3)
+static_assert(kFamilyParkSlots >= 2 && kFamilyParkSlots <= 16, "slot 0 is p; a family has at most 31 fork rows beyond it");
+struct FamilySpine {       // (82 bytes a family at 8 slots: the list is uploaded with every plan)
+  int8_t spine;            // member (0 .. count-1) the stream follows, or -1
+  int8_t n_slots;
+  int16_t slot_row[kFamilyParkSlots];
+  int16_t slot_dd_min[kFamilyParkSlots], slot_dd_max[kFamilyParkSlots];   // n - m of the members that use spine rows from slot_row on: those of later slots and the spine member
+  uint8_t slot_of[32];     // per member: the slot its tail starts from (the spine member's: unused)
+};
 struct FamilyArgs {        // the family kernel's second argument (KernelArgs stays what the other kernels were built against)
   const FamilyDesc* fams;  // sorted by modelled cost, largest first
   int32_t n_fams;
   int32_t reserved;
   double* park;            // per wavefront of the launch: kFamilyParkDoubles (the stem's last row: X, Y of every column)
   uint32_t* stats;         // [0] families whose stem certificate failed, [1] members the acceptance rule sent to the exact body, [2] members whose tail certificate failed
+  const FamilySpine* spines;   // per family, beside fams
 };
 constexpr int kFamilyMaxMembers = 32;            // members of a family (the wave's note list)
 constexpr int kFamilyMinC = 641, kFamilyMaxC = 64 * LTR_WMAX;   // read columns of a family of the wide band: one wavefront, one column block, strips of 11 .. 20
 constexpr int kFamilyNarrowMinC = 321, kFamilyNarrowMaxC = 640; // ... and of the narrow band: the same geometry with strips of 6 .. 10 -- reads the class rule packs two to a wavefront
-constexpr int kFamilyParkDoubles = 2 * LTR_WMAX * 64;
+constexpr int kFamilySlotDoubles = (2 * LTR_WMAX + 1) * 64;      // one park row: X, Y of every column and X of the column left of the lane's strip
+constexpr int kFamilyParkDoubles = kFamilyParkSlots * kFamilySlotDoubles;   // per wavefront (a plain family uses the head of slot 0)
 constexpr int kFamilyArgsOffset = (int)((sizeof(KernelArgs) + alignof(FamilyArgs) - 1) / alignof(FamilyArgs) * alignof(FamilyArgs));   // where FamilyArgs sits in the kernel's argument segment
 constexpr int kInlineCountOff = 8;                // xcount[kInlineCountOff + c]: pairs of exact class c the plan kernel scored in line (statistics)
 constexpr int kWgStatOff = 16;                    // xcount[kWgStatOff]: pairs the FIRST pass of the workgroup classes could not finish (certificate pass: sent to an exact list; threshold pass: aborted, -700); [+ 1]: pairs it scored -- what the context learns its first pass from

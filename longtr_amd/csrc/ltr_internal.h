@@ -256,6 +256,7 @@ struct DebugKnobs {
   int64_t ll_chunk_loci = 0;    // ltr_ll_genotype: loci per upload chunk (rule: as many as fit 8 MB of staging)
   int families = 0;             // haplotype families (ltr_dp_family.hpp): -1 = never, 0 = by rule (where modelled cheaper), 1 = whenever one can be formed from reads of 641 .. 1280 columns, 2 = ... of 321 .. 1280
   int family_min_rows = 0;      // ... fewest shared rows (0: ltrp::kFamMinRows)
+  int family_spine = 0;         // ... run along a spine (ltr_dp_family.hpp, spine_walk): -1 = never (plain families), 0 = by rule (plans of ltrp::kSpinePerCu families per CU and more), 1 = in any plan
 };
 DebugKnobs ctx_debug(const ltr_ctx* ctx);
 

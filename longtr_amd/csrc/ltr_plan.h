@@ -223,6 +223,9 @@ struct BatchScratch {
   RawBuf<PairDesc>& pairs; RawBuf<PairDesc>& sorted; RawBuf<int16_t>& key; RawBuf<int16_t>& bin; RawBuf<int32_t>& order;
   RawBuf<uint8_t>& read_acgt; RawBuf<uint8_t>& hap_acgt;
 };
+// What the host alone keeps of a spine: the family's modelled steps as it is run (the launch-order key) and every member's own fork
+// row max(p, min(lcp(spine, member), n - 1)) (the spine member's: its n; a plain family's: unused).
+struct FamilyForks { int64_t steps; int16_t fork[kFamilyMaxMembers]; };
 // What describe_batch decides about a batch; a plan (struct ltr_plan, ltr_ctx.h) starts out as one of these.
 struct __attribute__((visibility("hidden"))) BatchPlan {
   int64_t n_pairs = 0, ll_size = 0;
@@ -245,8 +248,13 @@ struct __attribute__((visibility("hidden"))) BatchPlan {
   std::vector<FamilyDesc> fams;
   std::vector<double> fam_U;            // per family: the acceptance bound the host filtered its members with (the device forms its own)
   int64_t fam_members = 0;
+  std::vector<FamilySpine> fam_spines;  // per family: its spine and park rows (spine -1: plain)
+  std::vector<FamilyForks> fam_forks;   // ... its steps and fork rows, kept only on request (ltr_debug_plan_family_forks)
+  bool keep_forks = false;
+  int64_t fam_with_spine = 0, fam_rows_saved = 0;   // families run along a spine; modelled steps they save against plain families
 };
 constexpr int kFamPerCu = 12;           // by rule a batch forms families from this many per CU up: one for every wavefront of the family launch's full grid (form_families)
+constexpr int kSpinePerCu = 24;         // by rule a plan runs its families along spines from this many families per CU up (form_families)
 constexpr int kFamMinRows = 64;         // fewest shared rows a family is formed for (ltr_ctx_set_debug "family_min_rows")
 // Haplotype families (ltr_dp_family.hpp).  A family is the pairs of one pooled read against two or more haplotypes of its locus whose
 // windows share their first rows; its fork row p = min(longest common prefix of the members' WINDOWS, smallest n - 1), so that every
@@ -267,12 +275,33 @@ constexpr int kFamMinRows = 64;         // fewest shared rows a family is formed
 // kFamPerCu per CU (a smaller plan keeps the launches it had); then both bands together are held against the same count, as before.  Knob 1 forms no
 // narrow family; knob 2 is "on request" in both bands: no cost rule, no count rule, and narrow candidates also from the one-wave
 // class of their strip width (where a batch that does not pack leaves them).
+// The SPINE (choose_spine; FamilySpine, ltr_dp_types.h) is chosen after forming and changes none of it -- p, U, count, W, dd_min, dd_max and
+// which families exist stay what they were; it only removes steps, so a family that pays keeps paying.  For a formed family the member s
+// that minimises (n_s - p) + sum over the others of (n_k - f_k), f_k = max(p, min(lcp(s, k), n_k - 1)), is the spine (the first such
+// member in haplotype order), at most kFamilyParkSlots - 1 of the distinct f_k beyond p are kept as park rows -- the subset that saves
+// most rows --, and a member whose own row is not kept starts from the nearest kept row below it.  A family in which no member forks
+// beyond p stays plain (spine -1).  The launch-order key is the modelled steps of the family AS RUN, (n_s - 1 + L-1) + sum(n_k - row_k + L-1),
+// so that the static deal balances the real work.  By rule only plans of at least kSpinePerCu families per CU (6144 on 256 CUs) use spines: a
+// smaller plan keeps plain families, the keys and the launch it had (why).  ltr_ctx_set_debug "family_spine": -1 never, 0 by
+// rule, 1 in any plan.
 struct FamilyRec {
   int64_t first_pair; FamilyDesc f; double U;        // (first_pair: in batch order, before the sort)
   int64_t row_at; uint64_t members; int16_t key;     // the read's first pair in batch order, its member pairs from there as bits, their launch-order key
+  int16_t plain_key;                                 // ... and the key of the family run as a plain one
+  int32_t steps, plain_steps;                        // modelled steps as it is run / as a plain family (the cost rule's)
+  int32_t locus, spine_at;                           // its spine: FamilySide::sp[locus][spine_at] (spine_at -1: plain)
 };
-void form_families(const ltr_locus_batch* b, const ModelConsts& mc, int F, int n_cu, int knob, int min_rows, const std::vector<int64_t>& pair_base,
-                   const BatchScratch& w, std::vector<FamilyRec>* out) __attribute__((visibility("hidden")));
+// The spines of the families of a batch (choose_spine), locus by locus beside the family list: written once where they are chosen, read
+// once where the sorted list is resolved.  fork: kFamilyMaxMembers fork rows per spine (FamilyForks::fork), kept on request only.
+struct FamilySide {
+  bool keep_forks = false;
+  std::vector<std::vector<FamilySpine>> sp;
+  std::vector<std::vector<int16_t>> fork;
+};
+// spine_knob: ltr_ctx_set_debug "family_spine" (-1 never: every family plain; 0 by rule: a spine wherever a member forks beyond p, in
+// plans of at least kSpinePerCu families per CU; 1: in any plan)
+void form_families(const ltr_locus_batch* b, const ModelConsts& mc, int F, int n_cu, int knob, int min_rows, int spine_knob, const std::vector<int64_t>& pair_base,
+                   const BatchScratch& w, std::vector<FamilyRec>* out, FamilySide* side) __attribute__((visibility("hidden")));
 // Validates the batch, gives every pair its descriptor, class and key, sorts them (w.sorted, w.order, w.key stay valid for the
 // caller) and fills *d.  mode: ltr_ctx_set_pair_packing.  LTR_OK, or LTR_ERR_INVALID with the reason in *err.
 int describe_batch(const ltr_locus_batch* b, const ModelConsts& mc, int indel_flank_len, int mode, int n_cu, const ltr::DebugKnobs& dbg,
@@ -375,6 +404,13 @@ int ltr_debug_threshold_groups(const int32_t* class_first, int merge, int keep_w
 // family class (from out[2] on) its window length in member_n[member_cap] and its LL index in member_out[].
 int ltr_debug_plan_families(const ltr_align_params* p, int mode, int n_cu, const ltr_locus_batch* b, const int32_t* knobs, int64_t* out,
                             int fam_cap, int32_t* fam, double* U, int member_cap, int32_t* member_n, int64_t* member_out);
+// ltr_debug_plan_family_forks: the same call with knobs[3] = families, family_min_rows, family_spine, for the spines (choose_spine).  out[4] =
+// families, members, families with a spine, modelled steps saved; per family (in the order of its members in the sorted pair list) 10
+// words in fam[fam_cap][10] = spine member (-1: plain), slots, modelled steps, park-slot capacity, then first member, members, p, strip
+// width, dd_min, dd_max as ltr_debug_plan_families lists them, and slot_row[fam_cap][capacity]; per sorted pair of the family class its
+// fork row in member_fork[member_cap] (the spine member's: its n; plain: p), its slot in member_slot[] and its LL index in member_out[].
+int ltr_debug_plan_family_forks(const ltr_align_params* p, int mode, int n_cu, const ltr_locus_batch* b, const int32_t* knobs, int64_t* out,
+                                int fam_cap, int32_t* fam, int32_t* slot_row, int member_cap, int32_t* member_fork, int32_t* member_slot, int64_t* member_out);
 }
 
 #endif

@@ -39,12 +39,12 @@ void release_plan_buffers(ltr_plan* plan, ltr_ctx* ctx) {
   void** bufs[] = {(void**)&plan->d_reads, (void**)&plan->d_haps, (void**)&plan->d_hap_codes, (void**)&plan->d_pairs,
                    (void**)&plan->d_ll, (void**)&plan->d_queue, (void**)&plan->d_scratch, (void**)&plan->d_redo_list,
                    (void**)&plan->d_ctrl_init, (void**)&plan->d_redo_init, (void**)&plan->d_pk_tabs, (void**)&plan->d_pl_entries, (void**)&plan->d_wave_clock,
-                   (void**)&plan->d_fams, (void**)&plan->d_fam_park, (void**)&plan->d_fam_stats};
+                   (void**)&plan->d_fams, (void**)&plan->d_fam_park, (void**)&plan->d_fam_stats, (void**)&plan->d_fam_spines};
   if (plan->d_block || plan->h_ll) {
     // a compact plan: one block holds every array but the scratch strips and the family launch's; the scores are a pinned block of the context
-    void* const scr = plan->d_scratch; void* const fm = plan->d_fams; void* const fp = plan->d_fam_park; void* const fs = plan->d_fam_stats;
+    void* const scr = plan->d_scratch; void* const fm = plan->d_fams; void* const fp = plan->d_fam_park; void* const fs = plan->d_fam_stats; void* const fsp = plan->d_fam_spines;
     for (void** p : bufs) *p = nullptr;
-    plan->d_scratch = (double*)scr; plan->d_fams = (FamilyDesc*)fm; plan->d_fam_park = (double*)fp; plan->d_fam_stats = (uint32_t*)fs;
+    plan->d_scratch = (double*)scr; plan->d_fams = (FamilyDesc*)fm; plan->d_fam_park = (double*)fp; plan->d_fam_stats = (uint32_t*)fs; plan->d_fam_spines = (FamilySpine*)fsp;
     if (ctx) ctx->pool.release(plan->d_block); else if (plan->d_block) (void)hipFree(plan->d_block);
     plan->d_block = nullptr;
     ctx_give_pinned(ctx, plan->h_ll);
@@ -365,6 +365,9 @@ int PlanBuild::size_scratch_and_fan() {
       for (const Launch& L : plan->sched.by_class) if (L.kind == kLaunchFamily) fam_grid = std::max(fam_grid, L.grid);
       PLAN_TRY(ctx->pool.alloc((void**)&plan->d_fams, plan->fams.size() * sizeof(FamilyDesc)));
       PLAN_TRY(hipMemcpy(plan->d_fams, plan->fams.data(), plan->fams.size() * sizeof(FamilyDesc), hipMemcpyHostToDevice));
+      PLAN_TRY(ctx->pool.alloc((void**)&plan->d_fam_spines, plan->fam_spines.size() * sizeof(FamilySpine)));
+      PLAN_TRY(hipMemcpy(plan->d_fam_spines, plan->fam_spines.data(), plan->fam_spines.size() * sizeof(FamilySpine), hipMemcpyHostToDevice));
+      // (kFamilyParkSlots park rows per wavefront: 8 x 41 x 64 doubles = 168 KB, 516 MB for the 3072 wavefronts of a full grid on 256 CUs)
       PLAN_TRY(ctx->pool.alloc((void**)&plan->d_fam_park, (size_t)fam_grid * kBlockWaves * kFamilyParkDoubles * sizeof(double)));
       PLAN_TRY(ctx->pool.alloc((void**)&plan->d_fam_stats, 4 * sizeof(uint32_t)));
       PLAN_TRY(hipMemset(plan->d_fam_stats, 0, 4 * sizeof(uint32_t)));

@@ -5,6 +5,8 @@
 #include <emmintrin.h>
 #endif
 
+#include <cstring>
+
 #include "ltr_internal.h"
 #include "ltr_plan.h"
 
@@ -218,22 +220,55 @@ static void move_beyond_quota_to_eight_waves(const int64_t quota, const BatchScr
 }
 
 // d->fams: the families in the order the sort left their members in: a family's members are one run of the family class, its first
-// member first (input order inside a key)
-static int resolve_families(const std::vector<FamilyRec>& fam_recs, const BatchScratch& w, BatchPlan* d, std::string* err) {
+// member first (input order inside a key).  Three passes: which sorted pairs are a family's first member (all host cores: a lookup by
+// batch position), the list of those runs (serial, a scan of one int per member), then every family's records written at their
+// final place (all host cores: the records are read in sorted order, which is scattered over the family list and the spine lists).
+static int resolve_families(const std::vector<FamilyRec>& fam_recs, const FamilySide& side, const BatchScratch& w, BatchPlan* d, std::string* err) {
   const RawBuf<PairDesc>& sorted = w.sorted;
   d->fams.clear(); d->fam_U.clear(); d->fam_members = 0;
-  for (int i = d->bin_first[kFamClass]; i < d->bin_first[kFamClass + 1];) {
-    const int64_t orig = w.order[(size_t)i];
-    const auto it = std::lower_bound(fam_recs.begin(), fam_recs.end(), orig, [](const FamilyRec& r, int64_t v) { return r.first_pair < v; });
-    bool ok = it != fam_recs.end() && it->first_pair == orig && i + it->f.count <= d->bin_first[kFamClass + 1];
-    for (int k = 0; ok && k < it->f.count; ++k)
-      ok = sorted[(size_t)(i + k)].read_off == sorted[(size_t)i].read_off && sorted[(size_t)(i + k)].m == sorted[(size_t)i].m && sorted[(size_t)(i + k)].n - 1 >= it->f.p;
-    if (!ok) { *err = "internal error: a haplotype family's members are not contiguous in the sorted pair list"; return LTR_ERR_INVALID; }
-    FamilyDesc f = it->f;
+  d->fam_spines.clear(); d->fam_forks.clear(); d->fam_with_spine = d->fam_rows_saved = 0;
+  const int f0 = d->bin_first[kFamClass], f1 = d->bin_first[kFamClass + 1];
+  if (f1 <= f0) return LTR_OK;
+  std::vector<int32_t> rec_of_pair(w.pairs.size(), -1);            // batch position of a family's first member -> its record
+  ltr::parallel_for((int64_t)fam_recs.size(), 4096, [&](int64_t r) { rec_of_pair[(size_t)fam_recs[(size_t)r].first_pair] = (int32_t)r; });
+  std::vector<int32_t> rec_at((size_t)(f1 - f0));
+  ltr::parallel_for((int64_t)(f1 - f0), 4096, [&](int64_t k) { rec_at[(size_t)k] = rec_of_pair[(size_t)w.order[(size_t)(f0 + k)]]; });
+  std::vector<int32_t> first_at; first_at.reserve(fam_recs.size() + 1);
+  for (int k = 0; k < f1 - f0; ++k) if (rec_at[(size_t)k] >= 0) first_at.push_back(k);
+  const size_t nf = first_at.size();
+  first_at.push_back(f1 - f0);
+  FamilySpine plain;
+  std::memset(&plain, 0, sizeof(plain));
+  plain.spine = -1;
+  d->fams.resize(nf); d->fam_U.resize(nf); d->fam_spines.resize(nf);
+  if (d->keep_forks) d->fam_forks.resize(nf);
+  std::atomic<int> bad((nf == 0 && f1 > f0) || (nf > 0 && first_at[0] != 0) ? 1 : 0);
+  std::vector<int32_t> saved(nf, 0);                               // modelled steps a family's spine saves
+  ltr::parallel_for((int64_t)nf, 1024, [&](int64_t j) {
+    const int i = f0 + first_at[(size_t)j];
+    const FamilyRec& rec = fam_recs[(size_t)rec_at[(size_t)first_at[(size_t)j]]];
+    bool ok = first_at[(size_t)j + 1] - first_at[(size_t)j] == rec.f.count;      // (its run ends where the next family's begins)
+    for (int k = 0; ok && k < rec.f.count; ++k)
+      ok = sorted[(size_t)(i + k)].read_off == sorted[(size_t)i].read_off && sorted[(size_t)(i + k)].m == sorted[(size_t)i].m && sorted[(size_t)(i + k)].n - 1 >= rec.f.p;
+    if (!ok) { bad.store(1, std::memory_order_relaxed); return; }
+    FamilyDesc f = rec.f;
     f.first = i;
-    d->fams.push_back(f); d->fam_U.push_back(it->U); d->fam_members += f.count;
-    i += f.count;
+    d->fams[(size_t)j] = f; d->fam_U[(size_t)j] = rec.U;
+    d->fam_spines[(size_t)j] = rec.spine_at < 0 ? plain : side.sp[(size_t)rec.locus][(size_t)rec.spine_at];
+    if (rec.spine_at >= 0) saved[(size_t)j] = rec.plain_steps - rec.steps;
+    if (d->keep_forks) {
+      FamilyForks fk;
+      std::memset(&fk, 0, sizeof(fk));
+      fk.steps = rec.steps;
+      if (rec.spine_at >= 0) std::memcpy(fk.fork, side.fork[(size_t)rec.locus].data() + (size_t)rec.spine_at * kFamilyMaxMembers, sizeof(fk.fork));
+      d->fam_forks[(size_t)j] = fk;
+    }
+  });
+  if (bad.load()) {
+    d->fams.clear(); d->fam_U.clear(); d->fam_spines.clear(); d->fam_forks.clear();
+    *err = "internal error: a haplotype family's members are not contiguous in the sorted pair list"; return LTR_ERR_INVALID;
   }
+  for (size_t j = 0; j < nf; ++j) { d->fam_members += d->fams[j].count; d->fam_with_spine += d->fam_spines[j].spine >= 0; d->fam_rows_saved += saved[j]; }
   return LTR_OK;
 }
 
@@ -260,8 +295,10 @@ int describe_batch(const ltr_locus_batch* b, const ModelConsts& mc, const int F,
   const int64_t n_pairs_total = d->n_pairs;
   // haplotype families: their members leave the one-wave classes (the plan kernel never sees them) for a class of their own
   std::vector<FamilyRec> fam_recs;
+  FamilySide fam_side;
+  fam_side.keep_forks = d->keep_forks;
   if (d->use_plan && rules.sym_model && dbg.families >= 0)
-    form_families(b, mc, F, n_cu, dbg.families, dbg.family_min_rows > 0 ? dbg.family_min_rows : kFamMinRows, pair_base, w, &fam_recs);
+    form_families(b, mc, F, n_cu, dbg.families, dbg.family_min_rows > 0 ? dbg.family_min_rows : kFamMinRows, dbg.family_spine, pair_base, w, &fam_recs, &fam_side);
   if (rules.wg_wide4 && rules.wide4_quota != INT64_MAX) move_beyond_quota_to_eight_waves(rules.wide4_quota, w);
   LTR_DBG("plan: pairs described");
   // ---- bin by launch class, longest first inside a class (ltrp::sort_by_class; all host cores) ----
@@ -290,7 +327,7 @@ int describe_batch(const ltr_locus_batch* b, const ModelConsts& mc, const int F,
     for (size_t i = (size_t)c * kPlanBlock; i < std::min(pairs.size(), ((size_t)c + 1) * kPlanBlock); ++i) sorted[i] = pairs[(size_t)order[i]];
   }, 1);
   LTR_DBG("plan: gathered");
-  return resolve_families(fam_recs, w, d, err);
+  return resolve_families(fam_recs, fam_side, w, d, err);
 }
 
 }  // namespace ltrp

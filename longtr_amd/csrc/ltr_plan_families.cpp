@@ -129,6 +129,84 @@ bool family_pays(const FamilyCall& fc, const ReadGeom& g, const LocusWindows& lw
   return true;
 }
 
+// The spine (FamilySpine): which member the stream follows beyond p, where the others leave it, which of those rows are parked.
+// Forming is settled before this is asked: a spine only removes rows and one fill/drain, so a family that pays keeps paying.
+// Member k leaves spine s at f_k = max(p, min(lcp(s, k), n_k - 1)); s minimises (n_s - p) + sum(n_k - f_k), the first such member.
+// Of the distinct f_k beyond p at most kFamilyParkSlots - 1 are kept, the subset that saves most rows: with v_0 = p < v_1 < .. the
+// kept rows and N(v) the members with f_k >= v, sum (v_i - v_(i-1)) N(v_i); a member whose own row is not kept starts from the
+// nearest kept row below it (exact all the same: it runs those rows again).
+// In two parts.  spine_of_members: what the members and p alone decide -- the spine member, the fork rows, the park rows, every member's
+// slot; the reads of a locus mostly meet the same candidates at the same p, so the locus keeps the last answer (SpineMemo).
+// spine_for_read: what the read adds -- the certificate ranges n - m and the modelled steps (L lanes).
+// *sp and fork[] are written only for a family with a spine (sp->spine >= 0).
+struct SpineMemo { uint64_t members = 0; int p = -1; FamilySpine sp; int16_t fork[kFamilyMaxMembers]; };
+void spine_of_members(LocusWindows* lw, const Candidates& c, const int p, FamilySpine* sp, int16_t* fork) {
+  sp->spine = -1;
+  // (park rows, ranges and fork rows are 16-bit: a member's n is bounded by the one-wave class, n <= m + 600 <= kFamilyMaxC + 601 -- checked all the same)
+  for (int k = 0; k < c.n; ++k) if (lw->wn[c.h[k]] > 0x7fff) return;
+  const auto fork_of = [&](const int s, const int k) { return std::max(p, std::min(lw->lcp_of(c.h[s], c.h[k]), lw->wn[c.h[k]] - 1)); };
+  int best = -1; int64_t best_rows = 0; bool forks = false;
+  for (int s = 0; s < c.n; ++s) {
+    int64_t rows = lw->wn[c.h[s]] - p; bool any = false;
+    for (int k = 0; k < c.n; ++k) if (k != s) { const int f = fork_of(s, k); rows += lw->wn[c.h[k]] - f; any = any || f > p; }
+    if (best < 0 || rows < best_rows) { best = s; best_rows = rows; forks = any; }
+  }
+  if (!forks) return;                                              // nothing beyond p for the best member: nothing for any
+  std::memset(sp, 0, sizeof(*sp)); std::memset(fork, 0, sizeof(int16_t) * kFamilyMaxMembers);
+  // the distinct fork rows beyond p, ascending, and the members at or beyond each
+  int v[kFamilyMaxMembers + 1], N[kFamilyMaxMembers + 1], nv = 1;
+  v[0] = p; N[0] = 0;
+  for (int k = 0; k < c.n; ++k) { fork[k] = (int16_t)(k == best ? lw->wn[c.h[k]] : fork_of(best, k)); }
+  for (int k = 0; k < c.n; ++k) if (k != best && fork[k] > p) {
+    int at = 1;
+    while (at < nv && v[at] < fork[k]) ++at;
+    if (at == nv || v[at] != fork[k]) { for (int j = nv; j > at; --j) v[j] = v[j - 1]; v[at] = fork[k]; ++nv; }
+  }
+  sp->spine = (int8_t)best;
+  sp->slot_row[0] = (int16_t)p;
+  if (nv <= kFamilyParkSlots) {
+    // every fork row has a slot (the common case; each kept row saves rows, so this is also what the search below would find)
+    sp->n_slots = (int8_t)nv;
+    for (int j = 1; j < nv; ++j) sp->slot_row[j] = (int16_t)v[j];
+  } else {
+    for (int i = 1; i < nv; ++i) { N[i] = 0; for (int k = 0; k < c.n; ++k) if (k != best && fork[k] >= v[i]) ++N[i]; }
+    // the best kept subset of at most kFamilyParkSlots - 1 of them: gain[j][i] = most rows saved with j kept rows, v[i] the last
+    int64_t gain[kFamilyParkSlots][kFamilyMaxMembers + 1]; int from[kFamilyParkSlots][kFamilyMaxMembers + 1];
+    gain[0][0] = 0;
+    int bj = 0, bi = 0; int64_t bg = 0;
+    for (int j = 1; j < kFamilyParkSlots; ++j)
+      for (int i = j; i < nv; ++i) {
+        gain[j][i] = -1;
+        for (int i2 = j - 1; i2 < i; ++i2) {
+          if (j == 1 && i2 != 0) break;
+          const int64_t ga = gain[j - 1][i2] + (int64_t)(v[i] - v[i2]) * N[i];
+          if (ga > gain[j][i]) { gain[j][i] = ga; from[j][i] = i2; }
+        }
+        if (gain[j][i] > bg) { bg = gain[j][i]; bj = j; bi = i; }
+      }
+    sp->n_slots = (int8_t)(bj + 1);
+    for (int j = bj, i = bi; j >= 1; i = from[j][i], --j) sp->slot_row[j] = (int16_t)v[i];
+  }
+  for (int k = 0; k < c.n; ++k) if (k != best) {
+    int s = 0;
+    while (s + 1 < sp->n_slots && sp->slot_row[s + 1] <= fork[k]) ++s;
+    sp->slot_of[k] = (uint8_t)s;
+  }
+}
+// Returns the family's modelled steps as it is run.
+int64_t spine_for_read(const ReadGeom& g, const LocusWindows& lw, const Candidates& c, FamilySpine* sp) {
+  const int best = sp->spine;
+  int64_t steps = (lw.wn[c.h[best]] - 1) + (g.L - 1);
+  for (int k = 0; k < c.n; ++k) if (k != best) steps += (lw.wn[c.h[k]] - sp->slot_row[sp->slot_of[k]]) + (g.L - 1);
+  // the certificate's range from each park row on: the members of later slots and the spine member
+  for (int s = 0; s < sp->n_slots; ++s) {
+    int lo = lw.wn[c.h[best]] - (int)g.m, hi = lo;
+    for (int k = 0; k < c.n; ++k) if (k != best && sp->slot_of[k] > s) { const int dd = lw.wn[c.h[k]] - (int)g.m; lo = std::min(lo, dd); hi = std::max(hi, dd); }
+    sp->slot_dd_min[s] = (int16_t)lo; sp->slot_dd_max[s] = (int16_t)hi;
+  }
+  return steps;
+}
+
 // The count rule.
 // A launch of its own pays once the batch fills the GPU: one wavefront runs a family's stem and all its tails one after the other, so
 // a family lasts as long as ~H pairs on one wave slot, and the families are dealt out statically.  Measured on MI355X (config-3 loci,
@@ -159,19 +237,21 @@ void mark_members(const std::vector<FamilyRec>& fams, const BatchScratch& w) {
 
 }  // namespace
 
-void form_families(const ltr_locus_batch* b, const ModelConsts& mc, const int F, const int n_cu, const int knob, const int min_rows_in,
-                   const std::vector<int64_t>& pair_base, const BatchScratch& w, std::vector<FamilyRec>* out) {
+void form_families(const ltr_locus_batch* b, const ModelConsts& mc, const int F, const int n_cu, const int knob, const int min_rows_in, const int spine_knob,
+                   const std::vector<int64_t>& pair_base, const BatchScratch& w, std::vector<FamilyRec>* out, FamilySide* side) {
   FamilyCall fc{b, F, knob, std::max(min_rows_in, 2) /* (the stem has a row of its own) */, w,
                 (double)mc.g, (double)mc.d, (double)mc.a, (double)mc.c, (double)mc.f, (double)mc.match, {}};
   // (as far as a fork row can reach: p <= n - 1 and a member's n <= m + 600 <= kFamilyMaxC + 601)
   fc.lpc.assign((size_t)kFamilyMaxC + 600 + 4, 0.0);
   for (size_t j = 1; j + 1 < fc.lpc.size(); ++j) fc.lpc[j + 1] = fc.lpc[j] + (double)mc.c;
   std::vector<std::vector<FamilyRec>> per_locus((size_t)b->n_loci);
+  side->sp.assign((size_t)b->n_loci, {}); side->fork.assign((size_t)b->n_loci, {});
   ltr::parallel_for(b->n_loci, 64, [&](int64_t l) {
     const int64_t r0 = b->locus_read_off[l], r1 = b->locus_read_off[l + 1];
     const int64_t h0 = b->locus_hap_off[l], h1 = b->locus_hap_off[l + 1];
     if (h1 - h0 < 2 || h1 - h0 > kMaxH) return;
     LocusWindows lw;
+    SpineMemo memo;
     int64_t at = pair_base[(size_t)l];
     for (int64_t r = r0; r < r1; ++r) {
       if (b->realign_read && !b->realign_read[r]) continue;
@@ -187,14 +267,37 @@ void form_families(const ltr_locus_batch* b, const ModelConsts& mc, const int F,
       int p = 0; int64_t fam_steps = 0;
       if (!fork_and_bound(fc, g, &lw, &c, &p, &rec.U) || !family_pays(fc, g, lw, c, p, &rec.f, &fam_steps)) continue;
       rec.first_pair = c.i[0]; rec.row_at = row_at; rec.members = 0;
-      rec.key = launch_key((double)fam_steps * (g.W + kStepOverhead));
+      rec.steps = rec.plain_steps = (int32_t)fam_steps; rec.locus = (int32_t)l; rec.spine_at = -1;
+      rec.key = rec.plain_key = launch_key((double)fam_steps * (g.W + kStepOverhead));
+      if (spine_knob >= 0) {
+        // the spine records of a locus sit in lists of their own: the family list, which is joined, filtered and searched, stays lean
+        uint64_t haps = 0;
+        for (int k = 0; k < c.n; ++k) haps |= 1ull << c.h[k];
+        if (memo.p != p || memo.members != haps) { spine_of_members(&lw, c, p, &memo.sp, memo.fork); memo.p = p; memo.members = haps; }
+        if (memo.sp.spine >= 0) {
+          FamilySpine sp = memo.sp;
+          const int16_t* fork = memo.fork;
+          const int64_t steps = spine_for_read(g, lw, c, &sp);
+          std::vector<FamilySpine>& sps = side->sp[(size_t)l];
+          if (sps.empty()) sps.reserve((size_t)(r1 - r));             // (at most one per remaining read)
+          rec.spine_at = (int32_t)sps.size(); rec.steps = (int32_t)steps;
+          rec.key = launch_key((double)steps * (g.W + kStepOverhead));
+          sps.push_back(sp);
+          if (side->keep_forks) side->fork[(size_t)l].insert(side->fork[(size_t)l].end(), fork, fork + kFamilyMaxMembers);
+        }
+      }
       for (int k = 0; k < c.n; ++k) rec.members |= 1ull << (c.i[k] - row_at);
       per_locus[(size_t)l].push_back(rec);
     }
   });
   out->clear();
+  { size_t total = 0; for (const std::vector<FamilyRec>& v : per_locus) total += v.size(); out->reserve(total); }
   for (const std::vector<FamilyRec>& v : per_locus) out->insert(out->end(), v.begin(), v.end());     // (ascending first_pair: loci, then reads, in batch order)
   if (knob <= 0) count_rule(n_cu, out);
+  // The spine's own count rule: by rule (knob 0) a plan runs its families along spines only when it forms at least kSpinePerCu of them
+  // per CU; a smaller plan keeps plain families and the launch it had (knob 1: whenever a member forks beyond p).
+  if (spine_knob == 0 && (int64_t)out->size() < (int64_t)kSpinePerCu * std::max(n_cu, 1))
+    for (FamilyRec& r : *out) { r.spine_at = -1; r.steps = r.plain_steps; r.key = r.plain_key; }
   mark_members(*out, w);
 }
 

@@ -188,4 +188,43 @@ int ltr_debug_plan_families(const ltr_align_params* p, int mode, int n_cu, const
   } catch (...) { return LTR_ERR_NOMEM; }
 }
 
+int ltr_debug_plan_family_forks(const ltr_align_params* p, int mode, int n_cu, const ltr_locus_batch* b, const int32_t* knobs, int64_t* out,
+                                int fam_cap, int32_t* fam, int32_t* slot_row, int member_cap, int32_t* member_fork, int32_t* member_slot, int64_t* member_out) {
+  if (!p || !b || !knobs || !out || n_cu <= 0 || mode < -1 || mode > 8 || fam_cap < 0 || member_cap < 0) return LTR_ERR_INVALID;
+  if ((fam_cap > 0 && (!fam || !slot_row)) || (member_cap > 0 && (!member_fork || !member_slot || !member_out))) return LTR_ERR_INVALID;
+  ModelConsts mc = ltrp::model_consts_from(*p);
+  mc.match = (float)(-0.000100005); mc.mismatch = (float)(-9.0);     // (as ltr_debug_plan_families)
+  try {
+    HookScratch hs;
+    const ltrp::BatchScratch w = hs.view();
+    ltr::DebugKnobs dbg;
+    dbg.families = knobs[0]; dbg.family_min_rows = knobs[1]; dbg.family_spine = knobs[2];
+    ltrp::BatchPlan d;
+    d.keep_forks = true;
+    std::string why;
+    const int rc = ltrp::describe_batch(b, mc, p->indel_flank_len, mode, n_cu, dbg, w, &d, &why);
+    if (rc != LTR_OK) return rc;
+    out[0] = (int64_t)d.fams.size(); out[1] = d.fam_members; out[2] = d.fam_with_spine; out[3] = d.fam_rows_saved;
+    const int f0 = d.bin_first[ltrp::kFamClass];
+    for (int i = 0; i < (int)d.fams.size(); ++i) {
+      const FamilyDesc& f = d.fams[(size_t)i];
+      const FamilySpine& sp = d.fam_spines[(size_t)i];
+      const ltrp::FamilyForks& fk = d.fam_forks[(size_t)i];
+      if (i < fam_cap) {
+        const int32_t v[10] = {sp.spine, sp.n_slots, (int32_t)fk.steps, kFamilyParkSlots, f.first, f.count, f.p, f.W, f.dd_min, f.dd_max};
+        std::memcpy(fam + (size_t)i * 10, v, sizeof(v));
+        for (int s = 0; s < kFamilyParkSlots; ++s) slot_row[(size_t)i * kFamilyParkSlots + s] = s < sp.n_slots ? sp.slot_row[s] : 0;
+      }
+      for (int k = 0; k < f.count; ++k) {
+        const int at = f.first + k - f0;
+        if (at < 0 || at >= member_cap) continue;
+        member_fork[at] = sp.spine < 0 ? f.p : fk.fork[k];
+        member_slot[at] = sp.spine < 0 ? 0 : sp.slot_of[k];
+        member_out[at] = w.sorted[(size_t)(f.first + k)].out_idx;
+      }
+    }
+    return LTR_OK;
+  } catch (...) { return LTR_ERR_NOMEM; }
+}
+
 }  // extern "C"

@@ -298,7 +298,7 @@ int Execute::launch_class(const Launch& L, int li) {
     case kLaunchOne: ltrk::launch_onewave(L.W, sym, grid, ls, A); break;
     case kLaunchFamily: {
       FamilyArgs FA;
-      FA.fams = plan->d_fams; FA.n_fams = (int32_t)plan->fams.size(); FA.reserved = 0; FA.park = plan->d_fam_park; FA.stats = plan->d_fam_stats;
+      FA.fams = plan->d_fams; FA.n_fams = (int32_t)plan->fams.size(); FA.reserved = 0; FA.park = plan->d_fam_park; FA.stats = plan->d_fam_stats; FA.spines = plan->d_fam_spines;
       ltrk::launch_family(grid, ls, A, FA);
       break;
     }
@@ -557,6 +557,12 @@ int ltr_plan_family_stats(ltr_plan* plan, int64_t* out5) {
     HIP_TRY(ctx, hipMemcpy(c, plan->d_fam_stats, sizeof(c), hipMemcpyDeviceToHost));
     out5[2] = c[0]; out5[3] = c[1]; out5[4] = c[2];
   }
+  return LTR_OK;
+}
+
+int ltr_plan_family_spine_stats(const ltr_plan* plan, int64_t* out2) {
+  if (!plan || !out2) return LTR_ERR_INVALID;
+  out2[0] = plan->fam_with_spine; out2[1] = plan->fam_rows_saved;
   return LTR_OK;
 }
 
