@@ -126,8 +126,13 @@ def ll_genotype(ctx, todo):
                            [len(SAMPLES)] * len(todo), prune=True, fields={})
 
 
-def run(ctx, vcf_path=None, max_loci=None, tmp_dir="/tmp", ref_vcf=None, prune=False, device_fields=False, from_ll=False):
-    """ref_vcf: a bgzipped, tabix-indexed VCF whose records give the candidate alleles (--ref-vcf: read_vcf_alleles,
+def run(ctx, vcf_path=None, max_loci=None, tmp_dir="/tmp", ref_vcf=None, prune=False, device_fields=False, from_ll=False, consensus=False):
+    """consensus (not with ref_vcf): candidate alleles by ltr_build_haplotypes_consensus -- reads of a sample without an exact allele are clustered
+    and the clusters' partial-order-alignment consensus joins the candidates.  It runs only where more than a quarter of a sample's reads
+    carry no exact allele.  On the bundled HiFi trio that is not nowhere: 13 consensus alleles join the candidates and 5 of the 39 genotyped loci
+    print differently (homopolymers and one 5 kb repeat, where a sample's reads disagree with every exact allele), the other 34 are unchanged
+    (main prints how many consensus alleles came out).
+    ref_vcf: a bgzipped, tabix-indexed VCF whose records give the candidate alleles (--ref-vcf: read_vcf_alleles,
     add_vcf_haplotype_block); a locus without a record gets the status "no panel record".
     prune: discovery mode as the reference runs it (seq_stutter_genotyper.cpp:636-645) -- alleles no sample carries in its best
     haplotype pair are removed once and the posteriors recomputed over the surviving haplotypes (ltr_plan_genotype), so the
@@ -162,7 +167,11 @@ def run(ctx, vcf_path=None, max_loci=None, tmp_dir="/tmp", ref_vcf=None, prune=F
         if b"N" in ref[PAD - 250:len(ref) - PAD + 250]:
             loc["status"] = "reference not covered by matching reads"; continue
         rs = _lib.ReadSet(raw, len(SAMPLES), reg["start"], reg["stop"], ref, lo)
-        if panel is None:
+        if panel is None and consensus:
+            hb = ctx.build_haplotypes_consensus([dict(rs=rs, region_start=reg["start"], region_stop=reg["stop"], period=reg["period"],
+                                                      chrom_seq_start=lo, chrom_len=chrom_len[reg["chrom"]])])[0]
+            loc["consensus_alleles"] = sum(hb["inexact"] or [])
+        elif panel is None:
             hb = rs.build_haplotype(reg["start"], reg["stop"], reg["period"], lo, chrom_len[reg["chrom"]])
         else:
             rec = panel.alleles(reg["chrom"], reg["start"], reg["stop"])
@@ -261,9 +270,12 @@ def main():
     ap.add_argument("--prune-alleles", action="store_true", help="remove the alleles no sample is called with and genotype again (the reference's discovery mode)")
     ap.add_argument("--device-fields", action="store_true", help="needs --prune-alleles, not with --ref-vcf: the records' numbers from the device, all records formatted in one call")
     ap.add_argument("--from-ll", action="store_true", help="with --device-fields: no resident plan, the matrices of ltr_calc_hap_aln_probs go into ltr_ll_genotype")
+    ap.add_argument("--consensus", action="store_true", help="not with --ref-vcf: candidate alleles by ltr_build_haplotypes_consensus (reads without an exact allele clustered, POA consensus per cluster)")
     args = ap.parse_args()
     ctx = _lib.Context(0)
-    loci = run(ctx, args.out, ref_vcf=args.ref_vcf, prune=args.prune_alleles, device_fields=args.device_fields, from_ll=args.from_ll)
+    loci = run(ctx, args.out, ref_vcf=args.ref_vcf, prune=args.prune_alleles, device_fields=args.device_fields, from_ll=args.from_ll, consensus=args.consensus)
+    if args.consensus:
+        print(f"consensus alleles added over all loci: {sum(l.get('consensus_alleles', 0) for l in loci)}")
     for l in loci:
         if l["status"] != "ok":
             print(f"{l['region']['name']:>16} {l['region']['chrom']}:{l['region']['start']}-{l['region']['stop']}  skipped: {l['status']}")

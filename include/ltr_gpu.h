@@ -312,6 +312,8 @@ int  ltr_ctx_set_pair_packing(ltr_ctx* ctx, int mode);
  *   "trace"          1: ltr_calc_hap_aln_probs prints a timestamped phase profile to stderr
  *   "wg_first_pass"  first pass of the workgroup-per-pair classes (long reads): 1 = always the certificate kernels, 2 = always the
  *                    threshold kernels; rule: what the context has learnt, see ltr_ctx_wg_first_pass
+ *   "poa_group_cap_bytes", "poa_call_budget_bytes"   ltr_poa_consensus: its memory rule, lowered (see there; the cap decides which
+ *                    groups are aligned, so this one switch does change results)
  *   "reset"          every switch back to the library's rule */
 int  ltr_ctx_set_debug(ltr_ctx* ctx, const char* key, double value);
 /* Which kernels score the workgroup-per-pair classes (reads beyond 1281 bases, symmetric models) FIRST in the next
@@ -521,7 +523,7 @@ int64_t ltr_extract_sequence(const ltr_read_set* rs, int32_t i, int32_t region_s
  * alleles by the exact-sequence rules of gen_candidate_seqs :295-373, sorted and trimmed :474-480, :14-82) and
  * fuse_haplotype_blocks (:580-607) -> [flank <= 35 bp][repeat block][flank <= 35 bp].  The partial-order-alignment
  * clustering of reads without a candidate (:376-472, spoa) is NOT performed here (ltr_build_haplotypes_clustered below
- * does it, with medoids for the consensus); the result says how many reads / samples the reference would have clustered.  ctx may be NULL (it only receives the hap-build time).
+ * does it with medoids for the consensus, ltr_build_haplotypes_consensus with a partial-order-alignment consensus); the result says how many reads / samples the reference would have clustered.  ctx may be NULL (it only receives the hap-build time).
  * A failed construction (the reference's failure_msg_) is not an error status: blocks() is NULL, failure() the text.
  */
 typedef struct ltr_hap_result ltr_hap_result;
@@ -618,6 +620,60 @@ int ltr_build_haplotypes_clustered(ltr_ctx* ctx, const ltr_hap_build_locus* loci
                                    ltr_hap_result** out /* [n_loci] */);
 const uint8_t* ltr_hap_result_inexact(const ltr_hap_result* r);
 int32_t        ltr_hap_result_cluster_threshold(const ltr_hap_result* r, int32_t sample);
+
+/* ---- the consensus of a cluster: partial-order alignment on the GPU -------- */
+/*
+ * HaplotypeGenerator::poa (HaplotypeGenerator.cpp:167-199, called at :427) for every group of sequences: the consensus of the
+ * group's members.  This is partial-order alignment by the PUBLISHED method (Lee, Grasso & Sharlow 2002; heaviest-bundle
+ * consensus) with the scoring :169 hands to spoa (global, linear gap, match +1, mismatch -1, gap -1) and every tie rule fixed
+ * (restated as code in tests/poa_util.py); it is NOT spoa's bytes, and parity with spoa is not claimed.
+ *   members     in the group's order, each weighing 1 (:174-176); bytes compared for equality; empty members are dropped; none
+ *               left: the consensus is empty; one left: it is that member, nothing is launched; of more than 30 (:171) the members
+ *               at floor(k * n / 30), k = 0 .. 29, are taken in that order (the reference draws 30 at random, :182-192)
+ *   result      group g's consensus is out_bytes[out_off[g] .. out_off[g+1]); status[g] = 0, or 1: the group is over the memory
+ *               cap below, it was not aligned and its consensus is empty
+ * A sequence may lie in several groups; there is no limit on the distinct bytes of a group.  out_cap must be at least
+ * ltr_poa_consensus_capacity(sg) (the bytes of all groups; < 0 for a malformed sg).  Errors as ltr_edit_distances: LTR_ERR_INVALID +
+ * ltr_last_error naming the group, then nothing is launched and the outputs are untouched.  No CPU fallback: without a context
+ * LTR_ERR_NO_DEVICE, whatever the other arguments are, and nothing is launched.
+ * Memory rule (ltr_poa.hip: one wavefront per group, all groups of a call in as few launch sets as the budget allows).  A group
+ * of B bases in all and a longest member of L keeps 50 bytes a base of graph arrays (in LDS up to 16 KB, else in its scratch)
+ * and, for the traceback, the score rows of ONE alignment: (nodes + 1) x (L + 1) cells of 2 bytes while B + L <= 32767 and 4
+ * beyond.  Nodes are known only as the graph grows (at most B; in practice two or three per column).
+ *   per-group cap    512 MB: 30 x 5000-base reads (BASELINE config 5) at some 12 000 nodes are 12 001 x 5 401 x 4 = 259 MB; the cap
+ *                    is reached at 24 000 nodes for such reads, or by 8 x 16 000-base members.  The wavefront tests it before
+ *                    every alignment; a group over it reports status 1.
+ *   per-call budget  16 GB a launch set (a group's block is min(cap, what B and L allow at most)); further groups go to further sets.
+ * ltr_ctx_set_debug "poa_group_cap_bytes" / "poa_call_budget_bytes" lower both (0: the rule); the cap is the one switch that
+ * changes a result (which groups report status 1), the budget never does.
+ */
+int     ltr_poa_consensus(ltr_ctx* ctx, const ltr_seq_groups* sg, uint8_t* out_bytes, int64_t out_cap, int64_t* out_off /* [n_groups+1] */,
+                          uint8_t* status /* [n_groups]: 0 consensus, 1 over the cap: empty */);
+int64_t ltr_poa_consensus_capacity(const ltr_seq_groups* sg);
+/*
+ * ltr_build_haplotypes_clustered with the consensus where the reference calls poa (HaplotypeGenerator.cpp:427): the centre of a
+ * cluster is ltr_poa_consensus of its members in the cluster's order, not its medoid.  A consensus is none of the input
+ * sequences, so the refinement loop (:418-440) needs distances the first matrix does not hold, and runs as rounds over all
+ * (locus, sample) groups of the call at once:
+ *   1  phases A and B as in ltr_build_haplotypes_clustered; the capped matrix serves greedy_clustering at every threshold
+ *   2  host, per group that starts a threshold: the ladder step (:405) and greedy_clustering (:237-268; a 16th centroid: next T)
+ *   3  ONE ltr_poa_consensus call over every cluster of every group in refinement whose ordered member list has not been aligned
+ *      before in this call (the reference aligns unchanged clusters again; the method is deterministic, the answer is the same)
+ *   4  ONE ltr_edit_distances call, cap 701, over each group's new centres: equal ones folded into one cluster (:428-434), sorted
+ *      from the second on (:437)
+ *   5  host: merge_clusters (:271-293; j from 1, (centre i, centre j) argument order, the empty-second-argument exception); a
+ *      group that merged goes back to 3, the others to the acceptance (:446-469), and to the next threshold at 2 if they fail it
+ * The is-it-a-candidate-already test (:457-458) is made on the consensus string against the exact and inexact candidates so far,
+ * the samples of a locus in order.  New alleles are the consensus strings, flagged inexact; sort, trim and fuse are unchanged.  A
+ * cluster over the memory cap of ltr_poa_consensus keeps its medoid and is counted.  A locus where no sample needs clustering
+ * comes out byte-identical to ltr_build_haplotype.  Results, errors and ownership as ltr_build_haplotypes_clustered, and
+ *   ltr_hap_result_consensus_rounds   refinement rounds (:422) the sample took, over all thresholds it tried (0: not clustered)
+ *   ltr_hap_result_medoid_kept        how many of the sample's final clusters kept the medoid because of the cap
+ */
+int     ltr_build_haplotypes_consensus(ltr_ctx* ctx, const ltr_hap_build_locus* loci, int64_t n_loci, int32_t indel_flank_len,
+                                       ltr_hap_result** out /* [n_loci] */);
+int32_t ltr_hap_result_consensus_rounds(const ltr_hap_result* r, int32_t sample);
+int32_t ltr_hap_result_medoid_kept(const ltr_hap_result* r, int32_t sample);
 
 /* ---- neighbour of the path: haplotype -> reference-haplotype alignment (GPU) -------- */
 /*

@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("LTR_GPU_LIB") or os.path.join(CSRC, "libltr_gpu.so")   # override: A/B builds only
 KERNEL_TUS = ["ltr_k_one.hip", "ltr_k_pack.hip", "ltr_k_plan.hip", "ltr_k_wg.hip", "ltr_k_wgt.hip", "ltr_k_exact.hip", "ltr_k_family.hip"]      # one family of DP kernels each
 PLAN_UNITS = ["ltr_plan_rules.cpp", "ltr_plan_sort.cpp", "ltr_plan_families.cpp", "ltr_plan_describe.cpp", "ltr_plan_schedule.cpp", "ltr_plan_hooks.cpp"]      # host-side planning (csrc/ltr_plan.h)
-SOURCES = ["ltr_ctx.hip", "ltr_plan_build.hip", "ltr_plan_run.hip", "ltr_posterior.hip", "ltr_plan_genotype.hip", "ltr_plan_fields.hip"] + KERNEL_TUS + ["ltr_short.hip", "ltr_nw.hip"] + PLAN_UNITS + ["ltr_host.cpp", "ltr_hap_aln.cpp", "ltr_genotype.cpp", "ltr_vcf.cpp", "ltr_prep.cpp", "ltr_io.cpp", "ltr_bam.cpp", "ltr_vcf_in.cpp", "ltr_editdist.hip", "ltr_cluster.cpp"]
+SOURCES = ["ltr_ctx.hip", "ltr_plan_build.hip", "ltr_plan_run.hip", "ltr_posterior.hip", "ltr_plan_genotype.hip", "ltr_plan_fields.hip"] + KERNEL_TUS + ["ltr_short.hip", "ltr_nw.hip"] + PLAN_UNITS + ["ltr_host.cpp", "ltr_hap_aln.cpp", "ltr_genotype.cpp", "ltr_vcf.cpp", "ltr_prep.cpp", "ltr_io.cpp", "ltr_bam.cpp", "ltr_vcf_in.cpp", "ltr_editdist.hip", "ltr_poa.hip", "ltr_cluster.cpp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-honor-nans", "-std=c++17", "-fPIC", "-shared", "-pthread", "-Wall"]
 LINK_LIBS = ["-lz"]                                         # BGZF blocks (ltr_bgzf.h: BAM, VCF writer, tabix-indexed VCF input)
 
@@ -52,6 +52,7 @@ EXPORTS = [
     "ltr_edit_distances", "ltr_cluster_sequences", "ltr_cluster_result_threshold", "ltr_cluster_result_n_clusters", "ltr_cluster_result_centroids",
     "ltr_cluster_result_new_allele", "ltr_cluster_result_counted", "ltr_cluster_result_members", "ltr_cluster_result_free",
     "ltr_build_haplotypes_clustered", "ltr_hap_result_inexact", "ltr_hap_result_cluster_threshold",
+    "ltr_poa_consensus", "ltr_poa_consensus_capacity", "ltr_build_haplotypes_consensus", "ltr_hap_result_consensus_rounds", "ltr_hap_result_medoid_kept",
 ]
 
 
@@ -443,12 +444,25 @@ class Context:
         """ltr_edit_distances: groups = list of lists of bytes; per group the U x U int32 matrix min(levenshtein, cap)."""
         return edit_distances(self, groups, cap)
 
+    def poa_consensus(self, groups, with_status=False):
+        """ltr_poa_consensus: groups = list of lists of bytes; per group its partial-order-alignment consensus."""
+        return poa_consensus(self, groups, with_status=with_status)
+
     def build_haplotypes_clustered(self, loci, indel_flank_len=5):
         """ltr_build_haplotypes_clustered.  loci: list of dict(rs=ReadSet, region_start, region_stop, period, chrom_seq_start, chrom_len).
         Per locus the dict of ReadSet.build_haplotype + inexact (per allele of the repeat block, None for a failed construction)
         + cluster_threshold (per sample: accepted T, -1 none, 0 not needed)."""
+        return self._build_haplotypes(loci, indel_flank_len, consensus=False)
+
+    def build_haplotypes_consensus(self, loci, indel_flank_len=5):
+        """ltr_build_haplotypes_consensus: build_haplotypes_clustered with the partial-order-alignment consensus of a cluster as its
+        centre (ltr_poa_consensus).  Per locus the same dict + consensus_rounds and medoid_kept (per sample)."""
+        return self._build_haplotypes(loci, indel_flank_len, consensus=True)
+
+    def _build_haplotypes(self, loci, indel_flank_len, consensus):
         L = lib()
-        L.ltr_build_haplotypes_clustered.argtypes = [C.c_void_p, C.POINTER(_abi.HapBuildLocus), C.c_int64, C.c_int32, C.POINTER(C.c_void_p)]
+        fn = L.ltr_build_haplotypes_consensus if consensus else L.ltr_build_haplotypes_clustered
+        fn.argtypes = [C.c_void_p, C.POINTER(_abi.HapBuildLocus), C.c_int64, C.c_int32, C.POINTER(C.c_void_p)]
         arr = (_abi.HapBuildLocus * max(len(loci), 1))()
         for i, l in enumerate(loci):
             rs = l["rs"]
@@ -456,8 +470,8 @@ class Context:
             arr[i].chrom_seq = rs.chrom.ctypes.data_as(C.POINTER(C.c_uint8))
             arr[i].chrom_seq_start, arr[i].chrom_seq_len, arr[i].chrom_len = l["chrom_seq_start"], len(rs.chrom), l["chrom_len"]
         out = (C.c_void_p * max(len(loci), 1))()
-        self._check(L.ltr_build_haplotypes_clustered(self._h, arr, len(loci), int(indel_flank_len), out))
-        return [_hap_result(C.c_void_p(out[i]), n_samples=l["rs"].n_samples) for i, l in enumerate(loci)]
+        self._check(fn(self._h, arr, len(loci), int(indel_flank_len), out))
+        return [_hap_result(C.c_void_p(out[i]), n_samples=l["rs"].n_samples, consensus=consensus) for i, l in enumerate(loci)]
 
     def close(self):
         if self._h:
@@ -1527,6 +1541,31 @@ def edit_distances(ctx, groups, cap, dist=None, packed=None):
     return out
 
 
+def poa_consensus(ctx, groups, packed=None, with_status=False, out=None):
+    """ltr_poa_consensus (ctx None: the call without a context, LTR_ERR_NO_DEVICE).  groups = list of lists of bytes; per group its
+    consensus (bytes), with_status: (consensus list, status list: 1 = over the memory cap, not aligned).  out: optional dict(bytes=uint8
+    array, off=int64 array, status=uint8 array) the call writes into (left as they are on an error)."""
+    L = lib()
+    L.ltr_poa_consensus.argtypes = [C.c_void_p, C.POINTER(_abi.SeqGroups), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.ltr_poa_consensus_capacity.argtypes, L.ltr_poa_consensus_capacity.restype = [C.POINTER(_abi.SeqGroups)], C.c_int64
+    pk = packed or pack_seq_groups(groups)
+    n = pk["sg"].n_groups
+    if out is None:
+        cap = L.ltr_poa_consensus_capacity(C.byref(pk["sg"]))
+        if cap < 0:
+            raise LtrError(int(cap), "ltr_poa_consensus_capacity")
+        out = dict(bytes=np.zeros(max(int(cap), 1), dtype=np.uint8), off=np.zeros(n + 1, dtype=np.int64), status=np.zeros(max(n, 1), dtype=np.uint8))
+        cap = int(cap)
+    else:
+        cap = out.get("cap", len(out["bytes"]))
+    rc = L.ltr_poa_consensus(None if ctx is None else ctx._h, C.byref(pk["sg"]), _p(out["bytes"]), cap, _p(out["off"]), _p(out["status"]))
+    if rc != 0:
+        raise LtrError(rc, lib().ltr_last_error(ctx._h).decode() if ctx is not None else "ltr_poa_consensus")
+    raw, off = out["bytes"].tobytes(), out["off"]
+    cons = [raw[off[g]:off[g + 1]] for g in range(n)]
+    return (cons, [int(x) for x in out["status"][:n]]) if with_status else cons
+
+
 def cluster_sequences(seqs, counts, dist, candidates=()):
     """ltr_cluster_sequences (host, no GPU): dict(threshold, clusters=[dict(centroid, members, counted, new_allele)...])."""
     L = lib()
@@ -1566,9 +1605,10 @@ def cluster_sequences(seqs, counts, dist, candidates=()):
         L.ltr_cluster_result_free(h)
 
 
-def _hap_result(h, n_samples=None):
+def _hap_result(h, n_samples=None, consensus=False):
     """An ltr_hap_result as dict(blocks=[...] or None, failure, unplaced_reads, samples_needing_clustering); frees it.
-    n_samples given (ltr_build_haplotypes_clustered): + inexact, cluster_threshold."""
+    n_samples given (ltr_build_haplotypes_clustered): + inexact, cluster_threshold; consensus (ltr_build_haplotypes_consensus): +
+    consensus_rounds, medoid_kept."""
     L = lib()
     L.ltr_hap_result_blocks.argtypes, L.ltr_hap_result_blocks.restype = [C.c_void_p], C.POINTER(_abi.HaplotypeBlocks)
     L.ltr_hap_result_failure.argtypes, L.ltr_hap_result_failure.restype = [C.c_void_p], C.c_char_p
@@ -1594,6 +1634,10 @@ def _hap_result(h, n_samples=None):
         ip = L.ltr_hap_result_inexact(h)
         out["inexact"] = [int(ip[i]) for i in range(len(out["blocks"][1]["alleles"]))] if (ip and out["blocks"]) else None
         out["cluster_threshold"] = [L.ltr_hap_result_cluster_threshold(h, s) for s in range(n_samples)]
+        if consensus:
+            L.ltr_hap_result_consensus_rounds.argtypes = L.ltr_hap_result_medoid_kept.argtypes = [C.c_void_p, C.c_int32]
+            out["consensus_rounds"] = [L.ltr_hap_result_consensus_rounds(h, s) for s in range(n_samples)]
+            out["medoid_kept"] = [L.ltr_hap_result_medoid_kept(h, s) for s in range(n_samples)]
     L.ltr_hap_result_free(h)
     return out
 

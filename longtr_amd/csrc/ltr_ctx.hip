@@ -223,6 +223,8 @@ int ltr_ctx_set_debug(ltr_ctx* ctx, const char* key, double value) {
   else if (k == "chain_min_w") ctx->dbg.chain_min_w = (int)value;
   else if (k == "chain_max_w") ctx->dbg.chain_max_w = (int)value;
   else if (k == "wave_clock") ctx->dbg.wave_clock = (int)value;
+  else if (k == "poa_group_cap_bytes") ctx->dbg.poa_group_cap_bytes = (int64_t)value;
+  else if (k == "poa_call_budget_bytes") ctx->dbg.poa_call_budget_bytes = (int64_t)value;
   else if (k == "pageable_staging" || k == "reset") {            // A/B: 1 = the library's own staging arrays in pageable memory again ("reset": pinned, the default)
     const bool pin = (k == "reset") || value == 0.0;
     if (pin != ctx->host_bytes[0].pinned) {

@@ -257,6 +257,8 @@ struct DebugKnobs {
   int families = 0;             // haplotype families (ltr_dp_family.hpp): -1 = never, 0 = by rule (where modelled cheaper), 1 = whenever one can be formed from reads of 641 .. 1280 columns, 2 = ... of 321 .. 1280
   int family_min_rows = 0;      // ... fewest shared rows (0: ltrp::kFamMinRows)
   int family_spine = 0;         // ... run along a spine (ltr_dp_family.hpp, spine_walk): -1 = never (plain families), 0 = by rule (plans of ltrp::kSpinePerCu families per CU and more), 1 = in any plan
+  int64_t poa_group_cap_bytes = 0;    // ltr_poa_consensus: scratch of one group at most (rule: 512 MB); a group over it is not aligned (status 1) -- the one switch results depend on
+  int64_t poa_call_budget_bytes = 0;  // ... scratch of one launch set at most (rule: 16 GB)
 };
 DebugKnobs ctx_debug(const ltr_ctx* ctx);
 

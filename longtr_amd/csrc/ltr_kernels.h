@@ -57,6 +57,19 @@ hipError_t occ_exact(int which, int* per_cu);
 void launch_exact(int which, bool sym, dim3 grid, hipStream_t st, const KernelArgs& A);
 int exact_block_threads(int which);
 
+// the consensus kernel (ltr_poa.hip): one wavefront per group of sequences, from its first sequence to its consensus; grid.x = the
+// groups of the launch set, lds_bytes = the largest graph block of a group that keeps its graph arrays in LDS
+struct PoaSeq { int64_t off; int32_t len, pad; };               // a member: its bytes in the call's sequence buffer
+struct PoaGroup {
+  int64_t first_seq;                                            // its members: seqs[first_seq .. first_seq + n_members)
+  int64_t scratch_off, graph_bytes, h_bytes;                    // its scratch block: [graph arrays, unless in LDS][score rows: h_bytes]
+  int64_t out_off;                                              // its consensus (at most n_ub bytes)
+  int32_t n_members, n_ub, l_max;                               // n_ub: bases of all members = the most nodes (and edges); l_max: the longest member
+  int32_t wide, graph_in_lds, slot;                             // wide: int32 score cells (else int16); slot: where its length and status go
+};
+void launch_poa(dim3 grid, size_t lds_bytes, hipStream_t st, const PoaGroup* groups, const PoaSeq* seqs, const uint8_t* bytes, uint8_t* scratch,
+                uint8_t* out, int32_t* out_len, int32_t* status);
+
 }  // namespace ltrk
 
 #endif

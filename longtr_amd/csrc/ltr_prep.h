@@ -16,7 +16,8 @@ struct ltr_hap_result {
   ltr_haplotype_blocks view;
   std::string failure;
   int32_t unplaced = 0, needs_clustering = 0;
-  std::vector<int32_t> cluster_threshold;                       // per sample: accepted T, -1 none, 0 not needed (ltr_build_haplotypes_clustered only)
+  std::vector<int32_t> cluster_threshold;                       // per sample: accepted T, -1 none, 0 not needed (ltr_build_haplotypes_clustered / _consensus only)
+  std::vector<int32_t> consensus_rounds, medoid_kept;           // per sample: refinement rounds taken; final clusters that kept the medoid (ltr_build_haplotypes_consensus only)
 };
 
 namespace ltr {
