@@ -1,8 +1,10 @@
-"""ctypes mirror of include/ltr_gpu.h (structs + flattening helpers).
+"""ctypes mirror of include/ltr_gpu.h (structs + flattening helpers + the signature of every function).
 
 Pure data-layout code: no compute lives here.  The product binding
-(longtr_amd/_lib.py) uses these structs; the test-side checker reuses them so
-that the same flattened inputs go to both sides.
+(longtr_amd/_lib.py and the modules behind it) uses these structs; the test-side
+checker reuses them so that the same flattened inputs go to both sides.
+SIGNATURES at the end is the one place a C signature is written down in Python:
+_loader.lib() applies it to the loaded library once, through bind().
 """
 import ctypes as C
 
@@ -504,3 +506,224 @@ class RawAlignment(C.Structure):
     _fields_ = [("pos", C.c_int32), ("end_pos", C.c_int32), ("bases", C.POINTER(C.c_uint8)), ("quals", C.POINTER(C.c_uint8)),
                 ("length", C.c_int32), ("n_cigar", C.c_int32), ("cigar_type", C.c_char_p), ("cigar_num", C.POINTER(C.c_int32)),
                 ("sample", C.c_int32), ("haplotype_tag", C.c_int32), ("reverse", C.c_uint8), ("use_for_hap_generation", C.c_uint8)]
+
+
+class BamRecord(C.Structure):
+    """struct ltr_bam_record."""
+
+    _fields_ = [("name", C.c_char_p), ("file_index", C.c_int32), ("ref_id", C.c_int32), ("pos", C.c_int32), ("end_pos", C.c_int32),
+                ("mapq", C.c_int32), ("flag", C.c_int32), ("mate_ref_id", C.c_int32), ("mate_pos", C.c_int32), ("tlen", C.c_int32),
+                ("length", C.c_int32), ("bases", C.c_char_p), ("quals", C.c_char_p), ("n_cigar", C.c_int32), ("cigar_type", C.c_char_p),
+                ("cigar_num", C.POINTER(C.c_int32)), ("aux", C.POINTER(C.c_uint8)), ("aux_len", C.c_int32)]
+
+
+# ---- the C signatures ---------------------------------------------------------------------------------
+# name -> (return type, [parameter types]) for every function include/ltr_gpu.h declares, written from the header
+# (tests/test_abi_signatures.py parses the header and holds this table to it).  Scalars have the header's width and kind.
+# Pointers: a struct with a mirror above is POINTER(that struct); an opaque handle (ltr_ctx*, ltr_plan*, ...) and any
+# buffer of numbers is c_void_p, which takes a numpy address, byref(), a ctypes array or None alike; handle** is
+# POINTER(c_void_p); char* is c_char_p, except text the library allocates (ltr_genotype_result_vcf_records ->
+# ltr_vcf_text_free), which stays a c_void_p so that it is never copied into a bytes object.  A returned pointer is typed.
+_P = C.POINTER
+_vp, _str, _int, _sz = C.c_void_p, C.c_char_p, C.c_int, C.c_size_t
+_u8, _i32, _u32, _i64, _f32, _f64 = C.c_uint8, C.c_int32, C.c_uint32, C.c_int64, C.c_float, C.c_double
+
+SIGNATURES = {
+    "ltr_default_params": (None, [_P(AlignParams)]),
+    "ltr_default_stutter_params": (None, [_P(StutterParams)]),
+    "ltr_ctx_set_stutter_params": (_int, [_vp, _P(StutterParams)]),
+    "ltr_ctx_set_pair_packing": (_int, [_vp, _int]),
+    "ltr_ctx_set_debug": (_int, [_vp, _str, _f64]),
+    "ltr_ctx_wg_first_pass": (_int, [_vp, _vp, _vp]),
+    "ltr_ctx_create": (_int, [_int, _P(_vp)]),
+    "ltr_ctx_destroy": (None, [_vp]),
+    "ltr_ctx_set_params": (_int, [_vp, _P(AlignParams)]),
+    "ltr_last_error": (_str, [_vp]),
+    "ltr_ctx_device_info": (_int, [_vp, _str, _int, _vp, _vp]),
+    "ltr_align_batch": (_int, [_vp, _P(LocusBatch), _vp, _vp]),
+    "ltr_plan_create": (_int, [_vp, _P(LocusBatch), _P(_vp)]),
+    "ltr_plan_destroy": (None, [_vp]),
+    "ltr_plan_num_pairs": (_i64, [_vp]),
+    "ltr_plan_ll_size": (_i64, [_vp]),
+    "ltr_plan_cells": (_f64, [_vp]),
+    "ltr_plan_input_bytes": (_f64, [_vp]),
+    "ltr_plan_execute": (_int, [_vp, _vp, _vp]),
+    "ltr_plan_fetch": (_int, [_vp, _vp, _vp]),
+    "ltr_plan_last_kernel_ms": (_int, [_vp, _vp, _vp]),
+    "ltr_num_kernels": (_int, []),
+    "ltr_kernel_lanes_per_pair": (_int, [_int]),
+    "ltr_kernel_family": (_int, [_int]),
+    "ltr_plan_set_timing": (_int, [_vp, _int]),
+    "ltr_plan_kernel_stats": (_int, [_vp, _int, _vp, _vp, _vp, _vp]),
+    "ltr_plan_kernel_ranges": (_int, [_vp, _int, _vp, _vp, _vp]),
+    "ltr_plan_debug_wave_clocks": (_int, [_vp, _vp, _i64]),
+    "ltr_plan_debug_entries": (_int, [_vp, _vp, _vp, _vp, _vp, _int]),
+    "ltr_plan_kernel_class": (_int, [_vp]),
+    "ltr_plan_family_stats": (_int, [_vp, _vp]),
+    "ltr_plan_family_spine_stats": (_int, [_vp, _vp]),
+    "ltr_process_reads": (_int, [_vp, _P(HaplotypeBlocks), _vp, _P(Alignment), _i32, _i32, _vp, _vp, _vp]),
+    "ltr_calc_hap_aln_probs": (_int, [_vp, _P(Locus), _i64, _P(_vp), _P(_vp)]),
+    "ltr_haplotype_num_combs": (_i64, [_P(HaplotypeBlocks)]),
+    "ltr_haplotype_seq": (_i64, [_P(HaplotypeBlocks), _i64, _vp, _i64]),
+    "ltr_trim_alignment": (_int, [_P(Alignment), _i32, _i32, _i32, _vp, _vp]),
+    "ltr_pool_reads": (_i32, [_P(_vp), _vp, _i32, _vp]),
+    "ltr_scatter_pool_probs": (_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ltr_posteriors": (_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "ltr_plan_posteriors": (_int, [_vp, _P(PosteriorBatch), _vp, _vp, _vp]),
+    "ltr_extract_genotypes": (_int, [_i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _P(GenotypeFields)]),
+    "ltr_ctx_timers": (_int, [_vp, _P(Timers), _int]),
+    "ltr_haps_to_alleles": (_int, [_P(HaplotypeBlocks), _i32, _vp]),
+    "ltr_unused_alleles": (_i32, [_i32, _vp, _vp, _vp, _i32, _vp, _i32, _vp]),
+    "ltr_remap_haplotypes": (_int, [_P(HaplotypeBlocks), _P(HaplotypeBlocks), _vp, _vp]),
+    "ltr_remap_aln_probs": (_int, [_vp, _i32, _i32, _vp, _i32, _vp]),
+    "ltr_default_vcf_options": (None, [_P(VcfOptions)]),
+    "ltr_get_alleles": (_i32, [_P(VcfLocus), _vp, _str, _i64, _vp]),
+    "ltr_vcf_record": (_i64, [_P(VcfLocus), _P(VcfOptions), _str, _i64, _vp]),
+    "ltr_vcf_header": (_i64, [_str, _str, _str, _P(VcfOptions), _P(_str), _i32, _str, _i64]),
+    "ltr_haplotype_aln_info_capacity": (_i64, [_vp, _i64]),
+    "ltr_haplotype_align_to_ref": (_int, [_vp, _vp, _i64, _str, _i64, _vp]),
+    "ltr_left_align_reads": (_int, [_P(RawAlignment), _i32, _i32, _i32, _i32, _vp, _i64, _i64, _P(_vp)]),
+    "ltr_phasing_priors": (_int, [_i32, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "ltr_read_set_size": (_i32, [_vp]),
+    "ltr_read_set_alignments": (_P(Alignment), [_vp]),
+    "ltr_read_set_alignment_strings": (_P(_str), [_vp]),
+    "ltr_read_set_deleted": (_P(_u8), [_vp]),
+    "ltr_read_set_source": (_P(_i32), [_vp]),
+    "ltr_read_set_sample": (_P(_i32), [_vp]),
+    "ltr_read_set_n_p1s": (_P(_i32), [_vp]),
+    "ltr_read_set_n_p2s": (_P(_i32), [_vp]),
+    "ltr_read_set_fail_count": (_i32, [_vp]),
+    "ltr_read_set_free": (None, [_vp]),
+    "ltr_extract_sequence": (_i64, [_vp, _i32, _i32, _i32, _vp, _i64]),
+    "ltr_build_haplotype": (_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _i64, _i64, _i32, _P(_vp)]),
+    "ltr_build_vcf_haplotype": (_int, [_vp, _vp, _i32, _str, _vp, _i32, _i32, _vp, _i64, _i64, _i64, _P(_vp)]),
+    "ltr_hap_result_blocks": (_P(HaplotypeBlocks), [_vp]),
+    "ltr_hap_result_failure": (_str, [_vp]),
+    "ltr_hap_result_unplaced_reads": (_i32, [_vp]),
+    "ltr_hap_result_samples_needing_clustering": (_i32, [_vp]),
+    "ltr_hap_result_free": (None, [_vp]),
+    "ltr_version": (_str, []),
+    "ltr_abi_version": (_int, []),
+    "ltr_ctx_timers_n": (_int, [_vp, _vp, _sz, _int]),
+    "ltr_ctx_short_kernel_split": (_int, [_vp, _vp, _int]),
+    "ltr_ctx_set_host_threads": (_int, [_vp, _int]),
+    "ltr_ctx_host_threads": (_int, [_vp]),
+    "ltr_host_threads_rule": (_int, [_int]),
+    "ltr_debug_parallel_threads": (_int, [_int, _i64, _int]),
+    "ltr_debug_prep_ahead_rule": (_int, [_int]),
+    "ltr_debug_num_classes": (_int, []),
+    "ltr_debug_class_info": (_int, [_int, _vp, _vp, _vp, _vp]),
+    "ltr_debug_classify": (_int, [_P(AlignParams), _int, _int, _i64, _i64, _i32, _i32, _i32, _int, _vp, _vp, _vp]),
+    "ltr_debug_sort_by_class": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp]),
+    "ltr_debug_pair_costs": (_int, [_P(AlignParams), _int, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "ltr_debug_threshold_table": (_int, [_f32, _vp, _i64]),
+    "ltr_debug_calc_seed_base": (_int, [_vp, _vp]),          # (struct pointers; the test-side checker passes them as plain addresses)
+    "ltr_read_regions": (_int, [_str, _u32, _str, _P(_vp), _str, _int]),
+    "ltr_region_set_size": (_i64, [_vp]),
+    "ltr_region_set_lines_read": (_i32, [_vp]),
+    "ltr_region_set_order": (None, [_vp]),
+    "ltr_region_set_free": (None, [_vp]),
+    "ltr_region_chrom": (_str, [_vp, _i64]),
+    "ltr_region_name": (_str, [_vp, _i64]),
+    "ltr_region_motif": (_str, [_vp, _i64]),
+    "ltr_region_period_str": (_str, [_vp, _i64]),
+    "ltr_region_start": (_i32, [_vp, _i64]),
+    "ltr_region_stop": (_i32, [_vp, _i64]),
+    "ltr_region_period": (_i32, [_vp, _i64]),
+    "ltr_fasta_open": (_int, [_str, _P(_vp), _str, _int]),
+    "ltr_fasta_close": (None, [_vp]),
+    "ltr_fasta_num_seqs": (_i64, [_vp]),
+    "ltr_fasta_seq_name": (_str, [_vp, _i64]),
+    "ltr_fasta_seq_len": (_i64, [_vp, _str]),
+    "ltr_fasta_fetch": (_i64, [_vp, _str, _i64, _i64, _str, _i64, _str, _int]),
+    "ltr_fasta_contig_lines": (_i64, [_vp, _str, _i64]),
+    "ltr_vcf_writer_open": (_int, [_str, _P(_vp)]),
+    "ltr_vcf_writer_header": (_int, [_vp, _str]),
+    "ltr_vcf_writer_add_record": (_int, [_vp, _str, _i32, _str]),
+    "ltr_vcf_writer_close": (_int, [_vp]),
+    "ltr_bam_open": (_int, [_P(_str), _i32, _i32, _P(_vp), _str, _int]),
+    "ltr_bam_close": (None, [_vp]),
+    "ltr_bam_num_refs": (_i32, [_vp]),
+    "ltr_bam_ref_name": (_str, [_vp, _i32]),
+    "ltr_bam_ref_len": (_i64, [_vp, _i32]),
+    "ltr_bam_num_read_groups": (_i32, [_vp]),
+    "ltr_bam_read_group_id": (_str, [_vp, _i32]),
+    "ltr_bam_read_group_sample": (_str, [_vp, _i32]),
+    "ltr_bam_read_group_library": (_str, [_vp, _i32]),
+    "ltr_bam_read_group_file": (_i32, [_vp, _i32]),
+    "ltr_bam_set_region": (_int, [_vp, _str, _i32, _i32]),
+    "ltr_bam_next": (_int, [_vp, _P(BamRecord)]),
+    "ltr_bam_aux_int": (_int, [_P(BamRecord), _str, _vp]),
+    "ltr_bam_aux_float": (_int, [_P(BamRecord), _str, _vp]),
+    "ltr_bam_aux_char": (_int, [_P(BamRecord), _str, _vp]),
+    "ltr_bam_aux_string": (_str, [_P(BamRecord), _str]),
+    "ltr_vcf_reader_open": (_int, [_str, _P(_vp), _str, _int]),
+    "ltr_vcf_reader_close": (None, [_vp]),
+    "ltr_vcf_read_alleles": (_int, [_vp, _str, _i32, _i32, _vp, _str, _i64, _vp, _vp]),
+    "ltr_vcf_index": (_int, [_str]),
+    "ltr_debug_vcf_query": (_i64, [_vp, _str, _i64, _i64, _str, _i64]),
+    "ltr_debug_tbi_parse": (_i32, [_str, _vp, _vp, _i32, _str, _i64]),
+    "ltr_prune_hap_blocks": (_int, [_P(HaplotypeBlocks), _i32, _vp, _i32, _P(_vp)]),
+    "ltr_plan_genotype": (_int, [_vp, _P(GenotypeBatch), _P(_vp)]),
+    "ltr_genotype_result_free": (None, [_vp]),
+    "ltr_genotype_result_n_loci": (_i64, [_vp]),
+    "ltr_genotype_result_n_haps": (_i32, [_vp, _i64]),
+    "ltr_genotype_result_new_to_old": (_P(_i32), [_vp, _i64]),
+    "ltr_genotype_result_allele_mapping": (_P(_i32), [_vp, _i64]),
+    "ltr_genotype_result_removed": (_i32, [_vp, _i64, _i32, _P(_P(_i32))]),
+    "ltr_genotype_result_num_aff_blocks": (_i32, [_vp, _i64]),
+    "ltr_genotype_result_num_aff_alleles": (_i32, [_vp, _i64]),
+    "ltr_genotype_result_blocks": (_P(HaplotypeBlocks), [_vp, _i64]),
+    "ltr_genotype_result_log_sample_posteriors": (_P(_f64), [_vp, _i64]),
+    "ltr_genotype_result_sample_total_ll": (_P(_f64), [_vp, _i64]),
+    "ltr_genotype_result_gts": (_P(_i32), [_vp, _i64]),
+    "ltr_genotype_result_read_ll": (_P(_f64), [_vp, _i64]),
+    "ltr_plan_genotype_fields": (_int, [_vp, _P(GenotypeBatch), _P(FieldsRequest), _P(_vp)]),
+    "ltr_genotype_result_fields": (_int, [_vp, _i64, _P(LocusFields)]),
+    "ltr_genotype_result_vcf_records": (_int, [_vp, _P(VcfLocus), _P(VcfOptions), _P(_vp), _vp, _vp]),
+    "ltr_vcf_text_free": (None, [_vp]),
+    "ltr_vcf_fields": (_int, [_P(VcfLocus), _i32, _i32, _i32, _P(_vp)]),
+    "ltr_vcf_field_set_view": (_P(LocusFields), [_vp]),
+    "ltr_vcf_field_set_free": (None, [_vp]),
+    "ltr_vcf_record_from_fields": (_i64, [_P(VcfLocus), _P(LocusFields), _P(VcfOptions), _str, _i64, _vp]),
+    "ltr_ll_genotype": (_int, [_vp, _P(LlBatch), _P(GenotypeBatch), _P(FieldsRequest), _P(_vp)]),
+    "ltr_plan_posteriors_ploidy": (_int, [_vp, _P(PosteriorBatch), _vp, _vp, _vp, _vp]),
+    "ltr_plan_genotype_ploidy": (_int, [_vp, _P(GenotypeBatch), _P(FieldsRequest), _vp, _P(_vp)]),
+    "ltr_ll_genotype_ploidy": (_int, [_vp, _P(LlBatch), _P(GenotypeBatch), _P(FieldsRequest), _vp, _P(_vp)]),
+    "ltr_genotype_result_haploid": (_i32, [_vp, _i64]),
+    "ltr_edit_distances": (_int, [_vp, _P(SeqGroups), _i32, _vp, _vp]),
+    "ltr_cluster_sequences": (_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _P(_vp)]),
+    "ltr_cluster_result_threshold": (_i32, [_vp]),
+    "ltr_cluster_result_n_clusters": (_i32, [_vp]),
+    "ltr_cluster_result_centroids": (_P(_i32), [_vp]),
+    "ltr_cluster_result_new_allele": (_P(_u8), [_vp]),
+    "ltr_cluster_result_counted": (_P(_u8), [_vp]),
+    "ltr_cluster_result_members": (_P(_i32), [_vp, _i32, _vp]),
+    "ltr_cluster_result_free": (None, [_vp]),
+    "ltr_build_haplotypes_clustered": (_int, [_vp, _P(HapBuildLocus), _i64, _i32, _P(_vp)]),
+    "ltr_hap_result_inexact": (_P(_u8), [_vp]),
+    "ltr_hap_result_cluster_threshold": (_i32, [_vp, _i32]),
+    "ltr_poa_consensus": (_int, [_vp, _P(SeqGroups), _vp, _i64, _vp, _vp]),
+    "ltr_poa_consensus_capacity": (_i64, [_P(SeqGroups)]),
+    "ltr_build_haplotypes_consensus": (_int, [_vp, _P(HapBuildLocus), _i64, _i32, _P(_vp)]),
+    "ltr_hap_result_consensus_rounds": (_i32, [_vp, _i32]),
+    "ltr_hap_result_medoid_kept": (_i32, [_vp, _i32]),
+}
+
+# The test hooks the library exports without declaring them in the public header (csrc/ltr_plan.h, csrc/ltr_internal.h).
+HOOK_SIGNATURES = {
+    "ltr_debug_describe_batch": (_int, [_P(AlignParams), _int, _int, _P(LocusBatch), _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _str, _int]),
+    "ltr_debug_threshold_groups": (_int, [_vp, _int, _int, _vp, _vp, _vp]),
+    "ltr_debug_plan_schedule": (_int, [_P(AlignParams), _int, _int, _P(LocusBatch), _vp, _vp, _vp, _vp, _int, _vp, _vp, _int, _vp, _int, _vp]),
+    "ltr_debug_plan_families": (_int, [_P(AlignParams), _int, _int, _P(LocusBatch), _vp, _vp, _int, _vp, _vp, _int, _vp, _vp]),
+    "ltr_debug_plan_family_forks": (_int, [_P(AlignParams), _int, _int, _P(LocusBatch), _vp, _vp, _int, _vp, _vp, _int, _vp, _vp, _vp]),
+    "ltr_debug_chunk_plan": (_int, [_i64, _f64, _vp, _int, _vp, _int, _vp]),
+}
+
+
+def bind(L):
+    """Give every function of the loaded library its signature: the one walk over the tables."""
+    for table in (SIGNATURES, HOOK_SIGNATURES):
+        for name, (ret, params) in table.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = ret, params

@@ -119,7 +119,6 @@ def pair_time_cost(n, C, pairs_in_batch=1 << 21, n_cu=256, params=None):
     out = np.zeros(win.size, dtype=np.float64)
     prm = params if params is not None else _abi.default_params()
     L = _lib.lib()
-    L.ltr_debug_pair_costs.argtypes = [C_.c_void_p, C_.c_int, C_.c_int, C_.c_int64, C_.c_int64, C_.c_int64, C_.c_void_p, C_.c_void_p, C_.c_void_p, C_.c_void_p]
     n_long = int((rl > 1281).sum() * max(pairs_in_batch // max(win.size, 1), 1)) if win.size else 0
     rc = L.ltr_debug_pair_costs(C_.byref(prm), -1, int(n_cu), int(pairs_in_batch), n_long, win.size, win.ctypes.data, rl.ctypes.data, hl.ctypes.data, out.ctypes.data)
     if rc != 0:

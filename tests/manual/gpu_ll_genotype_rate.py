@@ -71,7 +71,6 @@ def main():
     ctx = _lib.Context(0)
     ctx.set_host_threads(16)
     lib = _lib.lib()
-    _lib._bind_genotype(lib)
     batch, args = gt.pack(cases)
     plan = ctx.plan(batch)
     plan.execute()
@@ -95,8 +94,6 @@ def main():
     off, rpos = np.zeros(n + 1, dtype=np.int64), np.zeros(n, dtype=np.int32)
     sub = min(a.sub, n)
     buf, pos = C.create_string_buffer(1 << 20), C.c_int32(0)
-    lib.ltr_vcf_record.restype = C.c_int64
-    lib.ltr_vcf_record.argtypes = [C.POINTER(_abi.VcfLocus), C.POINTER(_abi.VcfOptions), C.c_char_p, C.c_int64, C.POINTER(C.c_int32)]
 
     def records(res, t0):
         t1 = time.perf_counter()

@@ -114,9 +114,6 @@ def main():
     del final
     arr = (_abi.VcfLocus * n)(*[p.struct for p in pv_new])
     buf, pos = C.create_string_buffer(1 << 20), C.c_int32(0)
-    lib.ltr_vcf_record.restype = C.c_int64
-    lib.ltr_vcf_record.argtypes = [C.POINTER(_abi.VcfLocus), C.POINTER(_abi.VcfOptions), C.c_char_p, C.c_int64, C.POINTER(C.c_int32)]
-    _lib._bind_genotype(lib)
     off, rpos = np.zeros(n + 1, dtype=np.int64), np.zeros(n, dtype=np.int32)
 
     def parent():

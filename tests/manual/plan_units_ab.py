@@ -104,12 +104,6 @@ def synth_batches():
 def dump(path, want_fold_literals):
     from longtr_amd import _abi, _lib
     L = _lib.lib()
-    L.ltr_debug_class_info.argtypes = [C.c_int] + [C.POINTER(C.c_int)] * 4
-    L.ltr_debug_classify.argtypes = [C.POINTER(_abi.AlignParams), C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int,
-                                     C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.ltr_debug_sort_by_class.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    L.ltr_debug_pair_costs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 4
-    L.ltr_debug_threshold_table.argtypes = [C.c_float, C.c_void_p, C.c_int64]
     NK = L.ltr_debug_num_classes()
     res = {}
 

@@ -69,8 +69,6 @@ def test_library_table_is_that_construction(c32):
     import ctypes as C
     from longtr_amd import _lib
     L = _lib.lib()
-    L.ltr_debug_threshold_table.argtypes = [C.c_float, C.c_void_p, C.c_int64]
-    L.ltr_debug_threshold_table.restype = C.c_int
     out = np.zeros(4096, dtype=np.float64)
     n = L.ltr_debug_threshold_table(C.c_float(c32), out.ctypes.data, out.size)
     assert n > 0 and n % 2 == 0

@@ -266,7 +266,6 @@ def test_errors_launch_nothing_and_name_the_locus(gpu_ctx):
         msg = L.ltr_last_error(gpu_ctx._h).decode()
         assert rc == _abi.LTR_ERR_INVALID and not h.value and text in msg, (rc, h.value, msg)
 
-    _lib._bind_genotype(L)
     wrong = list(case["blocks"])                                 # n_haps[5] no longer what haps[5] enumerates
     wrong[5] = [dict(b, alleles=list(b["alleles"])) for b in wrong[5]]
     wrong[5][1]["alleles"].append(wrong[5][1]["alleles"][0] + b"ACG")

@@ -280,7 +280,6 @@ def test_null_and_constant_arrays_are_the_old_entry_points(gpu_ctx):
     all-ones array (with pb->haploid set to the opposite: it is not read)."""
     case = _case(gpu_ctx)
     L = _lib.lib()
-    _lib._bind_genotype(L)
     plan, n = case["plan"], len(case["loci"])
     fr = _abi.FieldsRequest()
     fr.want_gls = fr.want_pls = fr.want_phased_gls = fr.want_posteriors = 1
@@ -324,7 +323,6 @@ def test_errors_are_the_old_ones_and_launch_nothing(gpu_ctx):
     """6. a bad batch with locus_haploid given fails exactly as without it: LTR_ERR_INVALID, the same text, *out left NULL."""
     case = _case(gpu_ctx)
     L = _lib.lib()
-    _lib._bind_genotype(L)
     plan, pattern = case["plan"], case["pattern"]
     plh = pattern.ctypes.data_as(C.c_void_p)
     fr = _abi.FieldsRequest()

@@ -44,7 +44,6 @@ def test_struct_layout_matches_the_header(tmp_path):
 
 def test_null_arguments_are_refused_without_a_device():
     L = _lib.lib()
-    _lib._bind_genotype(L)
     lb, gb, pb = _abi.LlBatch(), _abi.GenotypeBatch(), _abi.PosteriorBatch()
     gb.pb = C.pointer(pb)
     fake = C.c_void_p(0x1000)                                    # never dereferenced: the NULL argument is found first

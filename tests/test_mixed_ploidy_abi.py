@@ -15,7 +15,6 @@ NEW = ("ltr_plan_posteriors_ploidy", "ltr_plan_genotype_ploidy", "ltr_ll_genotyp
 
 def test_new_symbols_are_exported_declared_and_bound():
     L = _lib.lib()
-    _lib._bind_genotype(L)
     hdr = open(os.path.join(ROOT, "include", "ltr_gpu.h")).read()
     for name in NEW:
         assert hasattr(L, name) and name in _lib.EXPORTS and name + "(" in hdr, name
@@ -36,7 +35,6 @@ def test_abi_version_and_struct_sizes_are_the_parents():
 
 def test_null_arguments_are_refused_without_a_device():
     L = _lib.lib()
-    _lib._bind_genotype(L)
     lb, gb, pb = _abi.LlBatch(), _abi.GenotypeBatch(), _abi.PosteriorBatch()
     gb.pb = C.pointer(pb)
     lh = np.ones(4, dtype=np.uint8)

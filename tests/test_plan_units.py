@@ -9,10 +9,6 @@ import pytest
 from longtr_amd import _abi, _lib
 
 L = _lib.lib()
-L.ltr_debug_class_info.argtypes = [C.c_int] + [C.POINTER(C.c_int)] * 4
-L.ltr_debug_classify.argtypes = [C.POINTER(_abi.AlignParams), C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int,
-                                 C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-L.ltr_debug_sort_by_class.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
 NK = L.ltr_debug_num_classes()
 N_CU = 256
 
@@ -314,7 +310,6 @@ def test_shard_costs_are_the_plans_own_model():
                 _, key, _ = classify(n, Cc + 1, pairs=pairs, long_pairs=long_pairs)
                 win, rl = np.asarray([n], dtype=np.int32), np.asarray([Cc + 1], dtype=np.int32)
                 hl, out = win + 60, np.zeros(1)
-                L.ltr_debug_pair_costs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 4
                 p = _abi.default_params()
                 assert L.ltr_debug_pair_costs(C.byref(p), -1, N_CU, pairs, long_pairs, 1, win.ctypes.data, rl.ctypes.data, hl.ctypes.data, out.ctypes.data) == 0
                 c = float(out[0])

@@ -27,7 +27,6 @@ def test_symbols_and_documented_signatures():
                  "int32_t ltr_hap_result_medoid_kept(const ltr_hap_result* r, int32_t sample);"):
         assert decl in HEADER, decl
     assert "#define LTR_ABI_VERSION 6" in HEADER                   # no existing struct changed
-    L.ltr_abi_version.restype = C.c_int
     assert L.ltr_abi_version() == 6
 
 
@@ -54,7 +53,6 @@ def test_without_a_context_is_an_error_not_a_fallback():
 
 def test_capacity_and_malformed_groups():
     L = _lib.lib()
-    L.ltr_poa_consensus_capacity.argtypes, L.ltr_poa_consensus_capacity.restype = [C.POINTER(_abi.SeqGroups)], C.c_int64
     groups = [[b"ACGT", b"", b"AGGTT"], [], [b"AC"]]
     pk = _lib.pack_seq_groups(groups)
     assert L.ltr_poa_consensus_capacity(C.byref(pk["sg"])) == 11    # the bytes of all groups
@@ -78,7 +76,6 @@ def test_capacity_and_malformed_groups():
 
 def test_build_haplotypes_consensus_without_a_context():
     L = _lib.lib()
-    L.ltr_build_haplotypes_consensus.argtypes = [C.c_void_p, C.POINTER(_abi.HapBuildLocus), C.c_int64, C.c_int32, C.POINTER(C.c_void_p)]
     arr = (_abi.HapBuildLocus * 2)()
     out = (C.c_void_p * 2)(1, 1)
     assert L.ltr_build_haplotypes_consensus(None, arr, 2, 5, out) == _abi.LTR_ERR_NO_DEVICE
@@ -86,5 +83,4 @@ def test_build_haplotypes_consensus_without_a_context():
     assert L.ltr_build_haplotypes_consensus(None, arr, -1, 5, out) == _abi.LTR_ERR_INVALID
     assert L.ltr_build_haplotypes_consensus(None, arr, 2, -1, out) == _abi.LTR_ERR_INVALID
     assert L.ltr_build_haplotypes_consensus(None, arr, 2, 5, None) == _abi.LTR_ERR_INVALID
-    L.ltr_hap_result_consensus_rounds.argtypes = L.ltr_hap_result_medoid_kept.argtypes = [C.c_void_p, C.c_int32]
     assert L.ltr_hap_result_consensus_rounds(None, 0) == 0 and L.ltr_hap_result_medoid_kept(None, 0) == 0

@@ -1,5 +1,5 @@
 """The committed counter summary belongs to the library in the tree: bench.py attaches `roofline.traffic` / `valu_issue_frac` to its line
-only when `profiles/<round>/pmc_traffic.json` names the `source_id` of the sources that are built (longtr_amd/_lib.py::source_id: flags +
+only when `profiles/<round>/pmc_traffic.json` names the `source_id` of the sources that are built (longtr_amd/_build.py::source_id: flags +
 every file of longtr_amd/csrc + include/ltr_gpu.h).  Mid-round, after a kernel change and before the profiles are collected again, the
 ids differ: that is reported as a skip, not a failure -- the round's last commit is expected to make this test pass."""
 import glob
