@@ -314,6 +314,9 @@ int  ltr_ctx_set_pair_packing(ltr_ctx* ctx, int mode);
  *                    threshold kernels; rule: what the context has learnt, see ltr_ctx_wg_first_pass
  *   "poa_group_cap_bytes", "poa_call_budget_bytes"   ltr_poa_consensus: its memory rule, lowered (see there; the cap decides which
  *                    groups are aligned, so this one switch does change results)
+ *   "grid_cap"       n > 0: every DP launch of ltr_plan_execute (of plans created from now on) and every class launch of
+ *                    ltr_haplotype_align_to_ref on at most n workgroups, and whatever is sized by a grid with it -- the tests'
+ *                    way to many items per persistent wavefront on a device of any size (tests/test_gpu_grid_cap.py)
  *   "reset"          every switch back to the library's rule */
 int  ltr_ctx_set_debug(ltr_ctx* ctx, const char* key, double value);
 /* Which kernels score the workgroup-per-pair classes (reads beyond 1281 bases, symmetric models) FIRST in the next

@@ -44,17 +44,19 @@ LAUNCH_KINDS = ("one-wave", "packed", "multi", "packed-multi", "plan", "workgrou
 
 
 def debug_plan_schedule(batch, grids, params=None, mode=-1, n_cu=256, plan_kernel=0, no_multi=0, chain=0, chain_min_w=0, chain_max_w=0,
-                        plan_share=0, cap=0):
+                        plan_share=0, cap=0, grid_cap=0):
     """Test hook ltr_debug_plan_schedule (csrc/ltr_plan.h): describe_batch, class statistics and ltrp::build_schedule on a
     _abi.PackedBatch, no GPU.  grids: made-up occupancy grids, one per class (certificate, then exact), then of the multi-width
     one-wave launch, the multi-width packed launch and the plan kernel.  dict(launches, by_class: lists of dict(kind, cls, W,
     grid, small, cmax, pairs, cells, members); entries: list of dict(kind, W, first, pairs, queue_class, first_wave); n_tabs,
-    use_plan, max_grid, max_grid_wide, max_len, xcand, class_first, x_grid)."""
+    use_plan, max_grid, max_grid_wide, max_len, xcand, class_first, x_grid).  cap: Schedule::cap_grids (the scratch strips' cap);
+    grid_cap: the ltr_ctx_set_debug switch of that name (Schedule::cap_every_grid); one of the two at a time."""
     L = lib()
     nk = L.ltr_debug_num_classes()
     g = np.ascontiguousarray(grids, dtype=np.int32)
     assert g.size == nk + 3
-    knobs = np.asarray([plan_kernel, no_multi, chain, chain_min_w, chain_max_w, plan_share, cap], dtype=np.int32)
+    assert cap >= 0 and grid_cap >= 0 and not (cap and grid_cap)      # (one knob: the sign picks the cap)
+    knobs = np.asarray([plan_kernel, no_multi, chain, chain_min_w, chain_max_w, plan_share, -grid_cap if grid_cap else cap], dtype=np.int32)
     prm = params or _abi.default_params()
     n_exact = nk - sum(1 for k in range(nk) if L.ltr_kernel_family(k) != 3)
     out, x_grid = np.zeros(8 + n_exact + nk + 1, dtype=np.int64), np.zeros(n_exact, dtype=np.int32)
@@ -124,6 +126,27 @@ def debug_plan_family_forks(batch, params=None, mode=-1, n_cu=256, families=0, f
         at += d["count"]
         rows.append(d)
     return dict(families=rows, members=int(out[1]), with_spine=int(out[2]), steps_saved=int(out[3]), park_slots=n_slots)
+
+
+# ltrp::LaunchKind, then the kinds of the launches formed at execute time (csrc/ltr_plan.h, kNote*)
+LAUNCH_NOTE_KINDS = LAUNCH_KINDS + ("threshold", "exact", "exact-wide", "exact-narrow8", "nw-wave", "nw-workgroup")
+
+
+def debug_last_launches(plan=None, ctx=None):
+    """Test hook ltr_debug_last_launches (csrc/ltr_plan.h): every kernel launch of the last execute of a Plan, or (plan None) of the
+    last haplotype_align_to_ref of a Context, as it was made.  List of dict(kind: one of LAUNCH_NOTE_KINDS, cls, grid, takers: per
+    workgroup, wavefronts (or the workgroup itself) that take items independently, items: what the launch was given, -1 where only
+    the device knows)."""
+    L = lib()
+    hp, hc = (plan._h if plan is not None else None), (ctx._h if ctx is not None else None)
+    out = np.zeros((64, 5), dtype=np.int64)
+    n = L.ltr_debug_last_launches(hp, hc, out.shape[0], _p(out))
+    if n > out.shape[0]:
+        out = np.zeros((n, 5), dtype=np.int64)
+        n = L.ltr_debug_last_launches(hp, hc, out.shape[0], _p(out))
+    if n < 0:
+        raise LtrError(n, "ltr_debug_last_launches")
+    return [dict(kind=LAUNCH_NOTE_KINDS[int(r[0])], cls=int(r[1]), grid=int(r[2]), takers=int(r[3]), items=int(r[4])) for r in out[:n]]
 
 
 def debug_chunk_plan(n_loci, est_cells=0.0, budget=0, chunks=0, chunk_streams=0, chunk_growth=None, prep_ahead=0):

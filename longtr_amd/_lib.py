@@ -18,8 +18,8 @@ This module is the facade: every name is defined in one of the modules below, by
 from ._abi import BamRecord, SIGNATURES
 from ._build import CSRC, HERE, HIPCC_FLAGS, KERNEL_TUS, LIB_PATH, LINK_LIBS, OBJ_DIR, PLAN_UNITS, SOURCES, build, source_id
 from ._context import Context
-from ._debug import (LAUNCH_KINDS, debug_chunk_plan, debug_describe_batch, debug_plan_families, debug_plan_family_forks, debug_plan_schedule,
-                     debug_threshold_groups)
+from ._debug import (LAUNCH_KINDS, LAUNCH_NOTE_KINDS, debug_chunk_plan, debug_describe_batch, debug_last_launches, debug_plan_families,
+                     debug_plan_family_forks, debug_plan_schedule, debug_threshold_groups)
 from ._formats import Bam, Fasta, VcfPanel, VcfWriter, read_regions, tbi_parse, vcf_header, vcf_index
 from ._genotype import FAMILIES, GenotypeResult, Plan, _locus_haploid, get_alleles, vcf_fields, vcf_record, vcf_record_from_fields
 from ._haplotypes import ReadSet, _hap_result, cluster_sequences, edit_distances, pack_seq_groups, poa_consensus

@@ -87,6 +87,7 @@ struct ltr_ctx {
   std::mutex call_mu;                   // one ltr_calc_hap_aln_probs / NW call at a time per context: they stage in host_bytes / d_big (ctx_call_lock)
   std::mutex err_mu;                    // error text and timers are written from worker threads too
   ltr_timers tm = {};
+  std::vector<ltrp::LaunchNote> nw_log;   // the class launches of the last ltr_haplotype_align_to_ref as made (under err_mu; ltr_debug_last_launches)
   double short_split_ms[4] = {0, 0, 0, 0};   // ltr_ctx_set_debug "short_split": [prep + flank rows before the block, block row, flank rows after, seed log-sum]
 };
 
@@ -149,6 +150,8 @@ struct ltr_plan : ltrp::BatchPlan {     // (what ltrp::describe_batch decided: s
   int64_t redo_cap = 1;
   uint32_t seed_total = 0;
   int last_launches = 0;
+  int grid_cap = 0;                     // ltr_ctx_set_debug "grid_cap" as it stood when the plan was built (0: none): the grids formed at execute time follow it
+  std::vector<ltrp::LaunchNote> launch_log;   // the kernel launches of the last execute as made (ltr_debug_last_launches)
   bool executed = false;
   bool kernel_ms_counted = true;
 };

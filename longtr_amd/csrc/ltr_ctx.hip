@@ -45,6 +45,10 @@ void add_time(ltr_ctx* ctx, int which, double seconds, double kernel_ms) {
 void ctx_note_short_split(ltr_ctx* ctx, const double ms4[4]) { std::lock_guard<std::mutex> lk(ctx->err_mu); for (int k = 0; k < 4; ++k) ctx->short_split_ms[k] += ms4[k]; }
 ltr_align_params ctx_params(const ltr_ctx* ctx) { return ctx->params; }
 DebugKnobs ctx_debug(const ltr_ctx* ctx) { return ctx->dbg; }
+void ctx_note_nw_launch(ltr_ctx* ctx, int kind, int cls, int grid, int takers, int64_t items) {
+  std::lock_guard<std::mutex> lk(ctx->err_mu);
+  if (kind < 0) ctx->nw_log.clear(); else ctx->nw_log.push_back({kind, cls, grid, takers, items});
+}
 ltr_stutter_params ctx_stutter_params(const ltr_ctx* ctx) { return ctx->stutter; }
 int ctx_device(const ltr_ctx* ctx) { return ctx->device; }
 void* ctx_stream(const ltr_ctx* ctx) { return (void*)ctx->stream; }
@@ -223,6 +227,7 @@ int ltr_ctx_set_debug(ltr_ctx* ctx, const char* key, double value) {
   else if (k == "chain_min_w") ctx->dbg.chain_min_w = (int)value;
   else if (k == "chain_max_w") ctx->dbg.chain_max_w = (int)value;
   else if (k == "wave_clock") ctx->dbg.wave_clock = (int)value;
+  else if (k == "grid_cap") ctx->dbg.grid_cap = value > 0.0 ? (int)std::min(value, 1048576.0) : 0;
   else if (k == "poa_group_cap_bytes") ctx->dbg.poa_group_cap_bytes = (int64_t)value;
   else if (k == "poa_call_budget_bytes") ctx->dbg.poa_call_budget_bytes = (int64_t)value;
   else if (k == "pageable_staging" || k == "reset") {            // A/B: 1 = the library's own staging arrays in pageable memory again ("reset": pinned, the default)

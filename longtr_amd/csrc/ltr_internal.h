@@ -257,10 +257,13 @@ struct DebugKnobs {
   int families = 0;             // haplotype families (ltr_dp_family.hpp): -1 = never, 0 = by rule (where modelled cheaper), 1 = whenever one can be formed from reads of 641 .. 1280 columns, 2 = ... of 321 .. 1280
   int family_min_rows = 0;      // ... fewest shared rows (0: ltrp::kFamMinRows)
   int family_spine = 0;         // ... run along a spine (ltr_dp_family.hpp, spine_walk): -1 = never (plain families), 0 = by rule (plans of ltrp::kSpinePerCu families per CU and more), 1 = in any plan
+  int grid_cap = 0;             // tests: n > 0 = every DP launch of ltr_plan_execute and every class launch of ltr_haplotype_align_to_ref on at most n workgroups (many items per wavefront on any device); read when a plan is built
   int64_t poa_group_cap_bytes = 0;    // ltr_poa_consensus: scratch of one group at most (rule: 512 MB); a group over it is not aligned (status 1) -- the one switch results depend on
   int64_t poa_call_budget_bytes = 0;  // ... scratch of one launch set at most (rule: 16 GB)
 };
 DebugKnobs ctx_debug(const ltr_ctx* ctx);
+// the class launches of an ltr_haplotype_align_to_ref call as made, for ltr_debug_last_launches (ltr_plan.h: LaunchNote); kind < 0 begins a call
+void ctx_note_nw_launch(ltr_ctx* ctx, int kind, int cls, int grid, int takers, int64_t items);
 
 void set_error(ltr_ctx* ctx, const std::string& msg);
 ltr_align_params ctx_params(const ltr_ctx* ctx);

@@ -445,7 +445,7 @@ int nw_tasks(ltr_ctx* ctx, const ltr_haplotype_blocks* const* haps, int64_t n_lo
 // wavefront and a class of a 3000-locus call a handful of pairs per resident wavefront, so a launch on its own ends in a tail as
 // long as a pair with most of the GPU idle (rocprofv3, round 3: VALU issue 0.35 - 0.65 per launch).  Measured on MI355X, 21 k
 // haplotypes of 3000 config-3 loci, kernels first to last: one stream, task order 14.0 ms; profiles/r05/nw_rate.log.
-void nw_classes(NwCall& c, int n_cu) {
+void nw_classes(NwCall& c, int n_cu, int grid_cap) {
   const std::vector<NwTask>& tasks = c.tasks;
   for (int64_t k = 0; k < (int64_t)tasks.size(); ++k) {
     const int w = (tasks[(size_t)k].L1 + 63) / 64;
@@ -482,11 +482,13 @@ void nw_classes(NwCall& c, int n_cu) {
         int64_t waves = std::min<int64_t>((int64_t)c.cls_tasks[cl].size(), (int64_t)n_cu * 12);
         waves = std::max<int64_t>(1, std::min<int64_t>((int64_t)((double)waves * shrink), ((int64_t)6 << 30) / c.cls_stride[cl]));
         c.cls_grid[cl] = (waves + kNwWaveBlock - 1) / kNwWaveBlock;
+        if (grid_cap > 0) c.cls_grid[cl] = std::min<int64_t>(c.cls_grid[cl], grid_cap);      // (ltr_ctx_set_debug "grid_cap": tests; the regions below follow)
         c.trace_bytes += c.cls_grid[cl] * kNwWaveBlock * c.cls_stride[cl];
       } else {
         c.cls_stride[cl] = (((int64_t)(c.wg_max_l1 + 1) * (c.wg_max_l2 + 1)) + 255) / 256 * 256;   // per workgroup
         int64_t g = std::min<int64_t>((int64_t)c.cls_tasks[cl].size(), (int64_t)n_cu * 2);    // LDS (54 KB) admits two workgroups per CU
         c.cls_grid[cl] = std::max<int64_t>(1, std::min<int64_t>((int64_t)std::max(1.0, (double)g * shrink), ((int64_t)6 << 30) / c.cls_stride[cl]));
+        if (grid_cap > 0) c.cls_grid[cl] = std::min<int64_t>(c.cls_grid[cl], grid_cap);
         c.trace_bytes += c.cls_grid[cl] * c.cls_stride[cl];
       }
     }
@@ -522,6 +524,7 @@ int nw_device(ltr_ctx* ctx, NwCall& c, int n_cu) {
   DEV_TRY(ctx, hipMemsetAsync(d_queue, 0, kClasses * sizeof(uint32_t), st));
   DEV_TRY(ctx, lease.event(&c.ev0, true)); DEV_TRY(ctx, lease.event(&c.ev1, true));
   DEV_TRY(ctx, hipEventRecord(c.ev0, st));
+  ltr::ctx_note_nw_launch(ctx, -1, 0, 0, 0, 0);
   for (int q = 0; q < kClasses; ++q) {
     const int cl = (q < kClasses - 1) ? kClasses - 2 - q : kClasses - 1;      // strip widths 20, 16, .., 4, then the workgroup kernel
     const int n_c = (int)c.cls_tasks[cl].size();
@@ -542,6 +545,7 @@ int nw_device(ltr_ctx* ctx, NwCall& c, int n_cu) {
         hipLaunchKernelGGL(ltr_nw_kernel, g, dim3(kNwThreads), 0, sc, d_tasks, idx, n_c, d_queue + cl, d_seqs, tr, c.cls_stride[cl],
                            d_diag, diag_stride, c.d_out, c.d_len);
     }
+    ltr::ctx_note_nw_launch(ctx, cl < kClasses - 1 ? 11 : 12, cl, (int)c.cls_grid[cl], cl < kClasses - 1 ? kNwWaveBlock : 1, n_c);   // (ltr_plan.h: kNoteNwWave, kNoteNwWg)
     DEV_TRY(ctx, hipGetLastError());
     if (sc != st) {
       hipEvent_t ev_join = nullptr;
@@ -653,7 +657,7 @@ int ltr_haplotype_align_to_ref(ltr_ctx* ctx, const ltr_haplotype_blocks* const* 
   int n_cu = 0;
   (void)ltr_ctx_device_info(ctx, nullptr, 0, &n_cu, nullptr);
   n_cu = std::max(n_cu, 1);
-  nw_classes(c, n_cu);
+  nw_classes(c, n_cu, ltr::ctx_debug(ctx).grid_cap);
   rc = nw_device(ctx, c, n_cu);
   if (rc == LTR_OK) rc = nw_download(ctx, c);
   if (rc == LTR_OK) rc = nw_strings(ctx, c, aln_info, cap, info_off);

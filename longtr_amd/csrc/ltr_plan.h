@@ -351,7 +351,17 @@ struct __attribute__((visibility("hidden"))) Schedule {
   int ranges(const Launch& L, const int* bin_first, int32_t* lanes_per_pair, int32_t* strip_width, int64_t* n_pairs) const;
   // scratch strips are finite: no launch that uses them (one-wave bodies) gets more than cap workgroups
   void cap_grids(int cap);
+  // ltr_ctx_set_debug "grid_cap" (tests): NO launch gets more than cap workgroups -- the packed and workgroup launches, the
+  // four- and eight-wave exact lists and the W = 20 exact launch too; every kernel is persistent, so only the items a wavefront
+  // takes one after the other change
+  void cap_every_grid(int cap);
 };
+// One kernel launch as it was made (ltr_debug_last_launches): kind = LaunchKind of a first-pass launch, or one of the kinds below;
+// cls = launch class (exact list; class of ltr_haplotype_align_to_ref); takers = wavefronts (one-wave bodies) or workgroups
+// (workgroup kernels: 1) per workgroup that take items independently of each other; items = pairs / families / tasks the launch
+// was given, -1 where only the device knows (the exact lists)
+enum { kNoteThreshold = 7, kNoteExact = 8, kNoteExactWide = 9, kNoteExactNarrow8 = 10, kNoteNwWave = 11, kNoteNwWg = 12 };
+struct LaunchNote { int32_t kind, cls, grid, takers; int64_t items; };
 // The schedule of a described batch.  Pure: class ranges and statistics, occupancy grids and A/B knobs (chain*, plan_share) in.
 // Settles in *d what depends on it: without anything for the plan kernel to score use_plan falls back and the exact launches
 // take the list starters (xcand); with it the plan kernel scores them itself (x_seed = 0).
@@ -384,7 +394,8 @@ void build_threshold_table(float c, double* out);
 // ltr_debug_threshold_groups: ltrp::threshold_groups; nw / w / np hold ltr_debug_num_classes() entries each.
 // ltr_debug_plan_schedule: describe_batch, class_stats and build_schedule.  grids[ltr_debug_num_classes() + 3]: the occupancy grid of
 // every certificate class, of the exact kernels, then of the multi-width one-wave launch, the multi-width packed launch and the plan
-// kernel.  knobs[7] = plan_kernel, no_multi, chain, chain_min_w, chain_max_w, plan_share, grid cap (0: none).  Per launch 8 words
+// kernel.  knobs[7] = plan_kernel, no_multi, chain, chain_min_w, chain_max_w, plan_share, grid cap (0: none; n > 0: the strips' cap,
+// Schedule::cap_grids; -n: ltr_ctx_set_debug "grid_cap" = n, Schedule::cap_every_grid).  Per launch 8 words
 // in launch[launch_cap][8] = kind, class, strip width, grid, small, cmax, pairs, members and its cells in launch_cells[]; the
 // members of all launches one after the other in members[member_cap]; per entry 6 words in entry[entry_cap][6] = kind, strip
 // width, first pair, pairs, queue class, first_wave.  out[8 + kNumExact] = launches, level-2 launches (listed behind the first),
@@ -411,6 +422,12 @@ int ltr_debug_plan_families(const ltr_align_params* p, int mode, int n_cu, const
 // fork row in member_fork[member_cap] (the spine member's: its n; plain: p), its slot in member_slot[] and its LL index in member_out[].
 int ltr_debug_plan_family_forks(const ltr_align_params* p, int mode, int n_cu, const ltr_locus_batch* b, const int32_t* knobs, int64_t* out,
                                 int fam_cap, int32_t* fam, int32_t* slot_row, int member_cap, int32_t* member_fork, int32_t* member_slot, int64_t* member_out);
+// ltr_debug_last_launches (ltr_plan_run.hip; needs a device): the kernel launches of the last ltr_plan_execute of `plan`, or (plan
+// NULL) of the last ltr_haplotype_align_to_ref of `ctx`, in the order made and as made -- recorded at the launch, the grids formed at
+// execute time included.  Per launch 5 words in out[cap][5] = kind (ltrp::LaunchKind, kNote*), class, grid, takers per workgroup,
+// items (-1: on the device); returns the number of launches (which may exceed cap) or LTR_ERR_INVALID.
+struct ltr_plan; struct ltr_ctx;
+int ltr_debug_last_launches(const ltr_plan* plan, ltr_ctx* ctx, int cap, int64_t* out);
 }
 
 #endif

@@ -356,6 +356,8 @@ int PlanBuild::size_scratch_and_fan() {
     plan->fan_lanes = (ctx->pair_packing < 0 && (plan->n_pairs >= (int64_t)16 * ctx->n_cu || plan->uses_wg) && plan->n_pairs < fan_below) ? fan_n : 1;
     const int cap = (int)std::max<size_t>(16, ((size_t)8 << 30) / (per_wave * kBlockWaves * ((size_t)plan->fan_lanes + 1)));
     plan->sched.cap_grids(cap);
+    plan->grid_cap = std::max(ctx->dbg.grid_cap, 0);
+    if (plan->grid_cap > 0) plan->sched.cap_every_grid(plan->grid_cap);      // (tests; before anything below is sized by a grid)
     plan->scratch_lane_stride = (size_t)plan->sched.max_grid * kBlockWaves * 6 * (size_t)plan->scratch_stride;
     PLAN_TRY(ctx->pool.alloc((void**)&plan->d_scratch, plan->scratch_lane_stride * sizeof(double) * ((size_t)plan->fan_lanes + 1)));   // (+ 1: the kXLong exact launch, see ltr_plan_execute)
     // the family launch: its list, a parking block per wavefront of ITS grid (as capped above), its counters

@@ -135,6 +135,7 @@ int ltr_debug_plan_schedule(const ltr_align_params* p, int mode, int n_cu, const
     ltrp::Schedule S;
     ltrp::build_schedule(&d, st, occ, dbg, &S);
     if (knobs[6] > 0) S.cap_grids(knobs[6]);
+    else if (knobs[6] < 0) S.cap_every_grid(knobs[6] == INT32_MIN ? INT32_MAX : -knobs[6]);      // (seven knobs, as ever: the sign picks the cap)
     out[0] = (int64_t)S.launches.size(); out[1] = (int64_t)S.by_class.size(); out[2] = (int64_t)S.plan_entries.size(); out[3] = (int64_t)S.pack_tabs.size();
     out[4] = d.use_plan ? 1 : 0; out[5] = S.max_grid; out[6] = S.max_grid_wide; out[7] = d.max_len;
     for (int c = 0; c < kNumExact; ++c) { out[8 + c] = d.xcand[c]; x_grid[c] = S.x_grid[c]; }

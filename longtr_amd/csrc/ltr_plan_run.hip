@@ -70,6 +70,8 @@ struct Execute {
   int reset_control_words();
   int ensure_exact_events();
   hipStream_t exact_stream(int which) const;
+  int capped(int grid) const { return plan->grid_cap > 0 ? std::min(grid, plan->grid_cap) : grid; }   // (the grids formed here, under the plan's "grid_cap")
+  void note(int kind, int cls, int grid, int takers, int64_t items) { plan->launch_log.push_back({kind, cls, grid, takers, items}); }
   int behind_the_lanes(int c, hipStream_t s2, bool small_events);
   int launch_exact_list(int c, bool small_events);
   int launch_class(const Launch& L, int li);
@@ -233,12 +235,14 @@ int Execute::launch_exact_list(int c, bool small_events) {
     hipStream_t ws = exact_stream(kNumExact);
     if (ws != xs && (rc2 = behind_the_lanes(c, ws, small_events)) != LTR_OK) return rc2;
     ltrk::launch_exact(ltrk::kXWideLaunch, sym, dim3((unsigned)gw), ws, B);
+    note(kNoteExactWide, c, gw, kBlockWaves, -1);
     if (ws != st) {
       HIP_TRY(ctx, hipEventRecord(plan->ev_x[kNumExact], ws));
       HIP_TRY(ctx, hipStreamWaitEvent(st == xs ? st : xs, plan->ev_x[kNumExact], 0));     // (joined through the list's own stream / event below)
     }
     X.c_lo = 64 * kXWideW + 1;
     ltrk::launch_exact(c, sym, g, xs, X);
+    note(kNoteExact, c, grid, 1, -1);
   } else if (c == kXWg8) {
     // the list of 3586 .. 10241-base reads, two launches that skip each other's pairs: reads of up to 5121 bases on strips of
     // 10 columns at four waves per SIMD (the threshold bodies fit 128 registers up to there), the longer ones on 12 / 16 / 20
@@ -253,14 +257,17 @@ int Execute::launch_exact_list(int c, bool small_events) {
     // (the narrow launch IS the first-pass threshold kernel of 10-column strips, given the list: one strip width in the function --
     // a kernel of its own with an 8- and a 10-column body spilled inside its step loops, 5.7 GB of scratch writes and 30 ms per
     // config5hifi pass against 21 ms for the same pairs: profiles/r06/pmc_dispatch_config5hifi_*.txt)
-    const int gn = std::max(1, std::min(ctx->full_wgt_grid[1][10], grid * 2));
+    const int gn = capped(std::max(1, std::min(ctx->full_wgt_grid[1][10], grid * 2)));
     ltrk::launch_exact(c, sym, g, xs, X);
+    note(kNoteExact, c, grid, 1, -1);
     ltrk::launch_wgt(8, 10, dim3((unsigned)gn), xs, B);
+    note(kNoteExactNarrow8, c, gn, 1, -1);
   } else {
     // kXLong walks the column blocks of reads beyond the eight-wave workgroups' 10241 bases through scratch strips and
     // may run beside the generic exact kernel (which does the same for non-ACGT pairs): a strip region of its own
     if (c == kXLong) X.scratch = plan->d_scratch + (size_t)plan->fan_lanes * plan->scratch_lane_stride;
     ltrk::launch_exact(c, sym, g, xs, X);
+    note(kNoteExact, c, grid, kBlockWaves, -1);
   }
   HIP_TRY(ctx, hipGetLastError());
   if (xs != st) HIP_TRY(ctx, hipEventRecord(plan->ev_x[c], xs));
@@ -310,10 +317,14 @@ int Execute::launch_class(const Launch& L, int li) {
       if (wg_thr && thr.nw[k] != 0) {
         // (all of them on the plan's own stream, one after the other: two persistent eight-wave launches of different register
         // budgets side by side keep half-empty CUs from each other -- config5hifi, thresholds first: 21 + 12 ms alone, 41 ms side by side)
-        const int gt = std::max(1, std::min(np, ctx->full_wgt_grid[thr.nw[k] == 8 ? 1 : 0][thr.w[k]]));
+        const int gt = capped(std::max(1, std::min(np, ctx->full_wgt_grid[thr.nw[k] == 8 ? 1 : 0][thr.w[k]])));
         ltrk::launch_wgt(thr.nw[k], thr.w[k], dim3((unsigned)gt), lanes[0], A);
+        note(kNoteThreshold, k, gt, 1, np);
       } else ltrk::launch_wg(class_info(k).waves, L.W, grid, ls, A);
   }
+  if (L.kind == kLaunchFamily) note(L.kind, k, L.grid, kBlockWaves, (int64_t)plan->fams.size());
+  else if (L.kind != kLaunchWg) note(L.kind, k, L.grid, kBlockWaves, L.pairs);
+  else if (!(wg_thr && thr.nw[k] != 0)) note(L.kind, k, L.grid, 1, np);
   HIP_TRY(ctx, hipGetLastError());
   LTR_DBG("launched class %d grid %d pairs %d on lane %d", k, L.grid, np, li);
   ++launches;
@@ -340,6 +351,7 @@ void Execute::note_wg_stats() {
 int Execute::run() {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   int rc;
+  plan->launch_log.clear();
   if ((rc = snapshot_tables()) != LTR_OK || (rc = reset_control_words()) != LTR_OK) return rc;
   HIP_TRY(ctx, hipEventRecord(plan->ev0, st));
   // Launch order: the first-pass launches longest reads first (ltrp::build_schedule), then the exact kernels; with per-launch
@@ -588,6 +600,21 @@ int ltr_plan_debug_entries(const ltr_plan* plan, int32_t* kind, int32_t* strip_w
     if (cells) cells[i] = cl;
   }
   return n;
+}
+
+int ltr_debug_last_launches(const ltr_plan* plan, ltr_ctx* ctx, int cap, int64_t* out) {
+  if ((!plan && !ctx) || cap < 0 || (cap > 0 && !out)) return LTR_ERR_INVALID;
+  if (plan && (!plan->ctx || !plan->executed)) return LTR_ERR_INVALID;
+  std::vector<ltrp::LaunchNote> log;
+  try {
+    if (plan) log = plan->launch_log;
+    else { std::lock_guard<std::mutex> lk(ctx->err_mu); log = ctx->nw_log; }
+  } catch (...) { return LTR_ERR_NOMEM; }
+  for (size_t i = 0; i < log.size() && i < (size_t)cap; ++i) {
+    const int64_t v[5] = {log[i].kind, log[i].cls, log[i].grid, log[i].takers, log[i].items};
+    std::memcpy(out + i * 5, v, sizeof(v));
+  }
+  return (int)log.size();
 }
 
 int ltr_plan_debug_wave_clocks(ltr_plan* plan, uint64_t* out, int64_t cap) {

@@ -69,6 +69,13 @@ void Schedule::cap_grids(const int cap) {
   max_grid = std::min(max_grid, cap);
 }
 
+void Schedule::cap_every_grid(const int cap) {
+  for (std::vector<Launch>* list : {&launches, &by_class}) for (Launch& L : *list) L.grid = std::min(L.grid, cap);
+  for (int c = 0; c < kNumExact; ++c) x_grid[c] = std::min(x_grid[c], cap);      // (0 stays 0: not launched)
+  max_grid = std::min(max_grid, cap);
+  max_grid_wide = std::min(max_grid_wide, cap);
+}
+
 namespace {
 
 // grid and "small" flag of a persistent launch with work for wgs workgroups where `full` are resident

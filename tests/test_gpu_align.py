@@ -104,9 +104,8 @@ def test_every_read_length_1_to_140(gpu_ctx):
     _check(gpu_ctx, _abi.PackedBatch(cases))
 
 
-def test_certificate_and_exact_redo(gpu_ctx):
-    """Pairs that abort, or come close to the -600 line, must go through the exact kernel and still
-    match the oracle; ordinary pairs must not need it."""
+def hard_pairs():
+    """One-pair loci that abort or come close to the -600 line (test_certificate_and_exact_redo; tests/test_gpu_grid_cap.py)."""
     rng = np.random.default_rng(8)
     rs = lambda n: synth._rand_seq(rng, n).tobytes()
     hard = [([b"A" * 700], [b"C" * 800]), ([rs(400)], [rs(460)]), ([rs(900)], [rs(1000)]),
@@ -120,6 +119,13 @@ def test_certificate_and_exact_redo(gpu_ctx):
         for p in rng.choice(900, size=nmis, replace=False):
             r[p] = ord("A") if r[p] != ord("A") else ord("C")
         hard.append(([bytes(r)], [b"T" * 30 + bytes(base) + b"T" * 30]))
+    return hard
+
+
+def test_certificate_and_exact_redo(gpu_ctx):
+    """Pairs that abort, or come close to the -600 line, must go through the exact kernel and still
+    match the oracle; ordinary pairs must not need it."""
+    hard = hard_pairs()
     b = _abi.PackedBatch(hard)
     ll = _check(gpu_ctx, b)
     assert (ll == -700.0).sum() >= 4
@@ -166,9 +172,9 @@ def test_ont_params_and_flank_lengths(gpu_ctx):
         _check(gpu_ctx, _abi.PackedBatch(cs), _abi.make_params(_abi.default_params().as_tuple()[:7], indel_flank_len=F))
 
 
-def test_non_acgt_bytes_take_the_byte_compare_path(gpu_ctx):
-    # N, lower case and arbitrary bytes: the LUT kernels only see pure ACGT pairs, everything else
-    # must be scored by the byte-compare (exact) kernel with identical results
+def non_acgt_loci():
+    """Four loci with N, lower case and arbitrary bytes in reads and haplotypes (test_non_acgt_bytes_take_the_byte_compare_path;
+    tests/test_gpu_grid_cap.py)."""
     rng = np.random.default_rng(12)
     loci = [synth.synth_locus(rng, int(tr), 4, 3, 4, sub_rate=0.01, indel_rate=0.01) for tr in [30, 120, 300, 700]]
     flat = []
@@ -183,7 +189,13 @@ def test_non_acgt_bytes_take_the_byte_compare_path(gpu_ctx):
             haps[2][50] = 0xC3                       # arbitrary byte, also present in a read
             reads[2][20] = 0xC3
         flat.append(([bytes(r) for r in reads], [bytes(h) for h in haps]))
-    b = _abi.PackedBatch(flat)
+    return flat
+
+
+def test_non_acgt_bytes_take_the_byte_compare_path(gpu_ctx):
+    # N, lower case and arbitrary bytes: the LUT kernels only see pure ACGT pairs, everything else
+    # must be scored by the byte-compare (exact) kernel with identical results
+    b = _abi.PackedBatch(non_acgt_loci())
     _check(gpu_ctx, b)
     plan = gpu_ctx.plan(b)
     plan.execute()

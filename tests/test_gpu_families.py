@@ -92,15 +92,19 @@ def test_every_strip_width_accepts_its_tails(gpu_ctx, cols):
     assert st["stem_failures"] == 0 and st["tail_failures"] == 0 and st["rule_failures"] == 0       # every tail accepted: nothing went to the exact body
 
 
-def test_two_and_twelve_members(gpu_ctx):
-    rng = np.random.default_rng(12)
+def two_and_twelve_loci(rng):
+    """A locus of twelve alleles and one of two (test_two_and_twelve_members; tests/test_gpu_grid_cap.py)."""
     unit = _seq(rng, 6)
     prefix, suffix = _seq(rng, 120), _seq(rng, 200)
     twelve = _alleles(rng, prefix, unit, range(60, 72), suffix)                # windows of 680 .. 746 rows, fork after 60 copies
     two = _alleles(rng, prefix, unit, (64, 66), suffix)
     reads12 = [_mutate(rng, twelve[5], 3), _mutate(rng, twelve[9], 3)]
     reads2 = [_mutate(rng, two[0], 2), _mutate(rng, two[1], 2), _mutate(rng, two[1], 5)]
-    st, formed = _check(gpu_ctx, [(reads12, [_hap(rng, w) for w in twelve]), (reads2, [_hap(rng, w) for w in two])])
+    return [(reads12, [_hap(rng, w) for w in twelve]), (reads2, [_hap(rng, w) for w in two])]
+
+
+def test_two_and_twelve_members(gpu_ctx):
+    st, formed = _check(gpu_ctx, two_and_twelve_loci(np.random.default_rng(12)))
     assert sorted(f["count"] for f in formed["families"]) == [2, 2, 2, 12, 12]
     assert st["stem_failures"] == 0 and st["tail_failures"] == 0 and st["rule_failures"] == 0
 
@@ -144,32 +148,44 @@ def test_length_differences_of_600_next_to_601(gpu_ctx):
     assert st["members"] == 4 and st["stem_failures"] == 0 and st["tail_failures"] == 0 and st["rule_failures"] == 0, st
 
 
-def test_the_acceptance_rule_fails_on_the_device(gpu_ctx):
-    """A read with p / 9 + 4 substitutions at p = 100: its score stays far above -600 but not above U(100) = -108.9 -- the host cannot
-    know, the device's rule sends the member to the exact body."""
-    rng = np.random.default_rng(16)
+def rule_failure_locus(rng):
+    """Read 0 fails the acceptance rule for both members, read 1 is clean (test_the_acceptance_rule_fails_on_the_device)."""
     x = _seq(rng, 700)
     b = x[:100] + _other(x[100]) + x[101:]
     reads = [_mutate(rng, x, 100 // 9 + 4), _mutate(rng, x, 2)]
-    st, formed = _check(gpu_ctx, [(reads, [_hap(rng, x), _hap(rng, b)])])
+    return reads, [_hap(rng, x), _hap(rng, b)]
+
+
+def stem_failure_locus(rng):
+    """Read 0 is random: its family's stem certificate fails; read 1 is clean (test_a_random_read_fails_the_stem_certificate)."""
+    x = _seq(rng, 700)
+    b = x[:300] + _other(x[300]) + x[301:]
+    return [_seq(rng, 701), _mutate(rng, x, 2)], [_hap(rng, x), _hap(rng, b)]
+
+
+def tail_failure_locus(rng):
+    """One read, a clean stem of 300 rows and two random tails (test_random_tails_fail_the_tail_certificate_under_a_clean_stem)."""
+    x = _seq(rng, 700)
+    wins = [x, x[:300] + _other(x[300]) + _seq(rng, 399), x[:300] + (b"G" if x[300] not in b"G" else b"T") + _seq(rng, 420)]
+    return [_mutate(rng, x, 2)], [_hap(rng, w) for w in wins]
+
+
+def test_the_acceptance_rule_fails_on_the_device(gpu_ctx):
+    """A read with p / 9 + 4 substitutions at p = 100: its score stays far above -600 but not above U(100) = -108.9 -- the host cannot
+    know, the device's rule sends the member to the exact body."""
+    st, formed = _check(gpu_ctx, [rule_failure_locus(np.random.default_rng(16))])
     assert [f["p"] for f in formed["families"]] == [100, 100]
     assert st["rule_failures"] == 2 and st["stem_failures"] == 0 and st["tail_failures"] == 0      # both members of the noisy read; the clean read's are accepted
 
 
 def test_a_random_read_fails_the_stem_certificate(gpu_ctx):
-    rng = np.random.default_rng(17)
-    x = _seq(rng, 700)
-    b = x[:300] + _other(x[300]) + x[301:]
-    st, formed = _check(gpu_ctx, [([_seq(rng, 701), _mutate(rng, x, 2)], [_hap(rng, x), _hap(rng, b)])])
+    st, formed = _check(gpu_ctx, [stem_failure_locus(np.random.default_rng(17))])
     assert len(formed["families"]) == 2
     assert st["stem_failures"] == 1 and st["tail_failures"] == 0 and st["rule_failures"] == 0
 
 
 def test_random_tails_fail_the_tail_certificate_under_a_clean_stem(gpu_ctx):
-    rng = np.random.default_rng(18)
-    x = _seq(rng, 700)
-    wins = [x, x[:300] + _other(x[300]) + _seq(rng, 399), x[:300] + (b"G" if x[300] not in b"G" else b"T") + _seq(rng, 420)]
-    st, formed = _check(gpu_ctx, [([_mutate(rng, x, 2)], [_hap(rng, w) for w in wins])])
+    st, formed = _check(gpu_ctx, [tail_failure_locus(np.random.default_rng(18))])
     assert [(f["count"], f["p"]) for f in formed["families"]] == [(3, 300)]
     assert st["stem_failures"] == 0 and st["tail_failures"] == 2 and st["rule_failures"] == 0
 

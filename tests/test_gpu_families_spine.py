@@ -87,7 +87,19 @@ EDGE_COLUMNS = [(321, 6), (384, 6), (385, 7), (448, 7), (449, 8), (512, 8), (513
 
 @pytest.mark.parametrize("cols", [EDGE_COLUMNS[:10], EDGE_COLUMNS[10:20], EDGE_COLUMNS[20:]], ids=["W6-10", "W11-15", "W16-20"])
 def test_every_strip_width_parks_close_and_distant_rows(gpu_ctx, cols):
-    rng = np.random.default_rng(sum(c for c, _ in cols))
+    loci, want = edge_loci(np.random.default_rng(sum(c for c, _ in cols)), cols)
+    st, st_plain, formed = _check(gpu_ctx, loci)
+    assert len(formed["families"]) == len(want) == formed["with_spine"]
+    for f in formed["families"]:
+        assert f["count"] == 4 and f["spine"] == 2 and f["slots"] == 3
+        assert (f["W"], f["p"], (f["slot_rows"][1] - f["p"], f["slot_rows"][2] - f["p"])) in want, f
+    assert sorted(f["W"] for f in formed["families"]) == sorted(w for w, _, _ in want)
+    assert _clean(st) and _clean(st_plain), (st, st_plain)        # every member accepted from the stream or its tail
+
+
+def edge_loci(rng, cols):
+    """Per (read columns, strip width) two one-read loci of four alleles, three park slots each; and per locus (W, p, gaps of the
+    later park rows) (test_every_strip_width_parks_close_and_distant_rows; tests/test_gpu_grid_cap.py)."""
     loci, want = [], []
     for C, W in cols:
         assert W == -(-C // 64)
@@ -102,13 +114,7 @@ def test_every_strip_width_parks_close_and_distant_rows(gpu_ctx, cols):
             assert len(wins[1]) == m
             loci.append(([_mutate(rng, wins[1], 3)], [_hap(rng, w) for w in wins]))
             want.append((W, 80 + unit_len * copies[0], gaps))
-    st, st_plain, formed = _check(gpu_ctx, loci)
-    assert len(formed["families"]) == len(want) == formed["with_spine"]
-    for f in formed["families"]:
-        assert f["count"] == 4 and f["spine"] == 2 and f["slots"] == 3
-        assert (f["W"], f["p"], (f["slot_rows"][1] - f["p"], f["slot_rows"][2] - f["p"])) in want, f
-    assert sorted(f["W"] for f in formed["families"]) == sorted(w for w, _, _ in want)
-    assert _clean(st) and _clean(st_plain), (st, st_plain)        # every member accepted from the stream or its tail
+    return loci, want
 
 
 def _cpu_shapes(rng):
@@ -136,8 +142,8 @@ def _cpu_shapes(rng):
     return shapes
 
 
-def test_the_shapes_of_the_cpu_test(gpu_ctx):
-    rng = np.random.default_rng(31)
+def cpu_shape_loci(rng):
+    """Two reads per shape of _cpu_shapes (test_the_shapes_of_the_cpu_test; tests/test_gpu_grid_cap.py).  (loci, number of shapes)"""
     shapes = _cpu_shapes(rng)
     loci = []
     for wins in shapes.values():
@@ -146,13 +152,39 @@ def test_the_shapes_of_the_cpu_test(gpu_ctx):
         r = w[:701] if len(w) >= 701 else w + _seq(rng, 701 - len(w))
         reads = [_mutate(rng, r, 3), _mutate(rng, r, 5)]
         loci.append((reads, [_hap(rng, w) for w in wins]))
+    return loci, len(shapes)
+
+
+def test_the_shapes_of_the_cpu_test(gpu_ctx):
+    loci, n_shapes = cpu_shape_loci(np.random.default_rng(31))
     st, st_plain, formed = _check(gpu_ctx, loci, families=1)
-    assert len(formed["families"]) == 2 * len(shapes) and formed["with_spine"] == 2 * (len(shapes) - 1)
+    assert len(formed["families"]) == 2 * n_shapes and formed["with_spine"] == 2 * (n_shapes - 1)
     by_count = lambda n: [f for f in formed["families"] if f["count"] == n]
     assert all(f["slots"] == f["park_slots"] and len(set(f["fork"])) == 12 for f in by_count(12))      # more fork rows than slots
     assert any(f["spine"] >= 0 and f["slot_rows"][-1] == max(f["fork"][k] for k in range(f["count"]) if k != f["spine"]) == f["fork"][f["spine"]]
                for f in by_count(3))                              # a member that leaves the spine at the spine's end
     assert _clean(st) and _clean(st_plain), (st, st_plain)
+
+
+def failed_stream_locus(rng):
+    """(locus, p) of test_a_stream_that_fails_between_two_park_rows."""
+    unit = _seq(rng, 9)
+    prefix, suffix = _seq(rng, 499) + _other(unit[-1]), _other(unit[0]) + _seq(rng, 59)
+    wins = _tr(prefix, unit, (20, 23, 70, 68), suffix)
+    p = 500 + 9 * 20
+    read = bytearray(wins[2])
+    read[p + 30:p + 400] = _seq(rng, 370)
+    return ([bytes(read)], [_hap(rng, w) for w in wins]), p
+
+
+def spine_rule_failure_locus(rng):
+    """Read 0 fails the acceptance rule for all four members of a spine family, read 1 is clean
+    (test_the_acceptance_rule_fails_for_a_spine_family)."""
+    unit = _seq(rng, 9)
+    wins = _tr(_seq(rng, 69) + _other(unit[-1]), unit, (4, 6, 9, 8), _other(unit[0]) + _seq(rng, 560))
+    base = wins[2][:701] + _seq(rng, max(0, 701 - len(wins[2])))
+    reads = [_mutate(rng, base, 15), _mutate(rng, base, 2)]
+    return reads, [_hap(rng, w) for w in wins]
 
 
 def test_a_stream_that_fails_between_two_park_rows(gpu_ctx):
@@ -161,14 +193,8 @@ def test_a_stream_that_fails_between_two_park_rows(gpu_ctx):
     more than 600, so the stream's certificate fails some 300 rows into them, below the last park row -- the 68-copy allele's slot
     is never complete and it goes to the exact body with the spine member, two tail failures.  The two short alleles were parked
     below: their tails skip the noise inside the gap their length needs anyway (-460 and -433, above U(680) = -689) and are accepted."""
-    rng = np.random.default_rng(32)
-    unit = _seq(rng, 9)
-    prefix, suffix = _seq(rng, 499) + _other(unit[-1]), _other(unit[0]) + _seq(rng, 59)
-    wins = _tr(prefix, unit, (20, 23, 70, 68), suffix)
-    p = 500 + 9 * 20
-    read = bytearray(wins[2])
-    read[p + 30:p + 400] = _seq(rng, 370)
-    st, st_plain, formed = _check(gpu_ctx, [([bytes(read)], [_hap(rng, w) for w in wins])], families=1)
+    locus, p = failed_stream_locus(np.random.default_rng(32))
+    st, st_plain, formed = _check(gpu_ctx, [locus], families=1)
     (f,) = formed["families"]
     assert (f["p"], f["spine"], f["slot_rows"], f["slot"][:2] + f["slot"][3:]) == (p, 2, [p, p + 27, p + 432], [0, 1, 2])
     assert (st["stem_failures"], st["tail_failures"], st["rule_failures"]) == (0, 2, 0), st
@@ -178,12 +204,7 @@ def test_a_stream_that_fails_between_two_park_rows(gpu_ctx):
 def test_the_acceptance_rule_fails_for_a_spine_family(gpu_ctx):
     """p = 106 and a read with 15 substitutions: every member's score stays far above -600 but not above U(106) = -114.9; the clean
     read's members are accepted."""
-    rng = np.random.default_rng(33)
-    unit = _seq(rng, 9)
-    wins = _tr(_seq(rng, 69) + _other(unit[-1]), unit, (4, 6, 9, 8), _other(unit[0]) + _seq(rng, 560))
-    base = wins[2][:701] + _seq(rng, max(0, 701 - len(wins[2])))
-    reads = [_mutate(rng, base, 15), _mutate(rng, base, 2)]
-    st, st_plain, formed = _check(gpu_ctx, [(reads, [_hap(rng, w) for w in wins])], families=1)
+    st, st_plain, formed = _check(gpu_ctx, [spine_rule_failure_locus(np.random.default_rng(33))], families=1)
     assert [(f["p"], f["spine"], f["count"]) for f in formed["families"]] == [(106, 2, 4)] * 2
     assert (st["stem_failures"], st["tail_failures"], st["rule_failures"]) == (0, 0, 4), st
     assert (st_plain["stem_failures"], st_plain["tail_failures"], st_plain["rule_failures"]) == (0, 0, 4), st_plain

@@ -91,7 +91,9 @@ def test_every_strip_width_of_the_4_and_8_wave_classes(gpu_ctx):
     assert {k["strip_width"] for k in st2 if k["family"] != "exact" and k["lanes_per_pair"] == 256 and k["pairs"]} == set(range(5, 21))
 
 
-def test_long_pairs_abort_uncertain_and_unequal_lengths(gpu_ctx):
+def long_edge_pairs():
+    """(read, haplotype) pairs of the workgroup classes that sit at the -600 line, abort late or at once, differ in length, or are
+    shortcuts (test_long_pairs_abort_uncertain_and_unequal_lengths; tests/test_gpu_grid_cap.py)."""
     rng = np.random.default_rng(32)
     rs = lambda n: synth._rand_seq(rng, n).tobytes()
     pairs = []
@@ -108,6 +110,11 @@ def test_long_pairs_abort_uncertain_and_unequal_lengths(gpu_ctx):
         pairs.append((r, h2))
     pairs.append((rs(1200), rs(62)))             # |n - m| > 600 shortcut in a workgroup class
     pairs.append((rs(1200), rs(60)))             # haplotype <= 60
+    return pairs
+
+
+def test_long_pairs_abort_uncertain_and_unequal_lengths(gpu_ctx):
+    pairs = long_edge_pairs()
     ll = _check_pairs(gpu_ctx, pairs, modes=(-1, 3, 4))
     assert (ll == -700.0).sum() >= 6 and (ll > -600.0).sum() >= 4
     _check_pairs(gpu_ctx, pairs[:8] + pairs[10:], _abi.make_params(synth.ONT_PARAMS))

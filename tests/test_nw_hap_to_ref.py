@@ -48,8 +48,9 @@ def test_restatement_lengths_consistent_on_random_pairs():
             assert _consistent(info, len(haps[0]), len(h))
 
 
-@pytest.mark.gpu
-def test_gpu_kernel_equals_restatement(gpu_ctx):
+def restatement_loci():
+    """The loci of test_gpu_kernel_equals_restatement (and of tests/test_gpu_grid_cap.py): every launch class, reference lengths
+    around every strip-width edge, N and lower case, gaps in the left flank.  (loci, the flank-gap loci among them)."""
     rng = np.random.default_rng(82)
     loci = []
     for k in range(60):
@@ -77,6 +78,12 @@ def test_gpu_kernel_equals_restatement(gpu_ctx):
                          alleles=[run * ref_n] + [run * k for k in alt_ns], read_allele=[], trimmed_reads=[])
         flank_gaps.append(fl)
         loci.append(fl)
+    return loci, flank_gaps
+
+
+@pytest.mark.gpu
+def test_gpu_kernel_equals_restatement(gpu_ctx):
+    loci, flank_gaps = restatement_loci()
     got = gpu_ctx.haplotype_align_to_ref([L.blocks() for L in loci])
     n = slid = 0
     for L, infos in zip(loci, got):

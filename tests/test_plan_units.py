@@ -657,3 +657,38 @@ def test_schedule_grid_cap_lowers_the_strip_launches_only():
         assert (c["x_grid"][:4] == np.minimum(s["x_grid"][:4], 7)).all() and (c["x_grid"][4:] == s["x_grid"][4:]).all()
         big = _lib.debug_plan_schedule(batch, _grids(), n_cu=256, cap=40, **kw)
         assert big["launches"] == s["launches"] and big["max_grid"] == 25
+
+
+def test_schedule_grid_cap_switch_lowers_every_launch():
+    """ltr_ctx_set_debug "grid_cap" (Schedule::cap_every_grid): the launches cap_grids leaves alone -- packed, workgroup, the four- and
+    eight-wave exact lists, the W = 20 exact launch -- are lowered too, and nothing but grids moves."""
+    rng = np.random.default_rng(27)
+    seq = lambda n: bytes(rng.choice(list(b"ACGT"), size=n).astype(np.uint8))
+    # twelve families (one CU: families by rule from twelve up) of three members: twelve reads of 701 bases against three windows that share
+    # 200 rows -> 3 workgroups; six workgroup pairs (2700 columns: a plan of twelve pairs per CU and more keeps reads of up to 2560 on
+    # one wavefront; fewer than ten long pairs per CU) -> 6 workgroups and six
+    # candidates of the four-wave list, whose W = 20 launch gets ceil(6 / 4) = 2; a read with an N -> the generic list
+    prefix = seq(200)
+    fam = ([seq(701) for _ in range(12)], [seq(30) + prefix + b"ACG"[k:k + 1] + seq(n) + seq(30) for k, n in enumerate((449, 499, 559))])
+    n_read = _locus(rng, 201, 1, 2)
+    n_read[0][0] = n_read[0][0][:5] + b"N" + n_read[0][0][6:]
+    batch = _mixed_batch(rng, extra=[fam, _locus(rng, 2701, 3, 2), n_read])
+    for kw, kinds in ((dict(), {"family", "workgroup", "plan"}), (dict(plan_kernel=1, no_multi=1), {"workgroup", "one-wave", "packed"})):
+        s = _lib.debug_plan_schedule(batch, _grids(), n_cu=1, **kw)       # (families go with the plan kernel: a launch per class has none)
+        assert {l["kind"] for l in s["launches"]} == kinds
+        for kind in kinds:                                        # every kind has a launch the cap bites on
+            assert max(l["grid"] for l in s["launches"] if l["kind"] == kind) > 2, kind
+        # (the plan kernel scores its failed certificates in line; per class the 24 pairs of 1200 columns are candidates of the four-wave list too)
+        n4 = 6 if not kw else 30
+        assert s["x_grid"][4] == n4 and s["max_grid_wide"] == (n4 + 3) // 4 and s["max_grid"] > 2
+        for cap in (1, 2):
+            c = _lib.debug_plan_schedule(batch, _grids(), n_cu=1, grid_cap=cap, **kw)
+            for name in ("launches", "by_class"):
+                assert [l["grid"] for l in c[name]] == [min(l["grid"], cap) for l in s[name]]
+                assert [{**l, "grid": 0} for l in c[name]] == [{**l, "grid": 0} for l in s[name]]                   # nothing else moves
+            assert len(c["x_grid"]) == 6 and (c["x_grid"] == np.minimum(s["x_grid"], cap)).all() and c["x_grid"][4] == cap
+            assert c["max_grid_wide"] == min(s["max_grid_wide"], cap) == cap and c["max_grid"] == cap
+            assert c["entries"] == s["entries"] and c["n_tabs"] == s["n_tabs"] and c["use_plan"] == s["use_plan"] and c["max_len"] == s["max_len"]
+            assert (c["xcand"] == s["xcand"]).all() and (c["class_first"] == s["class_first"]).all()
+        # 0 is no cap
+        assert _lib.debug_plan_schedule(batch, _grids(), n_cu=1, grid_cap=0, **kw)["launches"] == s["launches"]
