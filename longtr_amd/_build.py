@@ -11,6 +11,10 @@ SOURCES = ["ltr_ctx.hip", "ltr_plan_build.hip", "ltr_plan_run.hip", "ltr_posteri
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-honor-nans", "-std=c++17", "-fPIC", "-shared", "-pthread", "-Wall"]
 LINK_LIBS = ["-lz"]                                         # BGZF blocks (ltr_bgzf.h: BAM, VCF writer, tabix-indexed VCF input)
 OBJ_DIR = os.path.join(CSRC, "build")
+# The read filter (include/ltr_filter.h) is a host library of its own: libltr_gpu.so, its sources and its source_id stay what they are.
+FILTER_SRC = os.path.join(HERE, "filter", "ltr_filter.cpp")
+FILTER_LIB_PATH = os.path.join(HERE, "filter", "libltr_filter.so")
+FILTER_FLAGS = ["-x", "c++", "-std=c++17", "-O2", "-fPIC", "-shared", "-Wall"]
 
 
 def build(force=False, extra_flags=()):
@@ -33,6 +37,7 @@ def build(force=False, extra_flags=()):
         if force or not os.path.exists(obj) or os.path.getmtime(obj) < max(os.path.getmtime(src), hdr_time):
             jobs.append([hipcc] + flags + ["-c", src, "-o", obj])
     objs = [os.path.join(OBJ_DIR, s + ".o") for s in SOURCES]
+    build_filter(hipcc, force)
     if not jobs and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(o) for o in objs):
         return LIB_PATH
     with ThreadPoolExecutor(max_workers=max(1, min(len(jobs), os.cpu_count() or 1))) as ex:
@@ -42,6 +47,15 @@ def build(force=False, extra_flags=()):
     open(stamp, "w").write(" ".join(flags))
     subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-pthread"] + objs + LINK_LIBS + ["-o", LIB_PATH], check=True)
     return LIB_PATH
+
+
+def build_filter(compiler=None, force=False):
+    """libltr_filter.so from filter/ltr_filter.cpp: host code only, one translation unit, no device pass."""
+    compiler = compiler or os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    deps = [FILTER_SRC, os.path.join(HERE, "..", "include", "ltr_filter.h")]
+    if force or not os.path.exists(FILTER_LIB_PATH) or os.path.getmtime(FILTER_LIB_PATH) < max(os.path.getmtime(d) for d in deps):
+        subprocess.run([compiler] + FILTER_FLAGS + [FILTER_SRC, "-o", FILTER_LIB_PATH], check=True)
+    return FILTER_LIB_PATH
 
 
 def source_id():

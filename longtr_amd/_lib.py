@@ -10,6 +10,7 @@ This module is the facade: every name is defined in one of the modules below, by
   _loader      lib() (loads at first use, applies SIGNATURES once), LtrError
   _context     Context
   _genotype    Plan, GenotypeResult, the VCF record of a locus
+  _filter      the reference's read filter for one region (libltr_filter.so, include/ltr_filter.h)
   _formats     region files, FASTA, VCF writer / panel / index, BAM
   _host        host-only helpers: trimming, pooling, pruning, remapping, phasing priors
   _haplotypes  ReadSet, edit distances, clustering, consensus
@@ -20,6 +21,7 @@ from ._build import CSRC, HERE, HIPCC_FLAGS, KERNEL_TUS, LIB_PATH, LINK_LIBS, OB
 from ._context import Context
 from ._debug import (LAUNCH_KINDS, LAUNCH_NOTE_KINDS, debug_chunk_plan, debug_describe_batch, debug_last_launches, debug_plan_families,
                      debug_plan_family_forks, debug_plan_schedule, debug_threshold_groups)
+from ._filter import filter_options, filter_reads
 from ._formats import Bam, Fasta, VcfPanel, VcfWriter, read_regions, tbi_parse, vcf_header, vcf_index
 from ._genotype import FAMILIES, GenotypeResult, Plan, _locus_haploid, get_alleles, vcf_fields, vcf_record, vcf_record_from_fields
 from ._haplotypes import ReadSet, _hap_result, cluster_sequences, edit_distances, pack_seq_groups, poa_consensus
