@@ -722,9 +722,19 @@ HOOK_SIGNATURES = {
 }
 
 
+# include/ltr_gpu_ploidy.h: the ploidy per (locus, sample).  A table of its own: SIGNATURES is held to ltr_gpu.h, declaration for
+# declaration (tests/test_sample_ploidy_abi.py parses the new header and holds this table to it the same way).
+PLOIDY_SIGNATURES = {
+    "ltr_plan_posteriors_sample_ploidy": (_int, [_vp, _P(PosteriorBatch), _vp, _vp, _vp, _vp]),
+    "ltr_plan_genotype_sample_ploidy": (_int, [_vp, _P(GenotypeBatch), _P(FieldsRequest), _vp, _P(_vp)]),
+    "ltr_ll_genotype_sample_ploidy": (_int, [_vp, _P(LlBatch), _P(GenotypeBatch), _P(FieldsRequest), _vp, _P(_vp)]),
+    "ltr_genotype_result_sample_haploid": (_i32, [_vp, _i64, _i32]),
+}
+
+
 def bind(L):
     """Give every function of the loaded library its signature: the one walk over the tables."""
-    for table in (SIGNATURES, HOOK_SIGNATURES):
+    for table in (SIGNATURES, PLOIDY_SIGNATURES, HOOK_SIGNATURES):
         for name, (ret, params) in table.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = ret, params

@@ -9,6 +9,7 @@ KERNEL_TUS = ["ltr_k_one.hip", "ltr_k_pack.hip", "ltr_k_plan.hip", "ltr_k_wg.hip
 PLAN_UNITS = ["ltr_plan_rules.cpp", "ltr_plan_sort.cpp", "ltr_plan_families.cpp", "ltr_plan_describe.cpp", "ltr_plan_schedule.cpp", "ltr_plan_hooks.cpp"]      # host-side planning (csrc/ltr_plan.h)
 SOURCES = ["ltr_ctx.hip", "ltr_plan_build.hip", "ltr_plan_run.hip", "ltr_posterior.hip", "ltr_plan_genotype.hip", "ltr_plan_fields.hip"] + KERNEL_TUS + ["ltr_short.hip", "ltr_nw.hip"] + PLAN_UNITS + ["ltr_host.cpp", "ltr_hap_aln.cpp", "ltr_genotype.cpp", "ltr_vcf.cpp", "ltr_prep.cpp", "ltr_io.cpp", "ltr_bam.cpp", "ltr_vcf_in.cpp", "ltr_editdist.hip", "ltr_poa.hip", "ltr_cluster.cpp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-honor-nans", "-std=c++17", "-fPIC", "-shared", "-pthread", "-Wall"]
+PUBLIC_HEADERS = ["ltr_gpu.h", "ltr_gpu_ploidy.h"]           # include/: what the sources are built against (ltr_filter.h is the filter library's)
 LINK_LIBS = ["-lz"]                                         # BGZF blocks (ltr_bgzf.h: BAM, VCF writer, tabix-indexed VCF input)
 OBJ_DIR = os.path.join(CSRC, "build")
 # The read filter (include/ltr_filter.h) is a host library of its own: libltr_gpu.so, its sources and its source_id stay what they are.
@@ -23,7 +24,7 @@ def build(force=False, extra_flags=()):
     side by side on the host cores, then linked."""
     import glob
     from concurrent.futures import ThreadPoolExecutor
-    hdrs = glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hpp")) + [os.path.join(HERE, "..", "include", "ltr_gpu.h")]
+    hdrs = glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hpp")) + [os.path.join(HERE, "..", "include", h) for h in PUBLIC_HEADERS]
     hdr_time = max(os.path.getmtime(h) for h in hdrs)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     os.makedirs(OBJ_DIR, exist_ok=True)
@@ -66,7 +67,7 @@ def source_id():
     import hashlib
     h = hashlib.sha256(" ".join(HIPCC_FLAGS).encode())
     files = sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hpp")) + glob.glob(os.path.join(CSRC, "*.hip"))
-                   + glob.glob(os.path.join(CSRC, "*.cpp")) + [os.path.join(HERE, "..", "include", "ltr_gpu.h")], key=os.path.basename)
+                   + glob.glob(os.path.join(CSRC, "*.cpp")) + [os.path.join(HERE, "..", "include", h) for h in PUBLIC_HEADERS], key=os.path.basename)
     for f in files:
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())

@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._genotype import GenotypeResult, Plan, _locus_haploid
+from ._genotype import GenotypeResult, Plan, _locus_haploid, _sample_haploid
 from ._haplotypes import _hap_result, edit_distances, poa_consensus
 from ._loader import Handle, LtrError, _p, lib
 
@@ -230,12 +230,14 @@ class Context(Handle):
                     loci_blocks=loci_blocks if loci_blocks is not None else [[dict(alleles=[b""] * int(h))] for h in n_haps])
 
     def genotype_ll(self, ll_list=None, seed_list=None, loci_blocks=None, locus_read_off=None, log_p1=None, log_p2=None, sample_label=None,
-                    n_samples=None, haploid=False, prune=True, want_read_ll=False, fields=None, sample_filtered=None, packed=None, locus_haploid=None):
+                    n_samples=None, haploid=False, prune=True, want_read_ll=False, fields=None, sample_filtered=None, packed=None, locus_haploid=None,
+                    sample_haploid=None):
         """ltr_ll_genotype: what Plan.genotype / Plan.genotype_fields do for a resident plan, on per-read matrices in host
         memory -- the output of calc_hap_aln_probs (any path: plans, the seeded stutter path, mates summed, realign masks).
         fields: None = no VCF fields (as Plan.genotype; posterior blocks are downloaded), or a dict with any of block,
         want_gls, want_pls, want_phased_gls, want_posteriors (as Plan.genotype_fields).  packed: a pack_ll_genotype image.
         locus_haploid: the ploidy of every locus (ltr_ll_genotype_ploidy; `haploid` is then not read), None = `haploid` for all.
+        sample_haploid: the ploidy of every (locus, sample), one array of S flags per locus (ltr_ll_genotype_sample_ploidy); not with locus_haploid.
         Returns a GenotypeResult (close() it, or use it as a context manager)."""
         if packed is None:
             packed = self.pack_ll_genotype(ll_list, seed_list, loci_blocks, locus_read_off, log_p1, log_p2, sample_label, n_samples, haploid,
@@ -253,12 +255,15 @@ class Context(Handle):
                 setattr(fr, k, int(bool(fields.get(k, False))))
         h = C.c_void_p()
         pfr = None if fr is None else C.byref(fr)
-        if locus_haploid is None:
+        if sample_haploid is not None:
+            sh = _sample_haploid(sample_haploid, packed["n_samples"], locus_haploid)
+            self._check(L.ltr_ll_genotype_sample_ploidy(self._h, C.byref(packed["lb"]), C.byref(packed["gb"]), pfr, _p(sh), C.byref(h)))
+        elif locus_haploid is None:
             self._check(L.ltr_ll_genotype(self._h, C.byref(packed["lb"]), C.byref(packed["gb"]), pfr, C.byref(h)))
         else:
             lh = _locus_haploid(locus_haploid, len(packed["n_samples"]))
             self._check(L.ltr_ll_genotype_ploidy(self._h, C.byref(packed["lb"]), C.byref(packed["gb"]), pfr, _p(lh), C.byref(h)))
-        return GenotypeResult(self, h, packed)
+        return GenotypeResult(self, h, packed, per_sample=sample_haploid is not None)
 
     def edit_distances(self, groups, cap):
         """ltr_edit_distances: groups = list of lists of bytes; per group the U x U int32 matrix min(levenshtein, cap)."""

@@ -41,9 +41,10 @@ class Plan(Handle):
         self.ctx._check(lib().ltr_plan_last_kernel_ms(self._h, C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
-    def posteriors(self, locus_read_off, pool_index, log_p1, log_p2, sample_label, n_samples, haploid=False, locus_haploid=None):
+    def posteriors(self, locus_read_off, pool_index, log_p1, log_p2, sample_label, n_samples, haploid=False, locus_haploid=None, sample_haploid=None):
         """ltr_plan_posteriors: all loci, from the device-resident LL of the last execute.
         locus_haploid: the ploidy of every locus (ltr_plan_posteriors_ploidy; `haploid` is then not read), None = `haploid` for all.
+        sample_haploid: the ploidy of every (locus, sample), one array of S flags per locus (ltr_plan_posteriors_sample_ploidy); not with locus_haploid.
         Returns (post_flat, post_off[units+1], sample_total_ll, gts[units,2]); units = (locus, sample) in order."""
         pb, keep = self._posterior_batch(locus_read_off, pool_index, log_p1, log_p2, sample_label, n_samples, haploid)
         ns = keep[5]
@@ -54,7 +55,10 @@ class Plan(Handle):
         post = np.zeros(max(int(off[-1]), 1), dtype=np.float64)
         stl = np.zeros(max(len(sizes), 1), dtype=np.float64)
         gts = np.zeros(2 * max(len(sizes), 1), dtype=np.int32)
-        if locus_haploid is None:
+        if sample_haploid is not None:
+            sh = _sample_haploid(sample_haploid, ns, locus_haploid)
+            self.ctx._check(lib().ltr_plan_posteriors_sample_ploidy(self._h, C.byref(pb), _p(sh), _p(post), _p(stl), _p(gts)))
+        elif locus_haploid is None:
             self.ctx._check(lib().ltr_plan_posteriors(self._h, C.byref(pb), _p(post), _p(stl), _p(gts)))
         else:
             lh = _locus_haploid(locus_haploid, len(ns))
@@ -92,42 +96,50 @@ class Plan(Handle):
         gb.prune, gb.want_read_ll = int(bool(prune)), int(bool(want_read_ll))
         return dict(gb=gb, keep=(pb, keep, phs, arr, sf), n_samples=keep[5], locus_read_off=keep[0], loci_blocks=loci_blocks)
 
-    def genotype_packed(self, packed, decode=True, locus_haploid=None):
+    def genotype_packed(self, packed, decode=True, locus_haploid=None, sample_haploid=None):
         """ltr_plan_genotype on a pack_genotype image.  decode=False: run, free the result, return None (timing).
-        locus_haploid: the ploidy of every locus (ltr_plan_genotype_ploidy), None = the image's `haploid` for all."""
+        locus_haploid: the ploidy of every locus (ltr_plan_genotype_ploidy), None = the image's `haploid` for all.
+        sample_haploid: one array of S flags per locus (ltr_plan_genotype_sample_ploidy); not with locus_haploid."""
         L = lib()
         h = C.c_void_p()
-        if locus_haploid is None:
+        if sample_haploid is not None:
+            sh = _sample_haploid(sample_haploid, packed["n_samples"], locus_haploid)
+            self.ctx._check(L.ltr_plan_genotype_sample_ploidy(self._h, C.byref(packed["gb"]), None, _p(sh), C.byref(h)))
+        elif locus_haploid is None:
             self.ctx._check(L.ltr_plan_genotype(self._h, C.byref(packed["gb"]), C.byref(h)))
         else:
             lh = _locus_haploid(locus_haploid, len(packed["n_samples"]))
             self.ctx._check(L.ltr_plan_genotype_ploidy(self._h, C.byref(packed["gb"]), None, _p(lh), C.byref(h)))
-        with GenotypeResult(self.ctx, h, packed) as res:
+        with GenotypeResult(self.ctx, h, packed, per_sample=sample_haploid is not None) as res:
             if not decode:
                 return None
-            out = [dict(res.locus(l), haploid=res.haploid(l)) for l in range(res.n_loci)]
+            out = [dict(res.locus(l), haploid=res.haploid(l)) for l in range(res.n_loci)]     # (locus() carries "sample_haploid")
             for d, S in zip(out, packed["n_samples"]):
                 if d["post"] is None:                            # (always downloaded here: None is the empty block of a locus without samples)
                     d["post"] = np.zeros((int(S), d["n_haps"], d["n_haps"]))
             return out
 
     def genotype(self, loci_blocks, locus_read_off, pool_index, log_p1, log_p2, sample_label, n_samples, haploid=False,
-                 sample_filtered=None, prune=True, want_read_ll=True, locus_haploid=None):
+                 sample_filtered=None, prune=True, want_read_ll=True, locus_haploid=None, sample_haploid=None):
         """ltr_plan_genotype: SeqStutterGenotyper::genotype after the alignment for every locus of the executed plan --
         posteriors, uncalled alleles pruned once (prune=True), posteriors again over the surviving haplotypes.  Returns per
         locus a dict: n_haps, new_to_old, allele_mapping, removed (per block), num_aff_blocks / num_aff_alleles, blocks (the
         final block list), post [S, H', H'], sample_total_ll [S], gts [S, 2] (new indices), read_ll [R, H'] or None, haploid (0 / 1).
-        locus_haploid: the ploidy of every locus (a whole-genome plan with --haploid-chrs), None = `haploid` for all."""
+        locus_haploid: the ploidy of every locus (a whole-genome plan with --haploid-chrs), None = `haploid` for all.
+        sample_haploid: the ploidy of every (locus, sample), one array of S flags per locus (chrX of a mixed cohort); not with locus_haploid."""
         return self.genotype_packed(self.pack_genotype(loci_blocks, locus_read_off, pool_index, log_p1, log_p2, sample_label, n_samples,
-                                                       haploid, sample_filtered, prune, want_read_ll), locus_haploid=locus_haploid)
+                                                       haploid, sample_filtered, prune, want_read_ll), locus_haploid=locus_haploid,
+                                    sample_haploid=sample_haploid)
 
     def genotype_fields(self, loci_blocks=None, locus_read_off=None, pool_index=None, log_p1=None, log_p2=None, sample_label=None,
                         n_samples=None, haploid=False, sample_filtered=None, prune=True, want_read_ll=False, block=None,
-                        want_gls=False, want_pls=False, want_phased_gls=False, want_posteriors=False, packed=None, locus_haploid=None):
+                        want_gls=False, want_pls=False, want_phased_gls=False, want_posteriors=False, packed=None, locus_haploid=None,
+                        sample_haploid=None):
         """ltr_plan_genotype_fields: ltr_plan_genotype and the VCF fields of every locus computed on the device (GT, Q, PQ,
         GLDIFF, DP, DSNP, PSNP, MALLREADS' alleles; GL / PL / PHASEDGL on request).  block: per locus, None = the first repeat
         block.  Posterior blocks / per-read matrices are downloaded only when asked for.  packed: a pack_genotype image (its
         want_read_ll holds).  locus_haploid: the ploidy of every locus (ltr_plan_genotype_ploidy), None = `haploid` for all.
+        sample_haploid: one array of S flags per locus (ltr_plan_genotype_sample_ploidy); not with locus_haploid.
         Returns a GenotypeResult (close() it, or use it as a context manager)."""
         if packed is None:
             packed = self.pack_genotype(loci_blocks, locus_read_off, pool_index, log_p1, log_p2, sample_label, n_samples, haploid,
@@ -142,12 +154,15 @@ class Plan(Handle):
         fr.want_gls, fr.want_pls, fr.want_phased_gls = int(bool(want_gls)), int(bool(want_pls)), int(bool(want_phased_gls))
         fr.want_posteriors = int(bool(want_posteriors))
         h = C.c_void_p()
-        if locus_haploid is None:
+        if sample_haploid is not None:
+            sh = _sample_haploid(sample_haploid, packed["n_samples"], locus_haploid)
+            self.ctx._check(L.ltr_plan_genotype_sample_ploidy(self._h, C.byref(packed["gb"]), C.byref(fr), _p(sh), C.byref(h)))
+        elif locus_haploid is None:
             self.ctx._check(L.ltr_plan_genotype_fields(self._h, C.byref(packed["gb"]), C.byref(fr), C.byref(h)))
         else:
             lh = _locus_haploid(locus_haploid, len(packed["n_samples"]))
             self.ctx._check(L.ltr_plan_genotype_ploidy(self._h, C.byref(packed["gb"]), C.byref(fr), _p(lh), C.byref(h)))
-        return GenotypeResult(self.ctx, h, packed)
+        return GenotypeResult(self.ctx, h, packed, per_sample=sample_haploid is not None)
 
     def set_timing(self, on=True):
         """on: False / True (every launch as it is launched) / 2 (the multi-width one-wave launch class by class)."""
@@ -264,8 +279,10 @@ class GenotypeResult(Handle):
 
     _free = "ltr_genotype_result_free"
 
-    def __init__(self, ctx, handle, packed):
-        self.ctx, self._h, self._packed = ctx, handle, packed
+    def __init__(self, ctx, handle, packed, per_sample=True):
+        """per_sample=False: the call gave no ploidy per sample, so the samples of a locus have the locus's (sample_haploid() then
+        asks the library once per locus, not once per sample)."""
+        self.ctx, self._h, self._packed, self._per_sample, self._flags = ctx, handle, packed, per_sample, {}
 
     def __enter__(self):
         return self
@@ -284,13 +301,30 @@ class GenotypeResult(Handle):
             raise LtrError(rc, "ltr_genotype_result_haploid")
         return int(rc)
 
+    def sample_haploid(self, l):
+        """ltr_genotype_result_sample_haploid: the ploidy every sample of locus l was genotyped with ([S] of 0 / 1)."""
+        if not 0 <= int(l) < self.n_loci:
+            raise LtrError(_abi.LTR_ERR_INVALID, "ltr_genotype_result_sample_haploid")
+        l = int(l)
+        if l not in self._flags:                                 # (asked for by fields() and locus() alike: once per locus)
+            S, L = int(self._packed["n_samples"][l]), lib()
+            if self._per_sample:
+                out = np.asarray([L.ltr_genotype_result_sample_haploid(self._h, l, s) for s in range(S)], dtype=np.int32)
+                if (out < 0).any():
+                    raise LtrError(int(out.min()), "ltr_genotype_result_sample_haploid")
+            else:
+                out = np.full(S, self.haploid(l), dtype=np.int32)
+            self._flags[l] = out.astype(np.uint8)
+        return self._flags[l].copy()
+
     def fields(self, l):
-        """The LocusFields.to_dict() image of locus l (copies)."""
+        """The LocusFields.to_dict() image of locus l (copies) + "sample_haploid" [S]: in a mixed locus (diploid widths) a haploid
+        sample's gls / pls row holds its V values first and 0 after them, its phased_gls row 0.0."""
         f = _abi.LocusFields()
         rc = lib().ltr_genotype_result_fields(self._h, int(l), C.byref(f))
         if rc != 0:
             raise LtrError(rc, "ltr_genotype_result_fields")
-        return f.to_dict()
+        return dict(f.to_dict(), sample_haploid=self.sample_haploid(l))
 
     def locus(self, l):
         """What Plan.genotype returns for locus l: post / read_ll are None when they were not asked for."""
@@ -307,7 +341,7 @@ class GenotypeResult(Handle):
             removed.append([ptr[i] for i in range(n)])
         post, rll = L.ltr_genotype_result_log_sample_posteriors(h, l), L.ltr_genotype_result_read_ll(h, l)
         return dict(
-            n_haps=Hn, new_to_old=take(L.ltr_genotype_result_new_to_old(h, l), Hn, np.int32),
+            sample_haploid=self.sample_haploid(l), n_haps=Hn, new_to_old=take(L.ltr_genotype_result_new_to_old(h, l), Hn, np.int32),
             allele_mapping=take(L.ltr_genotype_result_allele_mapping(h, l), Ho, np.int32), removed=removed,
             num_aff_blocks=L.ltr_genotype_result_num_aff_blocks(h, l), num_aff_alleles=L.ltr_genotype_result_num_aff_alleles(h, l),
             blocks=_abi.blocks_from_struct(L.ltr_genotype_result_blocks(h, l).contents) if any(removed) else old,
@@ -333,6 +367,19 @@ class GenotypeResult(Handle):
         finally:
             L.ltr_vcf_text_free(text)
         return [raw[off[l]:off[l + 1] - 1].decode() for l in range(n)], pos[:n].copy()
+
+
+def _sample_haploid(sample_haploid, n_samples, locus_haploid=None):
+    """The uint8 array of the *_sample_ploidy entry points (unit order) from one array of S_l flags per locus."""
+    if locus_haploid is not None:
+        raise LtrError(_abi.LTR_ERR_INVALID, "sample_haploid and locus_haploid in one call: give the ploidy once")
+    if len(sample_haploid) != len(n_samples):
+        raise LtrError(_abi.LTR_ERR_INVALID, f"sample_haploid: one array per locus ({len(n_samples)}), got {len(sample_haploid)}")
+    rows = [np.atleast_1d(np.asarray(f)).astype(bool).astype(np.uint8) for f in sample_haploid]
+    for l, (f, S) in enumerate(zip(rows, n_samples)):
+        if f.shape != (int(S),):
+            raise LtrError(_abi.LTR_ERR_INVALID, f"sample_haploid: locus {l} has {int(S)} samples, got {f.size} flags")
+    return np.ascontiguousarray(np.concatenate(rows + [np.zeros(1, dtype=np.uint8)]))     # (never empty: a valid address)
 
 
 def _locus_haploid(locus_haploid, n_loci):

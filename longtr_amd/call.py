@@ -42,7 +42,7 @@ CRAM_REFUSAL = "CRAM input is not supported: convert to BAM with a .bai index."
 DEFAULTS = dict(chrom=None, phased_bam=False, haploid_chrs=(), bam_samps=None, bam_libs=None, ref_vcf=None, min_mapq=20, min_mean_qual=30.0,
                 max_tr_len=1000, min_reads=10, max_reads=1000000, max_haps=1000, indel_flank_len=5, alignment_params=None, stutter_align_len=0,
                 output_gls=False, output_pls=False, output_phased_gls=False, output_filters=False, alleles="exact", chunk_loci=1024,
-                chunk_read_bytes=256 << 20, overlap=True, full_command="longtr_amd.call", require_spanning=1, min_flank=5)
+                chunk_read_bytes=256 << 20, overlap=True, full_command="longtr_amd.call", require_spanning=1, min_flank=5, sample_ploidy=None)
 
 
 # ---- the reference sequence ---------------------------------------------------------------------------------------------------
@@ -105,6 +105,45 @@ def sample_columns(read_groups, bam_samps=None, n_files=None):
             if not any(g["file"] == f for g in read_groups):
                 raise LtrError(_abi.LTR_ERR_INVALID, "Provided BAM/CRAM files don't contain read groups in the header and the --bam-samps flag was not specified")
     return sorted({g["sample"] for g in read_groups}, key=lambda s: s.encode())
+
+
+# ---- ploidy -------------------------------------------------------------------------------------------------------------------
+def read_sample_ploidy(source, samples=None):
+    """{(sample, chrom): 1 | 2} of --sample-ploidy: a path to tab-separated lines `sample  chrom  ploidy` (# starts a comment, blank
+    lines are skipped) or such a dict.  A ploidy other than 1 or 2, a malformed line, or -- with `samples`, the VCF's columns -- a
+    sample none of the inputs holds raise LtrError(LTR_ERR_INVALID).  A pair named twice keeps its last value."""
+    bad = lambda text: LtrError(_abi.LTR_ERR_INVALID, "--sample-ploidy: " + text)
+    table = {}
+    if source is None:
+        return table
+    if isinstance(source, dict):
+        rows = [(f"entry {k!r}", k, v) for k, v in source.items()]
+        for where, k, _ in rows:
+            if not (isinstance(k, tuple) and len(k) == 2 and all(isinstance(x, str) and x for x in k)):
+                raise bad(f"{where}: a key is (sample, chrom)")
+    else:
+        rows = []
+        with open(source) as fh:
+            for n, line in enumerate(fh, 1):
+                text = line.split("#", 1)[0].strip()
+                if not text:
+                    continue
+                cols = text.split("\t")
+                if len(cols) != 3 or not all(c.strip() for c in cols):
+                    raise bad(f"{source}:{n}: expected `sample<TAB>chrom<TAB>ploidy`, got {line.rstrip()!r}")
+                rows.append((f"{source}:{n}", (cols[0].strip(), cols[1].strip()), cols[2].strip()))
+    for where, key, val in rows:
+        if str(val) not in ("1", "2") or isinstance(val, bool):
+            raise bad(f"{where}: ploidy is 1 or 2, got {val!r} (leave a sample without a copy out of the BAM list)")
+        if samples is not None and key[0] not in samples:
+            raise bad(f"{where}: sample {key[0]!r} is in none of the BAMs (samples: {', '.join(samples)})")
+        table[key] = int(val)
+    return table
+
+
+def sample_ploidy(table, haploid_chrs, sample, chrom):
+    """1 or 2: the table's value for (sample, chrom); a pair it does not name is 1 on a chromosome of --haploid-chrs, else 2."""
+    return table.get((sample, chrom), 1 if chrom in haploid_chrs else 2)
 
 
 # ---- gates --------------------------------------------------------------------------------------------------------------------
@@ -193,6 +232,7 @@ def _check_options(options):
     if unknown:
         raise TypeError(f"genotype_regions: unknown option(s) {', '.join(sorted(unknown))}")
     o = dict(DEFAULTS, **options)
+    o["sample_ploidy"] = read_sample_ploidy(o["sample_ploidy"])   # (format errors here, before anything is opened; the samples are checked once the BAM headers are read)
     if o["alleles"] not in ("exact", "clustered", "consensus"):
         raise LtrError(_abi.LTR_ERR_INVALID, 'alleles is "exact", "clustered" or "consensus"')
     if o["ref_vcf"] and o["alleles"] != "exact":
@@ -281,6 +321,7 @@ def _gate(p, o, **facts):
 
 def _run_chunk(ctx, chunk, o, panel, columns, vopt, writer, stage, haploid_chrs):
     """Haplotypes, alignment, genotypes and records of one chunk (the calling thread: every GPU call is here)."""
+    one_copy = lambda p: [sample_ploidy(o["sample_ploidy"], haploid_chrs, s, p.region["chrom"]) == 1 for s in p.entry["samples"]]
     live = [p for p in chunk if p.rs is not None]
     try:
         t = time.perf_counter()
@@ -304,10 +345,15 @@ def _run_chunk(ctx, chunk, o, panel, columns, vopt, writer, stage, haploid_chrs)
         while todo:
             lro = np.zeros(len(todo) + 1, dtype=np.int64)
             lro[1:] = np.cumsum([len(p.alns) for p in todo])
+            # The ploidy per locus as long as the samples of every locus are alike (the bytes of --haploid-chrs); a call with a
+            # mixed locus carries the flags of every sample instead (its uniform loci take the per-locus path inside all the same).
+            flags = [one_copy(p) for p in todo]
+            mixed = any(len(set(f)) > 1 for f in flags)
+            by_chrom = lambda p: p.region["chrom"] in haploid_chrs                # (a locus without a sample: what --haploid-chrs says, as before)
+            ploidy = dict(sample_haploid=flags) if mixed else dict(locus_haploid=[f[0] if f else by_chrom(p) for f, p in zip(flags, todo)])
             result = ctx.genotype_ll([m for m, _ in res], [s for _, s in res], [p.blocks for p in todo], lro, np.concatenate([p.p1 for p in todo]),
                                      np.concatenate([p.p2 for p in todo]), np.concatenate([np.asarray(p.sample, dtype=np.int32) for p in todo]),
-                                     [len(p.entry["samples"]) for p in todo], prune=panel is None, fields=fields,
-                                     locus_haploid=[p.region["chrom"] in haploid_chrs for p in todo])
+                                     [len(p.entry["samples"]) for p in todo], prune=panel is None, fields=fields, **ploidy)
             # a sample without an optimal pair (best_gts = -1) would make ltr_genotype_result_vcf_records refuse the whole call
             bad = [k for k, p in enumerate(todo) if _gate(p, o, missing_pair=bool((result.fields(k)["best_gts"] < 0).any()))]
             if not bad:
@@ -333,7 +379,7 @@ def _run_chunk(ctx, chunk, o, panel, columns, vopt, writer, stage, haploid_chrs)
                     log_aln_probs=none, log_p1=p.p1, log_p2=p.p2, sample_label=np.asarray(p.sample, dtype=np.int32), alns=p.alns,
                     aln_deleted=[r["deleted"] for r in p.reads], log_sample_posteriors=none, sample_total_ll=none,
                     best_haplotypes=np.zeros(0, dtype=np.int32), n_p1s=p.rs.n_p1s, n_p2s=p.rs.n_p2s, sample_names=p.entry["samples"],
-                    haploid=reg["chrom"] in haploid_chrs, out_sample_names=columns)))
+                    haploid=all(one_copy(p)) if p.entry["samples"] else reg["chrom"] in haploid_chrs, out_sample_names=columns)))
                 p.entry.update(n_haplotypes=int(g["n_haps"]), n_alleles=len(alleles))
             lines, pos = result.vcf_records(pvs, vopt)
         for p, line, ps in zip(todo, lines, pos):
@@ -353,7 +399,8 @@ def genotype_regions(ctx, bams, reference, regions, out_vcf, **options):
     fetch(chrom, start, end) (0-based, end inclusive), length(chrom) and contig_lines().  regions: a region file (CHROM START STOP
     MOTIF [NAME], ltr_read_regions) or a list of the dicts read_regions gives.  out_vcf: the VCF (BGZF for *.gz).
 
-    options, with the reference's names and defaults: chrom, phased_bam, haploid_chrs, bam_samps, bam_libs (accepted; libraries are
+    options, with the reference's names and defaults: chrom, phased_bam, haploid_chrs, sample_ploidy (ours: a path or {(sample, chrom):
+    1 | 2}, the ploidy of a sample on a chromosome where it differs from what haploid_chrs says -- chrX of a cohort of men and women), bam_samps, bam_libs (accepted; libraries are
     unused, duplicate removal is off in the reference, hipstr_main.cpp:383), ref_vcf, min_mapq 20, min_mean_qual 30, max_tr_len 1000,
     min_reads 10, max_reads 1000000, max_haps 1000, indel_flank_len 5, alignment_params (7 numbers), stutter_align_len 0, output_gls,
     output_pls, output_phased_gls, output_filters.  Ours: alleles = "exact" (ltr_build_haplotype) | "clustered" | "consensus" (the two
@@ -389,6 +436,7 @@ def genotype_regions(ctx, bams, reference, regions, out_vcf, **options):
         read_groups = bam.read_groups()
         columns = sample_columns(read_groups, o["bam_samps"], len(bams))
         report["columns"] = columns
+        read_sample_ploidy(o["sample_ploidy"], samples=columns)   # a sample none of the BAMs holds: an error before any work
         samples_arg = dict(file_samples=list(o["bam_samps"])) if o["bam_samps"] is not None else dict(read_groups=read_groups)
         bam_refs = dict(bam.refs())
         for chrom in dict.fromkeys(r["chrom"] for r in regs):    # verify_chromosomes (bam_processor.cpp:490-533)
@@ -410,7 +458,9 @@ def genotype_regions(ctx, bams, reference, regions, out_vcf, **options):
 
         def prepared():
             for reg in regs:
-                yield _prepare(bam, ref, reg, ref.length(reg["chrom"]), o, samples_arg, fopt, stage)
+                p = _prepare(bam, ref, reg, ref.length(reg["chrom"]), o, samples_arg, fopt, stage)
+                p.entry["sample_ploidy"] = [sample_ploidy(o["sample_ploidy"], haploid_chrs, s, reg["chrom"]) for s in columns]
+                yield p
 
         chunks = iter_chunks(prepared(), lambda p: p.read_bytes, o["chunk_loci"], o["chunk_read_bytes"])
         source = _ahead(chunks) if o["overlap"] else chunks
@@ -502,6 +552,8 @@ def make_parser():
     ap.add_argument("--chrom", default=None, metavar="<chrom>", help="only consider regions on this chromosome")
     ap.add_argument("--phased-bam", action="store_true", help="use the reads' HP tags as phasing priors")
     ap.add_argument("--haploid-chrs", default="", metavar="<list_of_chroms>", help="comma separated list of chromosomes to treat as haploid")
+    ap.add_argument("--sample-ploidy", default=None, metavar="<ploidy.tsv>", help="tab separated lines `sample chrom ploidy` (1 or 2, # comments): the copies of a "
+                    "chromosome a sample has, e.g. chrX of a man; a pair not named is 1 on a chromosome of --haploid-chrs, else 2")
     ap.add_argument("--bam-samps", default=None, metavar="<list_of_samples>", help="comma separated list of samples in the same order as the BAM files")
     ap.add_argument("--bam-libs", default=None, metavar="<list_of_libraries>", help="accepted; libraries are unused (no duplicate removal)")
     ap.add_argument("--ref-vcf", default=None, metavar="<tr_ref_panel.vcf.gz>", help="bgzipped, tabix-indexed VCF of candidate alleles")
@@ -543,7 +595,7 @@ def options_from_args(args):
                 alignment_params=None if args.alignment_params is None else [float(x) for x in args.alignment_params.split(",")],
                 stutter_align_len=args.stutter_align_len, output_gls=args.output_gls, output_pls=args.output_pls,
                 output_phased_gls=args.output_phased_gls, output_filters=args.output_filters, alleles=args.alleles, chunk_loci=args.chunk_loci,
-                chunk_read_bytes=args.chunk_read_bytes, overlap=not args.no_overlap)
+                chunk_read_bytes=args.chunk_read_bytes, overlap=not args.no_overlap, sample_ploidy=read_sample_ploidy(args.sample_ploidy) or None)
 
 
 def main(argv=None):
@@ -553,6 +605,15 @@ def main(argv=None):
         options = options_from_args(args)
     except LtrError as e:
         ap.error(str(e))
+    if options["sample_ploidy"]:                                 # its samples against the BAM headers, before a GPU is opened
+        try:
+            bam = Bam(args.bams.split(","), merge_by_position=False)
+            try:
+                read_sample_ploidy(options["sample_ploidy"], samples=sample_columns(bam.read_groups(), options["bam_samps"], len(args.bams.split(","))))
+            finally:
+                bam.close()
+        except LtrError as e:
+            ap.error(str(e))
     from ._context import Context
     ctx = Context(args.device)
     try:

@@ -319,8 +319,11 @@ int haplotype_sizes(const ltr_haplotype_blocks* hap, std::vector<int32_t>* count
 int64_t write_haplotypes(const ltr_haplotype_blocks* hap, int64_t n_haps, std::vector<int32_t>* counts, uint8_t* bytes, int64_t at, int64_t* off);
 // Mate pairs share one row sum (seq_stutter_genotyper.cpp:546-559) in rows [n_reads x n_haps]; read 0 as a second mate: LTR_ERR_INVALID
 int sum_mate_rows(double* rows, int32_t n_reads, int64_t n_haps, const uint8_t* second_mate, const uint8_t* copy_read, const uint8_t* realign_to_hap);
-// ltr_vcf_record_from_fields into a string (ltr_vcf.cpp): the length of the text or a negative status
-int64_t vcf_record_string(const ltr_vcf_locus* v, const ltr_locus_fields* f, const ltr_vcf_options* opt, std::string* text, int32_t* pos);
+// ltr_vcf_record_from_fields into a string (ltr_vcf.cpp): the length of the text or a negative status.  sample_haploid: null, or
+// for a diploid-form locus (v->haploid == 0) the ploidy of each of its samples [n_samples] (ltr_gpu_ploidy.h): a haploid one fills
+// its ten-field column with one allele and "." where a single copy has no value.
+int64_t vcf_record_string(const ltr_vcf_locus* v, const ltr_locus_fields* f, const ltr_vcf_options* opt, std::string* text, int32_t* pos,
+                          const uint8_t* sample_haploid = nullptr);
 
 // A block list that owns its arrays (view points into them; not copyable once filled).
 struct OwnedHapBlocks {

@@ -19,7 +19,14 @@ struct LtrPruned {
 struct ltr_genotype_result {
   int64_t n_loci = 0;
   std::vector<int32_t> S, H, n_blocks;           // per locus
-  std::vector<uint8_t> haploid;                  // per locus: its ploidy, resolved once at the top of the call (LocusPloidy); every stage reads this
+  std::vector<uint8_t> haploid;                  // per locus: its ploidy, resolved once at the top of the call (LocusPloidy); every stage reads this.
+                                                 // With a ploidy per sample: 1 exactly when every sample of the locus is haploid (0 for a mixed locus)
+  std::vector<uint8_t> sample_haploid;           // per unit: the sample's ploidy, resolved in the same place (SamplePloidy): priors, fields and records follow it
+  bool mixed(int64_t l) const {                  // a locus with a haploid sample that is not all haploid: the diploid shape, some rows haploid
+    if (haploid[(size_t)l]) return false;
+    for (int64_t u = unit_off[(size_t)l]; u < unit_off[(size_t)l + 1]; ++u) if (sample_haploid[(size_t)u]) return true;
+    return false;
+  }
   std::vector<int64_t> unit_off, post1_off;      // [n_loci + 1]
   std::unique_ptr<double[]> post1, post2, read_ll;      // first-pass blocks (plan's H), second-pass blocks of the pruned loci
   std::vector<double> stl;                       // [units] final

@@ -17,20 +17,22 @@
 
 namespace ltrf {                  // (the kernel's argument types, of this unit only)
 
-// one locus of the fields kernel
+// One locus of the fields kernel.  A mixed locus (haploid and diploid samples, ltr_gpu_ploidy.h) has a second record after those
+// of all loci, equal but for the constants, which are the haploid flavour there: its haploid units name that one (FieldUnit.locus).
 struct FieldLocus {
   int64_t ll_off, map_off;       // the locus block in the LL buffer ([P x H]); new_to_old in the map buffer, -1: identity
   int64_t tab_off;               // in the table buffer: hap_to_allele [Hn], allele_first [V + 1], haps_by_allele [Hn] (allele, then haplotype, ascending)
   int64_t gl_off, pgl_off;       // sample 0 of the locus in gls / pls and in phased_gls
-  int32_t r0, r1, H, Hn, V, haploid, n_gl, n_pgl;
-  double hom_gl, het_gl, hom_pgl, het_pgl;   // prior + configuration term of a homozygous / heterozygous cell (genotyper.cpp:204-241; host libm)
+  int32_t r0, r1, H, Hn, V, haploid, n_gl, n_pgl;   // haploid: every sample of the locus is; n_gl / n_pgl: the row widths that follow from it (a mixed locus has the diploid ones)
+  double hom_gl, het_gl, hom_pgl, het_pgl;   // prior + configuration term of a homozygous / heterozygous cell (genotyper.cpp:204-241; host libm), in the flavour of the units that name this record
 };
 // one (locus, sample)
 struct FieldUnit {
   int64_t post_off;              // its [Hn x Hn] block in the posterior buffer of its pass
   int64_t cell_off;              // its [V x V] genotype posteriors in the workspace; -1: they fit LDS
-  int32_t locus, sample, out;    // out: slot in the per-unit outputs
+  int32_t locus, sample, out;    // locus: its record in FieldArgs.loci; out: slot in the per-unit outputs
   int32_t src, pass;             // slot in the total / best-pair buffers of pass 0 (first) or 1 (second)
+  int32_t haploid;               // the sample's ploidy (res->sample_haploid): the flavour of the constants, the index mapping and the strand rule
 };
 struct FieldArgs {
   const FieldUnit* units; const FieldLocus* loci; const int32_t* tab;
@@ -112,6 +114,8 @@ __device__ __forceinline__ void fields_unit(const FieldArgs& A, int unit0, doubl
   const FieldUnit u = A.units[unit0 + (int)blockIdx.x];
   const FieldLocus L = A.loci[u.locus];
   const int tid = threadIdx.x, V = L.V, Hn = L.Hn, VV = V * V, n_gl = L.n_gl;
+  const bool hap = u.haploid != 0;                               // the SAMPLE's ploidy; L.haploid / n_gl / n_pgl are the locus's (row widths)
+  const int n_out = hap ? V : n_gl;                              // values of this sample's gls / pls row: a haploid row of a mixed locus keeps 0 after its V
   const int32_t* __restrict__ h2a = A.tab + L.tab_off;
   const int32_t* __restrict__ afirst = h2a + Hn;
   const int32_t* __restrict__ alist = afirst + V + 1;
@@ -150,9 +154,9 @@ __device__ __forceinline__ void fields_unit(const FieldArgs& A, int unit0, doubl
   const double stl = A.stl[u.pass][u.src];
   double* gls = A.gls + L.gl_off + (int64_t)u.sample * n_gl;
   double my_max = -INFINITY;
-  for (int k = tid; k < n_gl; k += NT) {
+  for (int k = tid; k < n_out; k += NT) {
     int a = k, b = k;
-    if (!L.haploid) {                                            // k = a (a + 1) / 2 + b, b <= a
+    if (!hap) {                                                  // k = a (a + 1) / 2 + b, b <= a
       a = (int)((sqrt(8.0 * k + 1.0) - 1.0) * 0.5);
       while (a * (a + 1) / 2 > k) --a;
       while ((a + 1) * (a + 2) / 2 <= k) ++a;
@@ -165,14 +169,15 @@ __device__ __forceinline__ void fields_unit(const FieldArgs& A, int unit0, doubl
   }
   if (A.pgls) {
     double* __restrict__ pg = A.pgls + L.pgl_off + (int64_t)u.sample * L.n_pgl;
-    for (int k = tid; k < L.n_pgl; k += NT) {
-      const int a = L.haploid ? k : k / V, b = L.haploid ? k : k - a * V;
+    const int n_pout = hap ? (L.haploid ? V : 0) : L.n_pgl;     // a haploid sample of a mixed locus has no phased genotypes: its row stays 0.0
+    for (int k = tid; k < n_pout; k += NT) {
+      const int a = hap ? k : k / V, b = hap ? k : k - a * V;
       pg[k] = (stl - (a == b ? L.hom_pgl : L.het_pgl) + cells[a * V + b]) * LOG_E_BASE_10;
     }
   }
   const double max_gl = block_max<NT>(my_max, s_red, tid);       // (its barriers also publish gls to the workgroup)
   double my_second = -DBL_MAX;
-  for (int k = tid; k < n_gl; k += NT) { const double g = gls[k]; if (g < max_gl && g > my_second) my_second = g; }
+  for (int k = tid; k < n_out; k += NT) { const double g = gls[k]; if (g < max_gl && g > my_second) my_second = g; }
   double second = block_max<NT>(my_second, s_red, tid);
   if (tid == 0) {                                                // calc_gl_diff, :109-130
     double d;
@@ -180,21 +185,21 @@ __device__ __forceinline__ void fields_unit(const FieldArgs& A, int unit0, doubl
     else {
       if (second == -DBL_MAX) second = max_gl;
       const int hi = ga > gb ? ga : gb, lo = ga < gb ? ga : gb;
-      const double gi = gls[L.haploid ? ga : hi * (hi + 1) / 2 + lo];
+      const double gi = gls[hap ? ga : hi * (hi + 1) / 2 + lo];
       d = (fabs(max_gl - gi) < 1e-10) ? (max_gl - second) : gi - max_gl;
     }
     A.scalars[4 * A.nu + u.out] = d;
   }
   if (A.pls) {                                                   // calc_PLs, :102-107
     int32_t* __restrict__ pl = A.pls + L.gl_off + (int64_t)u.sample * n_gl;
-    for (int k = tid; k < n_gl; k += NT) { const int v = (int)(-10 * (gls[k] - max_gl)); pl[k] = v < 999 ? v : 999; }
+    for (int k = tid; k < n_out; k += NT) { const int v = (int)(-10 * (gls[k] - max_gl)); pl[k] = v < 999 ? v : 999; }
   }
   const int32_t* cmap = L.map_off >= 0 ? A.map + L.map_off : nullptr;
   for (int r = L.r0 + tid; r < L.r1; r += NT) {
     if (A.label[r] != u.sample) continue;
     const double p1 = A.lp1[r], p2 = A.lp2[r];
     int strand = 0;
-    if (!L.haploid && ha != hb) {
+    if (!hap && ha != hb) {
       const double* row = A.ll + L.ll_off + (DIRECT ? (int64_t)(r - L.r0) : (int64_t)A.pool_index[r]) * L.H;
       strand = (p1 + ltr_clamped_ll(row, cmap, ha) > p2 + ltr_clamped_ll(row, cmap, hb)) ? 0 : 1;      // :965-967
     }
@@ -227,32 +232,45 @@ void launch_fields(hipStream_t st, const FieldArgs& a, bool direct, size_t n_sma
     hipLaunchKernelGGL(direct ? ltr_ll_fields_kernel<256> : ltr_genotype_fields_kernel<256>, dim3((unsigned)n_large), dim3(256), (size_t)cell_cap_large * sizeof(double), st, a, (int)n_small, log_thresh);
 }
 
-// sizes and offsets of every locus (res->f_V, f_gl_off, f_pgl_off, f_read_off; floci when the kernel will run); the table entries needed
-int64_t layout_loci(const LlSource* src, const ltr_genotype_batch* gb, ltr_genotype_result* res, FieldLocus* floci) {
+// the constants of a record in one flavour: priors (the heterozygous one of a haploid call is 0, genotyper.cpp:210) and
+// configuration terms (:204-241) as ltr_genotype.cpp:108-111
+void set_constants(FieldLocus& F, int haploid) {
+  double hom_prior, het_prior;
+  ltr_log_priors(F.Hn, haploid, &hom_prior, &het_prior);
+  if (haploid) het_prior = 0.0;
+  const double lH = std::log((double)F.Hn), lV = std::log((double)F.V), l2 = std::log(2.0);
+  const double gl_cfg = haploid ? l2 + lH - lV : l2 + 2 * (lH - lV), pgl_cfg = haploid ? lH - lV : 2 * (lH - lV);
+  F.hom_gl = hom_prior + gl_cfg; F.het_gl = het_prior + gl_cfg; F.hom_pgl = hom_prior + pgl_cfg; F.het_pgl = het_prior + pgl_cfg;
+}
+
+// sizes and offsets of every locus (res->f_V, f_gl_off, f_pgl_off, f_read_off; floci when the kernel will run); the table entries needed.
+// floci: [n_loci + mixed loci]; alt[l]: the second record of a mixed locus (the haploid flavour, for its haploid units), -1: none
+int64_t layout_loci(const LlSource* src, const ltr_genotype_batch* gb, ltr_genotype_result* res, FieldLocus* floci, int32_t* alt) {
   const ltr_posterior_batch* pb = gb->pb;
   const int64_t nl = res->n_loci;
   res->f_gl_off.assign((size_t)nl + 1, 0); res->f_pgl_off.assign((size_t)nl + 1, 0);
   res->f_read_off.assign(pb->locus_read_off, pb->locus_read_off + nl + 1);
-  int64_t tab = 0, mo = 0;
+  int64_t tab = 0, mo = 0, n_alt = 0;
   for (int64_t l = 0; l < nl; ++l) {                             // (the block lists are warm from the caller's checks)
     const LtrPruned* p = res->pruned[(size_t)l].get();
     const ltr_haplotype_blocks* hb = p ? &p->blocks.view : gb->haps[l];
     const int32_t S = res->S[(size_t)l], H = res->H[(size_t)l], Hn = p ? p->Hn : H, V = hb->n_alleles[res->f_block[(size_t)l]];
     res->f_V[(size_t)l] = V;
-    if (!floci) continue;
+    if (!floci || !alt) continue;                               // (sizes only: ltr_plan_fields_empty)
     FieldLocus& F = floci[(size_t)l];
     F.ll_off = src->locus_off[l]; F.map_off = p ? mo : -1; F.tab_off = tab;
     F.gl_off = res->f_gl_off[(size_t)l]; F.pgl_off = res->f_pgl_off[(size_t)l];
     const int haploid = res->haploid[(size_t)l];                 // the locus's own (genotyper_bam_processor.cpp:248 -> :294): widths, priors and offsets below follow it
     F.r0 = (int32_t)pb->locus_read_off[l]; F.r1 = (int32_t)pb->locus_read_off[l + 1]; F.H = H; F.Hn = Hn; F.V = V; F.haploid = haploid;
     F.n_gl = haploid ? V : V * (V + 1) / 2; F.n_pgl = haploid ? V : V * V;
-    // priors (the heterozygous one of a haploid call is 0, genotyper.cpp:210) and configuration terms (:204-241) as ltr_genotype.cpp:108-111
-    double hom_prior, het_prior;
-    ltr_log_priors(Hn, haploid, &hom_prior, &het_prior);
-    if (haploid) het_prior = 0.0;
-    const double lH = std::log((double)Hn), lV = std::log((double)V), l2 = std::log(2.0);
-    const double gl_cfg = haploid ? l2 + lH - lV : l2 + 2 * (lH - lV), pgl_cfg = haploid ? lH - lV : 2 * (lH - lV);
-    F.hom_gl = hom_prior + gl_cfg; F.het_gl = het_prior + gl_cfg; F.hom_pgl = hom_prior + pgl_cfg; F.het_pgl = het_prior + pgl_cfg;
+    set_constants(F, haploid);
+    alt[l] = -1;
+    if (res->mixed(l)) {                                         // the same rows and widths, the haploid samples' constants
+      alt[l] = (int32_t)(nl + n_alt);
+      FieldLocus& A = floci[(size_t)(nl + n_alt++)];
+      A = F;
+      set_constants(A, 1);
+    }
     if (p) mo += p->Hn;
     tab += 2 * (int64_t)Hn + V + 1;
     res->f_gl_off[(size_t)l + 1] = F.gl_off + (int64_t)S * F.n_gl;
@@ -286,7 +304,7 @@ bool fill_tables(const ltr_genotype_batch* gb, const ltr_genotype_result* res, c
 
 // units: those of up to kFieldSmallH haplotypes first (one wavefront each), then the others; a V x V table beyond LDS goes to a workspace
 struct UnitLayout { size_t n_small = 0; int64_t ncells = 0; int cap_small = 1, cap_large = 1; };
-UnitLayout layout_field_units(const ltr_genotype_result* res, const FieldLocus* floci, FieldUnit* funits) {
+UnitLayout layout_field_units(const ltr_genotype_result* res, const FieldLocus* floci, const int32_t* alt, FieldUnit* funits) {
   const int64_t nl = res->n_loci;
   UnitLayout L;
   for (int64_t l = 0; l < nl; ++l) if (floci[(size_t)l].Hn <= kFieldSmallH) L.n_small += (size_t)res->S[(size_t)l];
@@ -301,6 +319,8 @@ UnitLayout layout_field_units(const ltr_genotype_result* res, const FieldLocus* 
       FieldUnit& u = funits[small ? ks++ : kl++];
       u.locus = (int32_t)l; u.sample = s; u.out = (int32_t)(res->unit_off[(size_t)l] + s);
       u.pass = p ? 1 : 0; u.src = p ? (int32_t)(unit2 + s) : u.out;
+      u.haploid = res->sample_haploid[(size_t)u.out];
+      if (u.haploid && alt[l] >= 0) u.locus = alt[l];
       u.post_off = (p ? p->post_off : res->post1_off[(size_t)l]) + (int64_t)s * F.Hn * F.Hn;
       if (vv > kFieldCellCap) { u.cell_off = L.ncells; L.ncells += vv; }
       else { u.cell_off = -1; int& cap = small ? L.cap_small : L.cap_large; cap = std::max(cap, (int)vv); }
@@ -313,7 +333,7 @@ UnitLayout layout_field_units(const ltr_genotype_result* res, const FieldLocus* 
 }  // namespace
 
 void ltr_plan_fields_empty(const ltr_genotype_batch* gb, ltr_genotype_result* res) {
-  layout_loci(nullptr, gb, res, nullptr);
+  layout_loci(nullptr, gb, res, nullptr, nullptr);
   res->f_i32.reset(new int32_t[std::max<size_t>((size_t)gb->pb->n_reads, 1)]()); res->f_f64.reset(new double[1]());
 }
 
@@ -322,12 +342,15 @@ int ltr_plan_fields_stage(ltr_ctx* ctx, const LlSource& src, const ltr_genotype_
   hipStream_t st = lease.st;
   const int64_t nl = res->n_loci;
   const size_t nu = (size_t)res->unit_off[(size_t)nl], nr = (size_t)gb->pb->n_reads;
-  FieldLocus* floci = lease.host<FieldLocus>((size_t)nl);
-  const size_t ntab = (size_t)layout_loci(&src, gb, res, floci);
+  size_t n_rec = (size_t)nl;                                     // one record per locus, a second one for a mixed locus
+  for (int64_t l = 0; l < nl; ++l) if (res->mixed(l)) ++n_rec;
+  FieldLocus* floci = lease.host<FieldLocus>(n_rec);
+  int32_t* alt = lease.host<int32_t>((size_t)nl);
+  const size_t ntab = (size_t)layout_loci(&src, gb, res, floci, alt);
   int32_t* ftab = lease.host<int32_t>(ntab);
   if (!fill_tables(gb, res, floci, ftab)) { ltr::set_error(ctx, std::string(src.direct ? "ltr_ll_genotype" : "ltr_plan_genotype_fields") + ": malformed haplotype blocks"); return LTR_ERR_INVALID; }
   FieldUnit* funits = lease.host<FieldUnit>(nu);
-  const UnitLayout ul = layout_field_units(res, floci, funits);
+  const UnitLayout ul = layout_field_units(res, floci, alt, funits);
   const int64_t ngl = res->f_gl_off[(size_t)nl], npgl = res->f_pgl_off[(size_t)nl];
   const size_t ni32 = 6 * nu + nr;
   res->f_i32.reset(new int32_t[ni32]); res->f_f64.reset(new double[5 * nu]);
@@ -337,7 +360,7 @@ int ltr_plan_fields_stage(ltr_ctx* ctx, const LlSource& src, const ltr_genotype_
   FieldUnit* d_funits = nullptr; FieldLocus* d_floci = nullptr; int32_t *d_ftab = nullptr, *d_fi32 = nullptr, *d_fpls = nullptr;
   double *d_ff64 = nullptr, *d_fgls = nullptr, *d_fpgls = nullptr, *d_fcells = nullptr;
   DEV_TRY(ctx, lease.alloc(&d_funits, nu * sizeof(FieldUnit)));
-  DEV_TRY(ctx, lease.alloc(&d_floci, (size_t)nl * sizeof(FieldLocus)));
+  DEV_TRY(ctx, lease.alloc(&d_floci, n_rec * sizeof(FieldLocus)));
   DEV_TRY(ctx, lease.alloc(&d_ftab, ntab * 4));
   DEV_TRY(ctx, lease.alloc(&d_fi32, ni32 * 4));
   DEV_TRY(ctx, lease.alloc(&d_ff64, 5 * nu * 8));
@@ -346,7 +369,7 @@ int ltr_plan_fields_stage(ltr_ctx* ctx, const LlSource& src, const ltr_genotype_
   if (fr->want_phased_gls) DEV_TRY(ctx, lease.alloc(&d_fpgls, (size_t)std::max<int64_t>(npgl, 1) * 8));
   if (ul.ncells) DEV_TRY(ctx, lease.alloc(&d_fcells, (size_t)ul.ncells * 8));
   DEV_TRY(ctx, hipMemcpyAsync(d_funits, funits, nu * sizeof(FieldUnit), hipMemcpyHostToDevice, st));
-  DEV_TRY(ctx, hipMemcpyAsync(d_floci, floci, (size_t)nl * sizeof(FieldLocus), hipMemcpyHostToDevice, st));
+  DEV_TRY(ctx, hipMemcpyAsync(d_floci, floci, n_rec * sizeof(FieldLocus), hipMemcpyHostToDevice, st));
   DEV_TRY(ctx, hipMemcpyAsync(d_ftab, ftab, ntab * 4, hipMemcpyHostToDevice, st));
   // a unit without an optimal pair (best_gts = -1) writes nothing else: its numbers read 0, not what the pool held before
   DEV_TRY(ctx, hipMemsetAsync(d_fi32, 0, 6 * nu * 4, st));
@@ -410,8 +433,10 @@ int ltr_genotype_result_vcf_records(const ltr_genotype_result* r, const ltr_vcf_
     v.hap = ltr_genotype_result_blocks(r, l);                   // the final block list (the pruned copy, or the caller's)
     v.block = r->f_block[(size_t)l];
     v.haploid = r->haploid[(size_t)l];                          // the ploidy the fields were made with: FORMAT and the GL / PL / PHASEDGL widths
+    // a mixed locus (v.haploid = 0: the ten-field form) carries the ploidy of its samples to the writer; every other locus is the per-locus case
+    const uint8_t* sample_haploid = r->mixed(l) ? r->sample_haploid.data() + r->unit_off[(size_t)l] : nullptr;
     int64_t rc = ltr_genotype_result_fields(r, l, &f);
-    if (rc == LTR_OK) rc = ltr::vcf_record_string(&v, &f, opt, &rec[(size_t)l], &rpos[(size_t)l]);
+    if (rc == LTR_OK) rc = ltr::vcf_record_string(&v, &f, opt, &rec[(size_t)l], &rpos[(size_t)l], sample_haploid);
     if (rc < 0) {
       status[(size_t)l] = rc;
       int64_t cur = bad.load();                                  // the first bad locus, whatever the thread count

@@ -246,6 +246,7 @@ struct GtCall {
   std::vector<int64_t> ll_off;                      // ... the locus offsets of that block (src.locus_off)
   PinnedPair stage;                                 // ... its staging
   const uint8_t* locus_haploid;                     // the caller's ploidy per locus; null: pb->haploid for all (resolved into res->haploid by layout_units)
+  const uint8_t* sample_haploid = nullptr;          // ... per (locus, sample) in unit order (ltr_gpu_ploidy.h); null: the locus's (resolved into res->sample_haploid there too)
   std::unique_ptr<ltr_genotype_result> res;
   GtUnit* units = nullptr; size_t nu = 0;           // the first pass's units (ctx->gt_units)
   std::vector<uint8_t> aligned;                     // per unit: one of the sample's reads was aligned (:262-266)
@@ -271,7 +272,7 @@ int layout_units(GtCall& c) {
   res->unit_off.assign((size_t)nl + 1, 0); res->post1_off.assign((size_t)nl + 1, 0);
   res->pruned.resize((size_t)nl); res->n_blocks.assign((size_t)nl, 0);
   res->haploid.assign((size_t)std::max<int64_t>(nl, 0), 0);
-  const LocusPloidy ploidy(pb, c.locus_haploid);
+  const SamplePloidy ploidy(pb, c.locus_haploid, c.sample_haploid);
   std::vector<int64_t> pool_base(src.direct ? 0 : (size_t)nl + 1, 0);   // first pool (= read of the plan) of every locus
   int32_t max_H = 1;
   for (int64_t l = 0; l < nl; ++l) {
@@ -283,9 +284,10 @@ int layout_units(GtCall& c) {
     res->post1_off[(size_t)l + 1] = res->post1_off[(size_t)l] + (int64_t)S * H * H;
     if (!src.direct) pool_base[(size_t)l + 1] = pool_base[(size_t)l] + src.P[l];
     max_H = std::max(max_H, H);
-    res->haploid[(size_t)l] = (uint8_t)ploidy(l);
+    res->haploid[(size_t)l] = (uint8_t)ploidy.all(l, res->unit_off[(size_t)l], S);
   }
   const size_t nu = c.nu = (size_t)res->unit_off[(size_t)nl];
+  res->sample_haploid.assign(nu, 0);
   res->identity.resize((size_t)max_H);
   for (int32_t k = 0; k < max_H; ++k) res->identity[(size_t)k] = k;
   res->stl.assign(nu, 0.0); res->gts.assign(2 * nu, -1);
@@ -330,7 +332,8 @@ int layout_units(GtCall& c) {
       u.ll_off = src.locus_off[l]; u.post_off = res->post1_off[(size_t)l] + (int64_t)s * H * H; u.map_off = -1;
       u.r0 = (int32_t)r0; u.r1 = (int32_t)r1;
       u.H = H; u.Hn = H; u.out = (int32_t)(u0 + s); u.sample = s;
-      ltr_log_priors(H, res->haploid[(size_t)l], &u.homoz, &u.hetz);
+      res->sample_haploid[(size_t)(u0 + s)] = (uint8_t)ploidy(l, u0 + s);
+      ltr_log_priors(H, res->sample_haploid[(size_t)(u0 + s)], &u.homoz, &u.hetz);   // the priors of a unit follow its sample
     }
   });
   if (bad_haps.load() >= 0) {
@@ -428,7 +431,7 @@ int prune_uncalled(GtCall& c) {
     for (int32_t s = 0; s < S; ++s) {
       GtUnit u = c.units[(size_t)(res->unit_off[(size_t)l] + s)];
       u.post_off = c.npost2 + (int64_t)s * p->Hn * p->Hn; u.map_off = map_off; u.Hn = p->Hn; u.out = (int32_t)c.units2.size();
-      ltr_log_priors(p->Hn, res->haploid[(size_t)l], &u.homoz, &u.hetz);   // :405-408: priors of the new number of haplotypes, the locus's ploidy
+      ltr_log_priors(p->Hn, res->sample_haploid[(size_t)(res->unit_off[(size_t)l] + s)], &u.homoz, &u.hetz);   // :405-408: priors of the new number of haplotypes, the sample's ploidy
       c.units2.push_back(u);
     }
     c.npost2 += (int64_t)S * p->Hn * p->Hn;
@@ -580,7 +583,8 @@ int genotype_stages(GtCall& c, const ltr_ll_batch* lb, ltr_genotype_result** out
 }  // namespace
 
 // ltr_plan_genotype (fr == null), ltr_plan_genotype_fields and ltr_plan_genotype_ploidy: the stages on the LL buffer of the plan's last execute
-static int plan_genotype(ltr_plan* plan, const ltr_genotype_batch* gb, const ltr_fields_request* fr, const uint8_t* locus_haploid, ltr_genotype_result** out) {
+static int plan_genotype(ltr_plan* plan, const ltr_genotype_batch* gb, const ltr_fields_request* fr, const uint8_t* locus_haploid, const uint8_t* sample_haploid,
+                         ltr_genotype_result** out) {
   if (out) *out = nullptr;
   if (!plan || !gb || !gb->pb || !out) return LTR_ERR_INVALID;
   ltr_ctx* ctx = plan->ctx;
@@ -601,6 +605,7 @@ static int plan_genotype(ltr_plan* plan, const ltr_genotype_batch* gb, const ltr
   src.base = plan->last_out; src.locus_off = plan->locus_ll_off.data(); src.H = plan->locus_H.data(); src.P = plan->locus_P.data();
   src.pool_seed = plan->seed.data();
   GtCall c(ctx, plan->last_stream, src, gb, fr, locus_haploid);
+  c.sample_haploid = sample_haploid;
   return genotype_stages(c, nullptr, out);
   LTR_GUARD_END(ctx)
 }
@@ -609,7 +614,11 @@ extern "C" {
 
 // the ploidy per locus (genotyper_bam_processor.cpp:248 -> :294); the two entry points below are this one with locus_haploid = null
 int ltr_plan_genotype_ploidy(ltr_plan* plan, const ltr_genotype_batch* gb, const ltr_fields_request* fr, const uint8_t* locus_haploid, ltr_genotype_result** out) {
-  return plan_genotype(plan, gb, fr, locus_haploid, out);
+  return plan_genotype(plan, gb, fr, locus_haploid, nullptr, out);
+}
+// ... per (locus, sample) (ltr_gpu_ploidy.h)
+int ltr_plan_genotype_sample_ploidy(ltr_plan* plan, const ltr_genotype_batch* gb, const ltr_fields_request* fr, const uint8_t* sample_haploid, ltr_genotype_result** out) {
+  return plan_genotype(plan, gb, fr, nullptr, sample_haploid, out);
 }
 int ltr_plan_genotype(ltr_plan* plan, const ltr_genotype_batch* gb, ltr_genotype_result** out) { return ltr_plan_genotype_ploidy(plan, gb, nullptr, nullptr, out); }
 int ltr_plan_genotype_fields(ltr_plan* plan, const ltr_genotype_batch* gb, const ltr_fields_request* fr, ltr_genotype_result** out) {
@@ -618,8 +627,8 @@ int ltr_plan_genotype_fields(ltr_plan* plan, const ltr_genotype_batch* gb, const
   return ltr_plan_genotype_ploidy(plan, gb, fr, nullptr, out);
 }
 
-int ltr_ll_genotype_ploidy(ltr_ctx* ctx, const ltr_ll_batch* lb, const ltr_genotype_batch* gb, const ltr_fields_request* fr, const uint8_t* locus_haploid,
-                           ltr_genotype_result** out) {
+static int ll_genotype(ltr_ctx* ctx, const ltr_ll_batch* lb, const ltr_genotype_batch* gb, const ltr_fields_request* fr, const uint8_t* locus_haploid,
+                       const uint8_t* sample_haploid, ltr_genotype_result** out) {
   if (out) *out = nullptr;
   if (!ctx || !lb || !gb || !gb->pb || !out) return LTR_ERR_INVALID;
   const ltr_posterior_batch* pb = gb->pb;
@@ -639,6 +648,7 @@ int ltr_ll_genotype_ploidy(ltr_ctx* ctx, const ltr_ll_batch* lb, const ltr_genot
   LlSource src;
   src.direct = true; src.H = lb->n_haps; src.read_seed = lb->seed_positions; src.who = "ltr_ll_genotype";
   GtCall c(ctx, ctx->stream, src, gb, fr, locus_haploid);
+  c.sample_haploid = sample_haploid;
   c.ll_off.assign((size_t)nl + 1, 0);                          // the blocks back to back, [R_l x H_l] each
   for (int64_t l = 0; l < nl; ++l) {
     const int64_t r0 = pb->locus_read_off[l], r1 = pb->locus_read_off[l + 1];
@@ -652,6 +662,14 @@ int ltr_ll_genotype_ploidy(ltr_ctx* ctx, const ltr_ll_batch* lb, const ltr_genot
   return genotype_stages(c, lb, out);
   LTR_GUARD_END(ctx)
 }
+int ltr_ll_genotype_ploidy(ltr_ctx* ctx, const ltr_ll_batch* lb, const ltr_genotype_batch* gb, const ltr_fields_request* fr, const uint8_t* locus_haploid,
+                           ltr_genotype_result** out) {
+  return ll_genotype(ctx, lb, gb, fr, locus_haploid, nullptr, out);
+}
+int ltr_ll_genotype_sample_ploidy(ltr_ctx* ctx, const ltr_ll_batch* lb, const ltr_genotype_batch* gb, const ltr_fields_request* fr, const uint8_t* sample_haploid,
+                                  ltr_genotype_result** out) {
+  return ll_genotype(ctx, lb, gb, fr, nullptr, sample_haploid, out);
+}
 int ltr_ll_genotype(ltr_ctx* ctx, const ltr_ll_batch* lb, const ltr_genotype_batch* gb, const ltr_fields_request* fr, ltr_genotype_result** out) {
   return ltr_ll_genotype_ploidy(ctx, lb, gb, fr, nullptr, out);
 }
@@ -663,6 +681,11 @@ int64_t ltr_genotype_result_n_loci(const ltr_genotype_result* r) { return r ? r-
 int32_t ltr_genotype_result_haploid(const ltr_genotype_result* r, int64_t l) {
   GT_LOCUS(r, l, LTR_ERR_INVALID);
   return r->haploid[(size_t)l] ? 1 : 0;
+}
+int32_t ltr_genotype_result_sample_haploid(const ltr_genotype_result* r, int64_t l, int32_t s) {
+  GT_LOCUS(r, l, LTR_ERR_INVALID);
+  if (s < 0 || s >= r->S[(size_t)l]) return LTR_ERR_INVALID;
+  return r->sample_haploid[(size_t)(r->unit_off[(size_t)l] + s)] ? 1 : 0;
 }
 int32_t ltr_genotype_result_n_haps(const ltr_genotype_result* r, int64_t l) {
   GT_LOCUS(r, l, LTR_ERR_INVALID);

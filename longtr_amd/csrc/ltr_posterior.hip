@@ -156,7 +156,8 @@ int ltr_posteriors(ltr_ctx* ctx, int32_t S, int32_t R, int32_t H,
 // Genotyper::calc_log_sample_posteriors + get_optimal_haplotypes for EVERY locus of a resident
 // plan, straight from the LL buffer of the last execute (no host round trip of the LL matrix).
 // locus_haploid: the ploidy of every locus (genotyper_bam_processor.cpp:248 -> :294 -> the priors, genotyper.cpp:21-33); null = pb->haploid.
-int ltr_plan_posteriors_ploidy(ltr_plan* plan, const ltr_posterior_batch* pb, const uint8_t* locus_haploid, double* post, double* sample_total_ll, int32_t* gts) {
+// sample_haploid: the ploidy of every (locus, sample) in unit order (ltr_gpu_ploidy.h); null = the locus's.  Only the priors of a unit read it.
+static int plan_posteriors(ltr_plan* plan, const ltr_posterior_batch* pb, const uint8_t* locus_haploid, const uint8_t* sample_haploid, double* post, double* sample_total_ll, int32_t* gts) {
   if (!plan || !pb || !post || !sample_total_ll) return LTR_ERR_INVALID;
   ltr_ctx* ctx = plan->ctx;
   if (!ctx) return LTR_ERR_INVALID;                          // the context was destroyed before this plan
@@ -167,7 +168,7 @@ int ltr_plan_posteriors_ploidy(ltr_plan* plan, const ltr_posterior_batch* pb, co
   LTR_GUARD_BEGIN
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   std::vector<PostUnit> units;                                 // (before the lease: a queued copy reads it)
-  const LocusPloidy haploid(pb, locus_haploid);
+  const SamplePloidy haploid(pb, locus_haploid, sample_haploid);
   int64_t post_off = 0;
   for (int64_t l = 0; l < pb->n_loci; ++l) {
     const int64_t r0 = pb->locus_read_off[l], r1 = pb->locus_read_off[l + 1];
@@ -180,7 +181,7 @@ int ltr_plan_posteriors_ploidy(ltr_plan* plan, const ltr_posterior_batch* pb, co
     for (int32_t sm = 0; sm < S; ++sm) {
       PostUnit u;
       u.ll_off = plan->locus_ll_off[(size_t)l]; u.post_off = post_off; u.r0 = (int32_t)r0; u.r1 = (int32_t)r1; u.H = H; u.sample = sm;
-      ltr_log_priors(H, haploid(l), &u.homoz, &u.hetz);
+      ltr_log_priors(H, haploid(l, (int64_t)units.size()), &u.homoz, &u.hetz);
       units.push_back(u);
       post_off += (int64_t)H * H;
     }
@@ -210,8 +211,14 @@ int ltr_plan_posteriors_ploidy(ltr_plan* plan, const ltr_posterior_batch* pb, co
   return LTR_OK;
   LTR_GUARD_END(ctx)
 }
+int ltr_plan_posteriors_ploidy(ltr_plan* plan, const ltr_posterior_batch* pb, const uint8_t* locus_haploid, double* post, double* sample_total_ll, int32_t* gts) {
+  return plan_posteriors(plan, pb, locus_haploid, nullptr, post, sample_total_ll, gts);
+}
 int ltr_plan_posteriors(ltr_plan* plan, const ltr_posterior_batch* pb, double* post, double* sample_total_ll, int32_t* gts) {
   return ltr_plan_posteriors_ploidy(plan, pb, nullptr, post, sample_total_ll, gts);
+}
+int ltr_plan_posteriors_sample_ploidy(ltr_plan* plan, const ltr_posterior_batch* pb, const uint8_t* sample_haploid, double* post, double* sample_total_ll, int32_t* gts) {
+  return plan_posteriors(plan, pb, nullptr, sample_haploid, post, sample_total_ll, gts);
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 #include <cmath>
 
 #include "ltr_ctx.h"
+#include "../../include/ltr_gpu_ploidy.h"
 
 // int_log(v) == log(v) (mathops.cpp:14-22); priors of genotyper.cpp:21-33 (host libm)
 inline void ltr_log_priors(int32_t H, int haploid, double* homoz, double* hetz) {
@@ -21,6 +22,19 @@ struct LocusPloidy {
   const uint8_t* per_locus; int batch;
   LocusPloidy(const ltr_posterior_batch* pb, const uint8_t* locus_haploid) : per_locus(locus_haploid), batch(locus_haploid ? 0 : (pb->haploid ? 1 : 0)) {}
   int operator()(int64_t l) const { return per_locus ? (per_locus[l] ? 1 : 0) : batch; }
+};
+// ... and of every (locus, sample) (ltr_gpu_ploidy.h): the caller's array in unit order, or null = the locus's own for each of its
+// samples.  all(l, u0, S): what stays per locus -- 1 exactly when every sample of the locus is haploid (a locus without a sample
+// keeps the locus's own).
+struct SamplePloidy {
+  const uint8_t* per_unit; LocusPloidy locus;
+  SamplePloidy(const ltr_posterior_batch* pb, const uint8_t* locus_haploid, const uint8_t* sample_haploid) : per_unit(sample_haploid), locus(pb, locus_haploid) {}
+  int operator()(int64_t l, int64_t unit) const { return per_unit ? (per_unit[unit] ? 1 : 0) : locus(l); }
+  int all(int64_t l, int64_t u0, int32_t S) const {
+    if (!per_unit || S <= 0) return locus(l);
+    for (int32_t s = 0; s < S; ++s) if (!per_unit[u0 + s]) return 0;
+    return 1;
+  }
 };
 
 // column a of a read's row in the final haplotype order (cmap: new_to_old, null = identity), clamped

@@ -429,7 +429,9 @@ void ltr_vcf_field_set_free(ltr_vcf_field_set* f) { delete f; }
 
 // The text half of write_vcf_record (:894-913, :1045-1366) for one repeat block of one locus: CHROM .. FORMAT and one column
 // per requested sample, from the fields.  Returns the length of the text written to `out` (no trailing newline) or < 0.
-static int64_t record_text(const ltr_vcf_locus* v, const ltr_locus_fields* f, const ltr_vcf_options* opt_in, std::string* text_out, int32_t* pos_out) {
+// sample_haploid: null, or for a diploid-form locus the ploidy of each sample (a mixed locus of ltr_genotype_result_vcf_records).
+static int64_t record_text(const ltr_vcf_locus* v, const ltr_locus_fields* f, const ltr_vcf_options* opt_in, std::string* text_out, int32_t* pos_out,
+                           const uint8_t* sample_haploid = nullptr) {
   if (!v || !f || !v->hap || !text_out || v->n_reads < 0 || v->n_samples <= 0 || v->block < 0 || v->block >= v->hap->n_blocks) return LTR_ERR_INVALID;
   if (!v->sample_label || !v->chrom || !v->sample_names) return LTR_ERR_INVALID;
   if (f->S != v->n_samples || f->R != v->n_reads || f->V != v->hap->n_alleles[v->block]) return LTR_ERR_INVALID;
@@ -442,6 +444,8 @@ static int64_t record_text(const ltr_vcf_locus* v, const ltr_locus_fields* f, co
     const int S = v->n_samples, R = v->n_reads, V = f->V;
     const int n_gl = haploid ? V : V * (V + 1) / 2, n_pgl = haploid ? V : V * V;
     if (f->n_gl != n_gl || f->n_pgl != n_pgl) return LTR_ERR_INVALID;
+    if (haploid) sample_haploid = nullptr;                      // (the six-field form has no other kind of sample)
+    auto one_copy = [&](int s) { return sample_haploid ? sample_haploid[s] != 0 : haploid; };   // the sample's own ploidy
     if ((opt.output_gls && !f->gls) || (opt.output_pls && !f->pls) || (!haploid && opt.output_phased_gls && !f->phased_gls)) return LTR_ERR_INVALID;
     for (int s = 0; s < 2 * S; ++s) if (f->best_gts[s] < 0 || f->best_gts[s] >= V) return LTR_ERR_INVALID;
     for (int r = 0; r < R; ++r) if (f->read_allele[r] < 0 || f->read_allele[r] >= V || v->sample_label[r] < 0 || v->sample_label[r] >= S) return LTR_ERR_INVALID;
@@ -486,7 +490,7 @@ static int64_t record_text(const ltr_vcf_locus* v, const ltr_locus_fields* f, co
       if (!wanted.count(v->sample_names[s]) || n_aligned[(size_t)s] == 0) continue;
       if (n_flank[(size_t)s] > opt.max_flank_indel_frac * n_aligned[(size_t)s]) { ++filt; continue; }
       if (!filtered(s)) {
-        if (haploid) { counts[(size_t)gts[2 * (size_t)s]]++; an += 1; }
+        if (one_copy(s)) { counts[(size_t)gts[2 * (size_t)s]]++; an += 1; }
         else { counts[(size_t)gts[2 * (size_t)s]]++; counts[(size_t)gts[2 * (size_t)s + 1]]++; an += 2; }
       } else ++skip;
     }
@@ -540,7 +544,11 @@ static int64_t record_text(const ltr_vcf_locus* v, const ltr_locus_fields* f, co
       if (filtered(s)) { o << (opt.output_filters ? empty + v->sample_filter[s] : std::string(".")); continue; }
       if (n_flank[(size_t)s] > n_aligned[(size_t)s] * opt.max_flank_indel_frac) { o << (opt.output_filters ? empty + "FLANK_INDEL_FRAC" : std::string(".")); continue; }
       const int g1 = gts[2 * (size_t)s], g2 = gts[2 * (size_t)s + 1];
-      if (!haploid) {
+      const bool one = one_copy(s);
+      if (one && !haploid) {                                    // a haploid sample in the ten-field form: "." in PQ, DSNP, PDP, PSNP
+        o << o2n[(size_t)g1] << ":" << bp_diffs[(size_t)g1] << ":" << std::exp(lunphased[(size_t)s]) << ":." << ":" << n_aligned[(size_t)s]
+          << ":." << ":" << n_flank[(size_t)s] << ":.:.";
+      } else if (!haploid) {
         o << o2n[(size_t)g1] << "|" << o2n[(size_t)g2] << ":" << bp_diffs[(size_t)g1] << "|" << bp_diffs[(size_t)g2]
           << ":" << std::exp(lunphased[(size_t)s]) << ":" << std::exp(lphased[(size_t)s])
           << ":" << n_aligned[(size_t)s] << ":" << n_snp[(size_t)s] << ":" << n_flank[(size_t)s]
@@ -554,9 +562,10 @@ static int64_t record_text(const ltr_vcf_locus* v, const ltr_locus_fields* f, co
       if (opt.output_mallreads) o << ":" << condense(ml_bps[(size_t)s]);
       const double* gl = f->gls ? f->gls + (size_t)s * n_gl : nullptr;
       const int32_t* pl = f->pls ? f->pls + (size_t)s * n_gl : nullptr;
-      if (haploid) {
+      if (one) {                                                // V values (entries 0..V-1 of the row, whatever its width)
         if (opt.output_gls) { o << ":" << gl[0]; for (int a = 1; a < V; ++a) o << "," << gl[n2o[(size_t)a]]; }
         if (opt.output_pls) { o << ":" << pl[0]; for (int a = 1; a < V; ++a) o << "," << pl[n2o[(size_t)a]]; }
+        if (!haploid && opt.output_phased_gls) o << ":.";
       } else {
         auto tri = [&](int a, int b) { const int lo = std::min(n2o[(size_t)a], n2o[(size_t)b]), hi = std::max(n2o[(size_t)a], n2o[(size_t)b]); return hi * (hi + 1) / 2 + lo; };
         if (opt.output_gls) { o << ":" << gl[0]; for (int a = 1; a < V; ++a) for (int b = 0; b <= a; ++b) o << "," << gl[tri(a, b)]; }
@@ -606,8 +615,9 @@ void ltr_vcf_text_free(char* text) { std::free(text); }
 }  // extern "C"
 
 namespace ltr {
-int64_t vcf_record_string(const ltr_vcf_locus* v, const ltr_locus_fields* f, const ltr_vcf_options* opt, std::string* text, int32_t* pos) {
-  return record_text(v, f, opt, text, pos);
+int64_t vcf_record_string(const ltr_vcf_locus* v, const ltr_locus_fields* f, const ltr_vcf_options* opt, std::string* text, int32_t* pos,
+                          const uint8_t* sample_haploid) {
+  return record_text(v, f, opt, text, pos, sample_haploid);
 }
 }  // namespace ltr
 
