@@ -710,11 +710,12 @@ SIGNATURES = {
     "ltr_hap_result_medoid_kept": (_i32, [_vp, _i32]),
 }
 
-# The test hooks the library exports without declaring them in the public header (csrc/ltr_plan.h, csrc/ltr_internal.h).
+# The test hooks the library exports without declaring them in the public header (csrc/ltr_plan.h, csrc/ltr_internal.h, csrc/ltr_short.h).
 HOOK_SIGNATURES = {
     "ltr_debug_describe_batch": (_int, [_P(AlignParams), _int, _int, _P(LocusBatch), _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _str, _int]),
     "ltr_debug_threshold_groups": (_int, [_vp, _int, _int, _vp, _vp, _vp]),
     "ltr_debug_plan_schedule": (_int, [_P(AlignParams), _int, _int, _P(LocusBatch), _vp, _vp, _vp, _vp, _int, _vp, _vp, _int, _vp, _int, _vp]),
+    "ltr_debug_short_geometry": (_int, [_i32, _i32, _i32, _i32, _i32, _vp]),
     "ltr_debug_plan_families": (_int, [_P(AlignParams), _int, _int, _P(LocusBatch), _vp, _vp, _int, _vp, _vp, _int, _vp, _vp]),
     "ltr_debug_plan_family_forks": (_int, [_P(AlignParams), _int, _int, _P(LocusBatch), _vp, _vp, _int, _vp, _vp, _int, _vp, _vp, _vp]),
     "ltr_debug_chunk_plan": (_int, [_i64, _f64, _vp, _int, _vp, _int, _vp]),

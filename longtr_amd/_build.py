@@ -7,7 +7,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("LTR_GPU_LIB") or os.path.join(CSRC, "libltr_gpu.so")   # override: A/B builds only
 KERNEL_TUS = ["ltr_k_one.hip", "ltr_k_pack.hip", "ltr_k_plan.hip", "ltr_k_wg.hip", "ltr_k_wgt.hip", "ltr_k_exact.hip", "ltr_k_family.hip"]      # one family of DP kernels each
 PLAN_UNITS = ["ltr_plan_rules.cpp", "ltr_plan_sort.cpp", "ltr_plan_families.cpp", "ltr_plan_describe.cpp", "ltr_plan_schedule.cpp", "ltr_plan_hooks.cpp"]      # host-side planning (csrc/ltr_plan.h)
-SOURCES = ["ltr_ctx.hip", "ltr_plan_build.hip", "ltr_plan_run.hip", "ltr_posterior.hip", "ltr_plan_genotype.hip", "ltr_plan_fields.hip"] + KERNEL_TUS + ["ltr_short.hip", "ltr_nw.hip"] + PLAN_UNITS + ["ltr_host.cpp", "ltr_hap_aln.cpp", "ltr_genotype.cpp", "ltr_vcf.cpp", "ltr_prep.cpp", "ltr_io.cpp", "ltr_bam.cpp", "ltr_vcf_in.cpp", "ltr_editdist.hip", "ltr_poa.hip", "ltr_cluster.cpp"]
+SOURCES = ["ltr_ctx.hip", "ltr_plan_build.hip", "ltr_plan_run.hip", "ltr_posterior.hip", "ltr_plan_genotype.hip", "ltr_plan_fields.hip"] + KERNEL_TUS + ["ltr_short.hip", "ltr_short_batch.cpp", "ltr_nw.hip"] + PLAN_UNITS + ["ltr_host.cpp", "ltr_hap_aln.cpp", "ltr_genotype.cpp", "ltr_vcf.cpp", "ltr_prep.cpp", "ltr_io.cpp", "ltr_bam.cpp", "ltr_vcf_in.cpp", "ltr_editdist.hip", "ltr_poa.hip", "ltr_cluster.cpp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-honor-nans", "-std=c++17", "-fPIC", "-shared", "-pthread", "-Wall"]
 PUBLIC_HEADERS = ["ltr_gpu.h", "ltr_gpu_ploidy.h"]           # include/: what the sources are built against (ltr_filter.h is the filter library's)
 LINK_LIBS = ["-lz"]                                         # BGZF blocks (ltr_bgzf.h: BAM, VCF writer, tabix-indexed VCF input)

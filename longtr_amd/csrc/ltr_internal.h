@@ -284,7 +284,8 @@ int process_reads_short(ltr_ctx* ctx, const ltr_haplotype_blocks* hap, const uin
 
 // The same in two halves, for many loci in one launch (ltr_calc_hap_aln_probs): add() prepares a
 // locus on the host (and writes its seeds / all-zero rows at once), run() scores everything queued.
-// aln_probs passed to add() must stay valid until run().
+// aln_probs passed to add() must stay valid until run().  (new / add / merge / free: ltr_short_batch.cpp, host code; run:
+// ltr_short.hip; the struct: ltr_short.h)
 struct ShortBatch;
 ShortBatch* short_batch_new();
 void short_batch_free(ShortBatch* b);

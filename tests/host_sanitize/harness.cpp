@@ -1,5 +1,6 @@
 // tests/host_sanitize/harness.cpp -- TEST INFRASTRUCTURE.
-// Fuzzes the host-only entry points of the C-ABI library (ltr_host.cpp, ltr_hap_aln.cpp, ltr_genotype.cpp, the planning units of ltr_plan_*.cpp) under
+// Fuzzes the host-only entry points of the C-ABI library (ltr_host.cpp, ltr_hap_aln.cpp, ltr_genotype.cpp, the planning units of ltr_plan_*.cpp, the
+// seeded path's batch builder ltr_short_batch.cpp) under
 // AddressSanitizer + UBSan on the CPU: trimming, haplotype enumeration, pooling, scatter, genotype
 // fields, and ltr_process_reads' host half (trim + haplotype strings) up to the point where it
 // would hand the batch to the GPU.  The four library-internal symbols those files need from the HIP
@@ -20,8 +21,10 @@
 
 #include "../../longtr_amd/csrc/ltr_internal.h"
 #include "../../longtr_amd/csrc/ltr_plan.h"
+#include "../../longtr_amd/csrc/ltr_short.h"
 
-struct ltr_ctx { ltr_align_params p; std::string err; std::vector<uint8_t> host_bytes[4]; std::mutex call_mu, err_mu; ltr::DebugKnobs knobs; bool fake_device = false; };
+struct ltr_ctx { ltr_align_params p; std::string err; std::vector<uint8_t> host_bytes[4]; std::mutex call_mu, err_mu; ltr::DebugKnobs knobs; bool fake_device = false;
+                 ltr_stutter_params stutter = {0.95, 0.05, 0.05, 0.95, 0.01, 0.01}; };    // (the library's defaults, ltr_default_stutter_params)
 struct ltr_plan { int64_t ll_size = 0, pairs = 0; std::vector<double> ll; };   // (the fake device's plan: its "scores")
 namespace ltr {
 std::atomic<int> g_trace{0};                                      // (the trace switch and its clock live with the context, ltr_ctx.hip)
@@ -33,15 +36,59 @@ void add_time(ltr_ctx*, int, double, double) {}
 void* ctx_side_stream(const ltr_ctx*, int) { return nullptr; }
 std::unique_lock<std::mutex> ctx_call_lock(ltr_ctx* ctx) { return std::unique_lock<std::mutex>(ctx->call_mu); }
 uint8_t* ctx_host_bytes(ltr_ctx* ctx, int which, size_t bytes) { ctx->host_bytes[which & 3].resize(bytes); return ctx->host_bytes[which & 3].data(); }
-int process_reads_short(ltr_ctx*, const ltr_haplotype_blocks*, const uint8_t*, const ltr_alignment*, int32_t, int32_t,
-                        const uint8_t*, double*, int32_t*) { return LTR_ERR_NO_DEVICE; }
-struct ShortBatch { int n = 0; };
-ShortBatch* short_batch_new() { return new ShortBatch(); }
-void short_batch_free(ShortBatch* b) { delete b; }
-int short_batch_add(ltr_ctx*, ShortBatch* b, const ltr_haplotype_blocks*, const uint8_t*, const ltr_alignment*, int32_t, int32_t,
-                    const uint8_t*, double*, int32_t*) { b->n++; return LTR_OK; }
-int short_batch_merge(ltr_ctx*, ShortBatch* dst, ShortBatch* src) { dst->n += src->n; src->n = 0; return LTR_OK; }
-int short_batch_run(ltr_ctx*, ShortBatch*) { return LTR_ERR_NO_DEVICE; }
+ltr_stutter_params ctx_stutter_params(const ltr_ctx* ctx) { return ctx->stutter; }
+// The seeded path: the batch builder is the library's (ltr_short_batch.cpp); the two functions of ltr_short.hip are defined here.
+// On a fake device a batch "runs" like a plan does below: pair by pair, every offset a kernel follows is followed over the extent
+// the kernel reads (checked against the array it points into: a vector's spare capacity hides an overrun from ASan), and the
+// pair's score is a checksum of what was read there, stored where the pair's result goes.
+int short_batch_run(ltr_ctx* ctx, ShortBatch* B) {
+  if (!ctx->fake_device) return LTR_ERR_NO_DEVICE;
+  auto bad = [&](const char* what) { set_error(ctx, std::string("fake short_batch_run: ") + what); return LTR_ERR_INVALID; };
+  auto in = [](int64_t off, int64_t n, size_t size) { return off >= 0 && n >= 0 && (uint64_t)off + (uint64_t)n <= size; };
+  if (B->phap.size() != B->pread.size() || B->pdst.size() != B->pread.size() || B->rv.size() != B->fw.size() || B->art.size() != B->fw.size() * kNumArt) return bad("array sizes");
+  // (the prep kernel WRITES wrong / correct at q_off and cum at cum_off, read by read: no two reads may share a slot there, and
+  // nothing here reads those arrays -- so: the reads lie back to back, as the builder lays them out)
+  int64_t rb = 0, qo = 0, co = 0;
+  for (const ShortRead& rd : B->reads) {
+    if (rd.seq_off != rb || rd.q_off != qo || rd.cum_off != co || rd.len < 3 || rd.seed < 1 || rd.seed > rd.len - 2) return bad("reads not back to back");
+    rb += (int64_t)rd.len + (rd.len - 1 - rd.seed); qo += rd.len; co += (int64_t)rd.len + 1;
+  }
+  if (rb != (int64_t)B->rbytes.size() || qo != (int64_t)B->qidx.size() || co != B->n_cum) return bad("read arrays longer than the reads");
+  for (size_t q = 0; q < B->pread.size(); ++q) {
+    if (!in(B->pread[q], 1, B->reads.size()) || !in(B->phap[q], 1, B->fw.size())) return bad("pair index");
+    const ShortRead& rd = B->reads[(size_t)B->pread[q]];
+    const int len = rd.len, seed = rd.seed, rlen = len - 1 - seed;
+    if (seed < 1 || rlen < 1 || std::max(seed, rlen) > B->maxS) return bad("seed");
+    if (rd.rev_off != rd.seq_off + len || !in(rd.seq_off, (int64_t)len + rlen, B->rbytes.size())) return bad("read bytes");
+    if (!in(rd.q_off, len, B->qidx.size()) || !in(rd.cum_off, (int64_t)len + 1, (size_t)B->n_cum)) return bad("quality offsets");
+    uint64_t s = 0;
+    for (int j = 0; j < len + rlen; ++j) s = s * 31 + B->rbytes[(size_t)rd.seq_off + j];
+    for (int j = 0; j < rlen; ++j) if (B->rbytes[(size_t)rd.rev_off + j] != B->rbytes[(size_t)rd.seq_off + len - 1 - j]) return bad("reversed read half");
+    for (int j = 0; j < len; ++j) { const uint8_t k = B->qidx[(size_t)rd.q_off + j]; if (k > 'J' - '!') return bad("quality index"); s = s * 31 + k; }
+    const ShortHap* dir[2] = {&B->fw[(size_t)B->phap[q]], &B->rv[(size_t)B->phap[q]]};
+    for (const ShortHap* h : dir) {
+      const int64_t hs = (int64_t)h->len[0] + h->len[1] + h->len[2];
+      if (h->len[0] < 1 || h->len[1] < 0 || h->len[2] < 1 || hs > B->maxHS || h->len[1] > B->maxB || !in(h->seq_off, hs, B->hbytes.size())) return bad("haplotype bytes");
+      if (h->num_deletions < 0 || h->num_deletions > kMaxDel || h->num_deletions * B->period > h->len[1]) return bad("num_deletions");
+      const int64_t nup = (int64_t)std::max(h->num_deletions, 1) * std::max(h->len[1], 1);
+      if (!in(h->up_off, nup, B->upstream.size())) return bad("upstream tables");
+      for (int64_t j = 0; j < hs; ++j) s = s * 31 + B->hbytes[(size_t)(h->seq_off + j)];
+      for (int64_t j = 0; j < nup; ++j) { const int32_t u = B->upstream[(size_t)(h->up_off + j)]; if (u < 0 || u > h->len[1]) return bad("upstream match length"); s = s * 31 + (uint64_t)u; }
+    }
+    const int64_t hs = (int64_t)dir[0]->len[0] + dir[0]->len[1] + dir[0]->len[2];
+    for (int64_t j = 0; j < hs; ++j) if (B->hbytes[(size_t)(dir[1]->seq_off + j)] != B->hbytes[(size_t)(dir[0]->seq_off + hs - 1 - j)]) return bad("reversed haplotype");
+    for (int a = 0; a < kNumArt; ++a) s = s * 31 + (uint64_t)(int64_t)(B->art[(size_t)B->phap[q] * kNumArt + a] * 1000.0);
+    *B->pdst[q] = -1.0 - (double)(s % 100000);
+  }
+  return LTR_OK;
+}
+int process_reads_short(ltr_ctx* ctx, const ltr_haplotype_blocks* hap, const uint8_t* realign_to_hap, const ltr_alignment* alns, int32_t n_alns,
+                        int32_t init_read_index, const uint8_t* realign_read, double* aln_probs, int32_t* seed_positions) {
+  ShortBatch B;                                                    // (as ltr_short.hip has it)
+  int rc = short_batch_add(ctx, &B, hap, realign_to_hap, alns, n_alns, init_read_index, realign_read, aln_probs, seed_positions);
+  if (rc == LTR_OK) rc = short_batch_run(ctx, &B);
+  return rc;
+}
 }
 namespace ltrp {                                                   // (no page-locked memory without a device: RawBuf falls back to malloc)
 void* pinned_alloc(size_t) { return nullptr; }
@@ -90,13 +137,17 @@ static int touch_batch(const ltr_locus_batch* b) {
 static std::mt19937_64 rng(20250225);
 static int ri(int lo, int hi) { return lo + (int)(rng() % (uint64_t)(hi - lo + 1)); }
 static std::string rseq(int n) { std::string s((size_t)n, 'A'); for (auto& c : s) c = "ACGT"[rng() & 3]; return s; }
+static std::string rhomo(int n) { std::string s((size_t)n, 'A'); for (auto& c : s) if (rng() % 8 == 0) c = "CGT"[rng() % 3]; return s; }   // a homopolymer run with a few interruptions
+static std::string rqual(int n) { std::string s((size_t)n, '5'); for (auto& c : s) c = (char)ri(20, 90); return s; }     // Phred+33, with bytes below '!' (33) and above 'J' (74)
 
 // Loci for ltr_calc_hap_aln_probs: [flank][repeat][flank] blocks of block_len bp with up to max_alleles repeat alleles, n_reads
 // reads of up to read_len bases (dup_reads: a later read is a copy of the first every other time, so that reads pool) placed
 // start_off around the first block; masks: every few loci carry second_mate (never at read 0), realign_to_hap, realign_pool or copy_read.
-struct LocSpec { int block_len[2], max_alleles, n_reads[2], read_len, start_off[2]; bool dup_reads, masks; };
+// seeded: loci for the seeded stutter path -- the repeat has period 1 and homopolymer alleles of 0 .. 30 bases (every fourth locus
+// has an EMPTY one: num_deletions == 0), every read has base qualities, locus 3 has a left flank of one base, locus 4 such a right flank.
+struct LocSpec { int block_len[2], max_alleles, n_reads[2], read_len, start_off[2]; bool dup_reads, masks, seeded; };
 struct Loc { std::vector<int32_t> bs, be, per, na; std::vector<uint8_t> rep, bytes; std::vector<int64_t> off;
-             std::vector<std::string> seqs, types; std::vector<std::vector<int32_t>> nums; std::vector<ltr_alignment> alns;
+             std::vector<std::string> seqs, quals, types; std::vector<std::vector<int32_t>> nums; std::vector<ltr_alignment> alns;
              ltr_haplotype_blocks hb; std::vector<double> probs; std::vector<int32_t> seeds; std::vector<uint8_t> mate, to_hap, pool, copy; };
 struct LocSet {
   std::vector<Loc> L; std::vector<ltr_locus> loci; std::vector<double*> pp; std::vector<int32_t*> sp;
@@ -107,21 +158,26 @@ struct LocSet {
       X.off.push_back(0);
       for (int b = 0; b < 3; ++b) {
         const bool is_rep = (b == 1);
-        const int len = ri(s.block_len[0], s.block_len[1]), nall = is_rep ? ri(1, s.max_alleles) : 1;
+        const bool one_base = s.seeded && ((l == 3 && b == 0) || (l == 4 && b == 2)), empty_allele = s.seeded && is_rep && l % 4 == 0;
+        const int len = one_base ? 1 : ri(s.block_len[0], s.block_len[1]), nall = is_rep ? ri(empty_allele ? 2 : 1, s.max_alleles) : 1;
         X.bs.push_back(pos); X.be.push_back(pos + len); pos += len;
-        X.rep.push_back(is_rep); X.per.push_back(is_rep ? ri(2, 6) : 0); X.na.push_back(nall);
-        for (int k = 0; k < nall; ++k) { const std::string a = rseq(k == 0 ? len : ri(1, 60)); X.bytes.insert(X.bytes.end(), a.begin(), a.end()); X.off.push_back((int64_t)X.bytes.size()); }
+        X.rep.push_back(is_rep); X.per.push_back(is_rep ? (s.seeded ? 1 : ri(2, 6)) : 0); X.na.push_back(nall);
+        for (int k = 0; k < nall; ++k) {
+          const std::string a = !s.seeded ? rseq(k == 0 ? len : ri(1, 60)) : (!is_rep ? rseq(len) : rhomo(k == 0 ? len : (k == 1 && empty_allele ? 0 : ri(0, 30))));
+          X.bytes.insert(X.bytes.end(), a.begin(), a.end()); X.off.push_back((int64_t)X.bytes.size());
+        }
       }
       X.hb = {3, X.bs.data(), X.be.data(), X.rep.data(), X.per.data(), X.na.data(), X.bytes.data(), X.off.data()};
       const int R = ri(s.n_reads[0], s.n_reads[1]);
       for (int r = 0; r < R; ++r) {
         X.seqs.push_back(s.dup_reads && r > 0 && (rng() & 1) ? X.seqs[0] : rseq(ri(1, s.read_len)));
         X.types.push_back("="); X.nums.push_back({(int32_t)X.seqs.back().size()});
+        if (s.seeded) X.quals.push_back(rqual((int)X.seqs.back().size()));       // (pooled copies of a read: each its own, so the pool's are medians)
       }
       for (int r = 0; r < R; ++r) {
         const int st = X.bs[0] + ri(s.start_off[0], s.start_off[1]);
         X.alns.push_back({st, st + X.nums[(size_t)r][0] - 1, (const uint8_t*)X.seqs[(size_t)r].data(), (int32_t)X.seqs[(size_t)r].size(), 1,
-                          X.types[(size_t)r].data(), X.nums[(size_t)r].data(), nullptr});
+                          X.types[(size_t)r].data(), X.nums[(size_t)r].data(), s.seeded ? (const uint8_t*)X.quals[(size_t)r].data() : nullptr});
       }
       const int64_t H = ltr_haplotype_num_combs(&X.hb);
       X.probs.assign((size_t)std::max<int64_t>(1, R * H), 0.0); X.seeds.assign((size_t)std::max(1, R), 0);
@@ -140,6 +196,7 @@ struct LocSet {
     Loc& X = L[(size_t)l];
     if ((int)X.alns.size() > r) { X.types[(size_t)r] = "Q"; X.alns[(size_t)r].cigar_type = X.types[(size_t)r].data(); }
   }
+  const uint8_t* drop_qual(int l, int r) { const uint8_t* q = L[(size_t)l].alns[(size_t)r].qual; L[(size_t)l].alns[(size_t)r].qual = nullptr; return q; }
   void clear_outputs() { for (Loc& X : L) { std::fill(X.probs.begin(), X.probs.end(), 0.0); std::fill(X.seeds.begin(), X.seeds.end(), -7); } }
 };
 static ltr_ctx* init_ctx(ltr_ctx* ctx, bool fake_device) { std::memset(&ctx->p, 0, sizeof(ctx->p)); ctx->p.indel_flank_len = 5; ctx->fake_device = fake_device; return ctx; }
@@ -177,7 +234,7 @@ int main(int argc, char** argv) {
       const bool is_rep = (b % 2 == 1);
       const int len = ri(is_rep ? 0 : 5, 60), nall = is_rep ? ri(1, 5) : 1;
       bs.push_back(pos); be.push_back(pos + len); pos += len;
-      rep.push_back(is_rep); per.push_back(is_rep ? ri(1, 6) : 0); na.push_back(nall);
+      rep.push_back(is_rep); per.push_back(is_rep ? (it % 5 == 0 ? 1 : ri(1, 6)) : 0); na.push_back(nall);      // (period 1: the seeded path below)
       for (int k = 0; k < nall; ++k) { const std::string s = rseq(k == 0 ? len : ri(0, 80)); bytes.insert(bytes.end(), s.begin(), s.end()); off.push_back((int64_t)bytes.size()); }
     }
     ltr_haplotype_blocks hb = {nb, bs.data(), be.data(), rep.data(), per.data(), na.data(), bytes.data(), off.data()};
@@ -188,21 +245,23 @@ int main(int argc, char** argv) {
       const int64_t n = ltr_haplotype_seq(&hb, k, buf.data(), (int64_t)buf.size());
       if (k >= 0 && k < H && n < 0 && n != LTR_ERR_INVALID) { std::printf("haplotype_seq rc %ld\n", (long)n); return 1; }
     }
-    // reads over the locus, through ltr_process_reads (host half; the stub scorer says "no device")
-    ltr_ctx ctx; std::memset(&ctx.p, 0, sizeof(ctx.p)); ctx.p.indel_flank_len = ri(0, 35); ctx.p.use_short_path = (it % 5 == 0);
+    // reads over the locus, through ltr_process_reads (host half; the stub scorer says "no device"); every fifth locus down the
+    // seeded path on the fake device, every other one of those with base qualities (without: LTR_ERR_INVALID at the first seed)
+    ltr_ctx ctx; std::memset(&ctx.p, 0, sizeof(ctx.p)); ctx.p.indel_flank_len = ri(0, 35); ctx.p.use_short_path = (it % 5 == 0); ctx.fake_device = (it % 5 == 0);
     const int R = ri(0, 6);
-    std::vector<std::string> seqs, types; std::vector<std::vector<int32_t>> nums; std::vector<ltr_alignment> alns;
+    std::vector<std::string> seqs, quals, types; std::vector<std::vector<int32_t>> nums; std::vector<ltr_alignment> alns;
     for (int r = 0; r < R; ++r) {
       const int len = ri(1, 300);
-      seqs.push_back(rseq(len)); types.push_back(std::string(1, '=')); nums.push_back({len});
+      seqs.push_back(rseq(len)); quals.push_back(rqual(len)); types.push_back(std::string(1, '=')); nums.push_back({len});
     }
     for (int r = 0; r < R; ++r) {
       const int st = bs[0] + ri(-150, 50);
       alns.push_back({st, st + nums[(size_t)r][0] - 1, (const uint8_t*)seqs[(size_t)r].data(), (int32_t)seqs[(size_t)r].size(), 1,
-                      types[(size_t)r].data(), nums[(size_t)r].data(), nullptr});
+                      types[(size_t)r].data(), nums[(size_t)r].data(), it % 10 == 0 ? (const uint8_t*)quals[(size_t)r].data() : nullptr});
     }
     std::vector<double> probs((size_t)std::max<int64_t>(1, R * H), 0.0); std::vector<int32_t> seeds((size_t)std::max(1, R), 0);
     (void)ltr_process_reads(&ctx, &hb, nullptr, alns.data(), R, 0, nullptr, probs.data(), seeds.data());
+    if (ctx.err.rfind("fake short_batch_run", 0) == 0) { std::printf("process_reads, seeded path: %s\n", ctx.err.c_str()); return 1; }
     checks++;
   }
   // ---- ltr_calc_hap_aln_probs: threaded per-locus preparation + concatenation --------------------
@@ -263,6 +322,75 @@ int main(int argc, char** argv) {
     long written = 0, kept = 0;                                          // (the masks did mask, and did not mask everything)
     for (const Loc& X : S.L) for (size_t r = 0; r < X.alns.size(); ++r) (X.seeds[r] == -7 ? kept : written)++;
     if (!written || !kept) { std::printf("masked chunk pipeline: %ld reads written, %ld kept\n", written, kept); return 1; }
+  }
+  // ---- the same pipeline down the seeded stutter path (period-1 loci under use_short_path): every locus prepared by the library's
+  // own batch builder on whatever thread has it, the batches strung together in locus order (short_batch_merge shifts their
+  // offsets), the fake device following every offset.  Identical rows and seeds under the four modes; a read without base
+  // qualities and a bad CIGAR operation are the call's error ----
+  {
+    const int NL = 2600;
+    LocSet S(NL, {{20, 45}, 4, {1, 6}, 150, {-60, 30}, true, true, true});
+    std::vector<std::vector<double>> rows; std::vector<std::vector<int32_t>> seeds;
+    auto seeded_ctx = [](ltr_ctx* ctx, int mode) {
+      init_ctx(ctx, true); ctx->p.use_short_path = 1;
+      ctx->knobs.chunks = mode == 3 ? 1 : 5; ctx->knobs.chunk_growth = 1.3; ctx->knobs.chunk_growth_set = true;
+      ctx->knobs.prep_ahead = mode == 1 ? 3 : (mode == 2 ? -1 : 0);
+    };
+    for (int mode = 0; mode < 4; ++mode) {
+      ltr_ctx ctx; seeded_ctx(&ctx, mode);
+      S.clear_outputs();
+      const int rc = ltr_calc_hap_aln_probs(&ctx, S.loci.data(), NL, S.pp.data(), S.sp.data());
+      if (rc != LTR_OK) { std::printf("seeded calc_hap_aln_probs on the fake device: rc %d (%s)\n", rc, ctx.err.c_str()); return 1; }
+      if (mode == 0) for (const Loc& X : S.L) { rows.push_back(X.probs); seeds.push_back(X.seeds); }
+      else for (int l = 0; l < NL; ++l)
+        if (rows[(size_t)l] != S.L[(size_t)l].probs || seeds[(size_t)l] != S.L[(size_t)l].seeds) { std::printf("seeded chunk pipeline: mode %d differs at locus %d\n", mode, l); return 1; }
+      checks++;
+    }
+    long seeded = 0, unseeded = 0, kept = 0, scored = 0;                 // (kept: reads a copy_read mask leaves alone)
+    for (const Loc& X : S.L) {
+      for (size_t r = 0; r < X.alns.size(); ++r) (X.seeds[r] >= 0 ? seeded : (X.seeds[r] == -1 ? unseeded : kept))++;
+      for (const double v : X.probs) scored += v < 0.0;
+    }
+    std::printf("seeded path: %ld seeded reads, %ld unseeded, %ld left alone by a mask; %ld cells scored\n", seeded, unseeded, kept, scored);
+    if (seeded <= 0 || unseeded <= 0 || scored <= 0 || 4 * seeded < seeded + unseeded + kept) { std::printf("seeded path: too few seeded or unseeded reads\n"); return 1; }
+    // (the four modes string the same batches together in the same order; what the merge itself must keep: eight loci scored from one
+    // merged batch get the scores each gets from a batch of its own)
+    {
+      ltr_ctx ctx; seeded_ctx(&ctx, 0);
+      for (int l0 = 0; l0 + 8 <= 800; l0 += 8) {
+        ltr::ShortBatch one[8], all;
+        std::vector<std::vector<double>> alone;
+        int rc = LTR_OK;
+        for (int k = 0; k < 8 && rc == LTR_OK; ++k) {
+          Loc& X = S.L[(size_t)(l0 + k)];
+          std::fill(X.probs.begin(), X.probs.end(), 0.0);
+          rc = ltr::short_batch_add(&ctx, &one[k], &X.hb, nullptr, X.alns.data(), (int32_t)X.alns.size(), 0, nullptr, X.probs.data(), X.seeds.data());
+          if (rc == LTR_OK) rc = ltr::short_batch_run(&ctx, &one[k]);
+          alone.push_back(X.probs);
+          std::fill(X.probs.begin(), X.probs.end(), 0.0);
+        }
+        for (int k = 0; k < 8 && rc == LTR_OK; ++k) rc = ltr::short_batch_merge(&ctx, &all, &one[k]);
+        if (rc == LTR_OK) rc = ltr::short_batch_run(&ctx, &all);
+        if (rc != LTR_OK) { std::printf("seeded path, merged batch: rc %d (%s)\n", rc, ctx.err.c_str()); return 1; }
+        for (int k = 0; k < 8; ++k) if (S.L[(size_t)(l0 + k)].probs != alone[(size_t)k]) { std::printf("seeded path: locus %d scores differently from a merged batch\n", l0 + k); return 1; }
+        checks++;
+      }
+    }
+    {
+      const uint8_t* q = S.drop_qual(1500, 0);
+      ltr_ctx ctx; seeded_ctx(&ctx, 0);
+      const int rc = ltr_calc_hap_aln_probs(&ctx, S.loci.data(), NL, S.pp.data(), S.sp.data());
+      if (rc != LTR_ERR_INVALID) { std::printf("seeded path, a read without base qualities: rc %d\n", rc); return 1; }
+      S.L[1500].alns[0].qual = q;
+      checks++;
+    }
+    {
+      S.bad_cigar(2000, 0);                                              // (locus 2000 has no realign_pool mask: pool 0 is realigned)
+      ltr_ctx ctx; seeded_ctx(&ctx, 0);
+      const int rc = ltr_calc_hap_aln_probs(&ctx, S.loci.data(), NL, S.pp.data(), S.sp.data());
+      if (rc != LTR_ERR_CIGAR) { std::printf("seeded path, a bad CIGAR operation: rc %d\n", rc); return 1; }
+      checks++;
+    }
   }
   // ---- two callers at once, own contexts: one gets the worker pool, the other finds it busy and falls back to
   // short-lived threads (ltr_internal.h) ----

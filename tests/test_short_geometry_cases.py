@@ -1,12 +1,40 @@
 """CPU: the crafted short-path cases of short_util (the inputs of tests/test_gpu_short_geometry.py) reach the side lengths,
 flank shapes and block lengths they are meant to reach, the restatement scores them (rc 0, finite), and the geometry rules
-of ltr_short.hip's short_geometry restated in short_util.geometry give the constants worked out by hand below."""
+of the library's short_geometry (ltr_short_batch.cpp) restated in short_util.geometry give the constants worked out by hand below -- and
+the restatement equals the library's rule itself (test hook ltr_debug_short_geometry), for every case here and over a grid."""
+import ctypes as C
+import itertools
+
 import numpy as np
 import pytest
 
 import oracle_lib as ol
 import short_util as su
-from longtr_amd import _abi
+from longtr_amd import _abi, _lib
+
+
+def lib_geometry(max_side, max_block, max_hap, n_pairs, lane_knob=0):
+    """short_geometry of the library for a batch with these maxima, in short_util.geometry's terms (+ LP, grid, per_block)."""
+    out = (C.c_int64 * 8)()
+    assert _lib.lib().ltr_debug_short_geometry(max_side, max_block, max_hap, n_pairs, lane_knob, out) == 0
+    S, HS, LP, lds, cap, wave, grid, per_block = list(out)
+    return dict(S=S, HS=HS, lds_bytes=lds, chunk_cap=cap, four_launch=bool(wave)), dict(LP=LP, grid=grid, per_block=per_block)
+
+
+def geometry(max_side, max_block, max_hap, n_pairs):
+    """su.geometry, held to the library's rule"""
+    g = su.geometry(max_side, max_block, max_hap, n_pairs)
+    assert g == lib_geometry(max_side, max_block, max_hap, n_pairs)[0], (max_side, max_block, max_hap, n_pairs)
+    return g
+
+
+def geometry_of(blocks, side_list, n_pairs):
+    """su.geometry_of, held to the library's rule"""
+    g = su.geometry_of(blocks, side_list, n_pairs)
+    mb = max(len(a) for a in blocks[1]["alleles"])
+    args = (max(max(s) for s in side_list), mb, len(blocks[0]["alleles"][0]) + mb + len(blocks[2]["alleles"][0]), n_pairs)
+    assert g == su.geometry(*args) == lib_geometry(*args)[0], args
+    return g
 
 
 def _prm():
@@ -53,13 +81,13 @@ def test_case_a_and_b_reach_every_edge_side():
     assert set(su.EDGE_SIDES) <= {l for l, _ in sd} and set(su.EDGE_SIDES) <= {r for _, r in sd}
     assert max(max(s) for s in sd) == 512
     assert all(min(s) <= 64 for s in sd)                                                  # the other side of every read is short
-    assert su.geometry_of(blocks, sd, 3 * len(alns))["four_launch"]
+    assert geometry_of(blocks, sd, 3 * len(alns))["four_launch"]
     assert any(b" " in a["qual"] and b"!" in a["qual"] and b"~" in a["qual"] and b"N" in a["seq"] and a["seq"] != a["seq"].upper() for a in alns)
     blocks, alns = su.case_b()
     sb = _score(blocks, alns)
     assert sb[:len(sd)] == sd
     assert set(su.EDGE_SIDES + su.PAST_512) <= {l for l, _ in sb} and set(su.EDGE_SIDES + su.PAST_512) <= {r for _, r in sb}
-    assert not su.geometry_of(blocks, sb, 3 * len(alns))["four_launch"]
+    assert not geometry_of(blocks, sb, 3 * len(alns))["four_launch"]
 
 
 @pytest.mark.parametrize("which", [1, 2, 3, 4])
@@ -69,7 +97,7 @@ def test_case_c_block_shapes(which):
     flat = [x for s in sd for x in s]
     assert min(flat) < 128 and max(flat) > 256 if which != 4 else max(flat) > 128
     lens = sorted(len(a) for a in blocks[1]["alleles"])
-    g = su.geometry_of(blocks, sd, len(alns) * len(lens))
+    g = geometry_of(blocks, sd, len(alns) * len(lens))
     assert g["four_launch"]
     if which == 1:
         assert lens == [0, 1, 2, 3, 5, 6, 7, 13]                                          # num_deletions 0, 1, 2, 3, 5, 6, 6, 6
@@ -104,22 +132,36 @@ def test_case_f_and_the_lds_rule():
         blocks, alns = su.case_f(block_len)
         sd = _score(blocks, alns)
         assert 6 <= len(alns) <= 8 and max(max(s) for s in sd) < 512 and max(max(s) for s in sd) > 256 and min(min(s) for s in sd) < 128
-        g = su.geometry_of(blocks, sd, 2 * len(alns))
+        g = geometry_of(blocks, sd, 2 * len(alns))
         assert g["lds_bytes"] == lds and g["four_launch"] is four and g["S"] == block_len + 5
 
 
 def test_chunk_rule_constants():
     # cap = (2^30 - 64) // (2 * 13 * 8 * S): a maximum side of 512 (block 15) gives S = 514, 208 * 514 = 106912,
     # 1073741760 // 106912 = 10043 (10043 * 106912 = 1073717216, remainder 24544)
-    g = su.geometry(512, 15, 85, 10 ** 6)
+    g = geometry(512, 15, 85, 10 ** 6)
     assert g["S"] == 514 and g["chunk_cap"] == 10043
-    assert su.geometry(512, 15, 85, 300)["chunk_cap"] == 300                              # one chunk when the call is small
-    assert su.geometry(20, 300, 370, 10 ** 6)["S"] == 304                                 # the block, not the side
-    assert su.geometry(5, 0, 13, 10 ** 6)["S"] == 15                                      # the 13 artifact sizes
+    assert geometry(512, 15, 85, 300)["chunk_cap"] == 300                              # one chunk when the call is small
+    assert geometry(20, 300, 370, 10 ** 6)["S"] == 304                                 # the block, not the side
+    assert geometry(5, 0, 13, 10 ** 6)["S"] == 15                                      # the 13 artifact sizes
     blocks, alns = su.case_e()
     sd = _score(blocks, alns)
     assert len(alns) == 48 and sorted(max(s) for s in sd)[-3:] == [sorted(max(s) for s in sd)[-3], 512, 512] and sorted(max(s) for s in sd)[-3] <= 64
     assert sd[0][0] == 512 and sd[1][1] == 512
-    cap = su.geometry_of(blocks, sd, 10 ** 6)["chunk_cap"]
+    cap = geometry_of(blocks, sd, 10 ** 6)["chunk_cap"]
     tiles, rr, rh, pairs = su.case_e_tiling(len(alns), cap)
     assert cap == 10043 and pairs == tiles * 46 * 2 and 2 * cap < pairs <= 2 * cap + 92 and rr[0] and rr[1]      # three chunks, the last partial
+
+
+def test_restatement_equals_the_library_rule_over_a_grid():
+    for max_side, max_block, n_pairs in itertools.product([1, 4, 128, 129, 511, 512, 513, 700, 1100], [0, 1, 15, 300, 601, 1501], [1, 300, 10 ** 6]):
+        g = geometry(max_side, max_block, 70 + max_block, n_pairs)
+        assert g["four_launch"] == (max_side <= 512 and g["lds_bytes"] <= 65536)
+        # the knob ("short_lane_kernel") forces the lane-per-pair kernel and changes nothing else
+        want, rest = lib_geometry(max_side, max_block, 70 + max_block, n_pairs)
+        forced, rest_forced = lib_geometry(max_side, max_block, 70 + max_block, n_pairs, lane_knob=1)
+        assert not forced["four_launch"] and dict(forced, four_launch=want["four_launch"]) == want and rest_forced == rest
+        # LP = max(S, HS) + 8; per_block = (19 S + LP + 2 (HS + 2)) * 64 doubles; grid = min(ceil(pairs / 64), 4096, 8 GB / per_block bytes)
+        assert rest["LP"] == max(g["S"], g["HS"]) + 8 and rest["per_block"] == (19 * g["S"] + rest["LP"] + 2 * (g["HS"] + 2)) * 64
+        assert rest["grid"] == min((n_pairs + 63) // 64, 4096, max(1, (8 << 30) // (rest["per_block"] * 8)))
+    assert _lib.lib().ltr_debug_short_geometry(-1, 0, 70, 1, 0, (C.c_int64 * 8)()) != 0
