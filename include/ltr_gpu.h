@@ -194,7 +194,9 @@ int ltr_plan_family_spine_stats(const ltr_plan* plan, int64_t* out2);
  * pairs scored with the exact body, ticks spent there} per wavefront of the last execute, then 4096 words: a count and
  * (n << 32 | m) of the pairs that took the exact body, then 256 words: per entry of the plan kernel's table (ltr_plan_debug_entries) the
  * ticks all wavefronts together spent in it.  cap (64-bit words) must hold 4 x wavefronts + 4096 + 256.
- * Returns the number of wavefronts written (0: not recorded), negative on error. */
+ * Returns the number of wavefronts written (0: not recorded), negative on error.
+ * (Under the same knob the family launch records its wavefronts' first and last clock in a buffer of its own: the hook
+ * ltr_debug_family_wave_clocks, csrc/ltr_plan.h.) */
 int ltr_plan_debug_wave_clocks(ltr_plan* plan, uint64_t* out, int64_t cap);
 /* The plan kernel's table, in walk order: kind (0 one pair per wavefront, 1 packed strip width, 2 pairs that start with the exact
  * body, 3 = 0 by the chained walk), strip width, pairs, nominal cells of every entry.  Returns the number of entries. */

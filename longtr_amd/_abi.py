@@ -720,6 +720,7 @@ HOOK_SIGNATURES = {
     "ltr_debug_plan_family_forks": (_int, [_P(AlignParams), _int, _int, _P(LocusBatch), _vp, _vp, _int, _vp, _vp, _int, _vp, _vp, _vp]),
     "ltr_debug_chunk_plan": (_int, [_i64, _f64, _vp, _int, _vp, _int, _vp]),
     "ltr_debug_last_launches": (_int, [_vp, _vp, _int, _vp]),
+    "ltr_debug_family_wave_clocks": (_int, [_vp, _vp, _i64]),
 }
 
 

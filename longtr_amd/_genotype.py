@@ -180,6 +180,15 @@ class Plan(Handle):
         self.entry_ticks = buf[4 * n + 4096:4 * n + 4096 + 256].copy()       # per entry of the plan kernel's table: ticks of all wavefronts together
         return buf[:4 * n].reshape(n, 4)
 
+    def family_wave_clocks(self):
+        """(n_waves, 2) uint64: first / last wall clock (100 MHz) per wavefront of the family launch of the last execute (debug knob
+        wave_clock; the same clock as wave_clocks()).  Empty when nothing was recorded: the knob off, or a plan without families."""
+        buf = np.zeros(2 * 4 * 4096, dtype=np.uint64)
+        n = lib().ltr_debug_family_wave_clocks(self._h, _p(buf), buf.size)
+        if n < 0:
+            raise LtrError(n, "ltr_debug_family_wave_clocks")
+        return buf[:2 * n].reshape(n, 2)
+
     def family_spine_stats(self):
         """ltr_plan_family_spine_stats: dict(with_spine: families of the plan run along a spine, steps_saved: modelled wavefront
         steps that saves against plain families)."""

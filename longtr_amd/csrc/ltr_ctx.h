@@ -135,6 +135,8 @@ struct ltr_plan : ltrp::BatchPlan {     // (what ltrp::describe_batch decided: s
   FamilySpine* d_fam_spines = nullptr;  // fam_spines (BatchPlan): per family, beside d_fams
   double* d_fam_park = nullptr;         // ... per wavefront of its grid: kFamilyParkDoubles (the park rows: the stem's last row, the spine's fork rows)
   uint32_t* d_fam_stats = nullptr;      // ... 4 words, zeroed by every execute (FamilyArgs::stats)
+  unsigned long long* d_fam_wave_clock = nullptr;   // (debug) ... two wall-clock words per wavefront of its grid (FamilyArgs::wave_clock)
+  int fam_clock_waves = 0;              // ... wavefronts of the family launch of the last execute
   hipEvent_t bin_ev[ltrp::kNumKernels + 1] = {nullptr};   // bracket every DP launch on the launch stream
   uint32_t* d_ctrl_init = nullptr;      // image of the control words (queues = 0, redo count = n_generic)
   int32_t* d_redo_init = nullptr;       // indices of the generic pairs: copied over the head of the redo list every execute

@@ -279,7 +279,7 @@ __device__ __attribute__((noinline)) int family_narrow_call(int64_t kernarg_v, i
 // failures).  The spine member's score is the stream's last step.
 template <int W>
 __device__ __forceinline__ int spine_walk(const KernelArgs& A, const FamilyArgs& F, const int fi, const int lane,
-                                           const double* emit_tab, int* note, double* park) {
+                                           const double* emit_tab, int* note, int* spl, double* park) {
   const FamilyDesc* __restrict__ fd = F.fams + fi;
   const FamilySpine* __restrict__ sp = F.spines + fi;
   const int first = uni(fd->first), count = uni(fd->count), p = uni(fd->p);
@@ -287,6 +287,15 @@ __device__ __forceinline__ int spine_walk(const KernelArgs& A, const FamilyArgs&
   const PairDesc* pp0 = A.pairs + first;
   const int spine = uni((int)sp->spine), n_slots = uni((int)sp->n_slots);
   const PairDesc* pps = pp0 + spine;                           // the member the stream follows
+  // ---- the spine record, once per family, to this wavefront's LDS words (kSpineLds*): inside the stream's loop a lane reads its
+  // slot's row and range with an index of its own, and an LDS read waits on lgkmcnt -- no vector-memory counter, so nothing there
+  // waits for the park stores.  (Written and read by this wavefront alone, in its program order: LDS serves a wavefront in order.)
+  if (lane <= 16) spl[kSpineLdsRow + lane] = lane < n_slots ? (int)sp->slot_row[min(lane, kFamilyParkSlots - 1)] : kSpineNoRow;
+  if (lane < kFamilyParkSlots) { spl[kSpineLdsDdMin + lane] = (int)sp->slot_dd_min[lane]; spl[kSpineLdsDdMax + lane] = (int)sp->slot_dd_max[lane]; }
+  if (lane < kFamilyMaxMembers) spl[kSpineLdsSlotOf + lane] = (int)sp->slot_of[lane];
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   const int m = uni(pp0->m);
   const uint8_t* __restrict__ read = A.read_bytes + uni64(pp0->read_off);
   const double ca = A.mc.a, cc = A.mc.c, cd = A.mc.d, ce = A.mc.e, cf = A.mc.f, cg = A.mc.g, cb = A.mc.b;
@@ -431,24 +440,40 @@ __device__ __forceinline__ int spine_walk(const KernelArgs& A, const FamilyArgs&
 
   // ---- the stream: rows 1 .. n_s - 1 of the spine member, no drain at p.  A lane parks a park row's state -- X, Y of its columns
   // and X(row - 1, j0 - 1) -- when its own row reaches row - 1 (step row - 2 + lane: the lanes reach a row on different steps, and
-  // park rows closer than L rows are in flight together), and from that row on tests against the members still on the spine ----
+  // park rows closer than L rows are in flight together), and from that row on tests against the members still on the spine.
+  // A parking step does not wait for memory: the lane's chunk of the slot is 2W+2 consecutive doubles (ltr_dp_types.h: lane-major),
+  // W+1 16-byte stores from one address; the slot's row and range come from the LDS copy; and the step's two prefetches (the next
+  // haplotype row code, the next column-0 record) are waited for BEFORE the branch, a step after they were issued, so that the
+  // stores are the youngest vector-memory operations in flight and no wait of that step covers them ----
+  constexpr int CH = 2 * W + 2;                                // doubles of a lane's chunk
+  constexpr int SLOT = 64 * CH;                                // ... of a slot at this width
+  double* const chunk0 = park + lane * CH;                     // my chunk of slot 0
   int pk = p - 2 + lane;                                       // the step after which I park my next slot
   int psl = 0;                                                 // ... which slot that is
   auto park_if = [&](const int t) __attribute__((always_inline)) {
+    asm volatile("" : "+v"(h_next), "+v"(bX_next), "+v"(bZ_next));
     if (t == pk) {
-      double* sl = park + psl * kFamilySlotDoubles + lane;
+      d2v_t* sl = (d2v_t*)(chunk0 + psl * SLOT);
 #pragma unroll
-      for (int s = 0; s < W; ++s) { sl[s * 64] = Xp[s]; sl[(W + s) * 64] = Yp[s]; }
-      sl[2 * W * 64] = leftX;
-      const int R = sp->slot_row[psl];
-      kd = (double)(sp->slot_dd_min[psl] - R + j0); kd2 = (double)(sp->slot_dd_max[psl] - R + j0);   // (my next row is R)
+      for (int i = 0; i <= W; ++i) {                           // X[0 .. W-1], Y[0 .. W-1], leftX, pad (at odd W one pair is X[W-1], Y[0])
+        const int a = 2 * i, b = 2 * i + 1;
+        d2v_t v;
+        v.x = a < W ? Xp[a < W ? a : 0] : (a < 2 * W ? Yp[a < 2 * W ? a - W : 0] : leftX);
+        v.y = b < W ? Xp[b < W ? b : 0] : (b < 2 * W ? Yp[b < 2 * W ? b - W : 0] : leftX);
+        sl[i] = v;
+      }
+      const int R = spl[kSpineLdsRow + psl];
+      kd = (double)(spl[kSpineLdsDdMin + psl] - R + j0); kd2 = (double)(spl[kSpineLdsDdMax + psl] - R + j0);   // (my next row is R)
       ++psl;
-      pk = (psl < n_slots ? sp->slot_row[psl < kFamilyParkSlots ? psl : 0] : 0x3fffffff) - 2 + lane;
+      pk = spl[kSpineLdsRow + psl] - 2 + lane;                 // (from n_slots on: kSpineNoRow, a step that never comes)
     }
   };
   int bad = 0, t_bad = 0;
   {
     const int T = (nr - 1) + (L - 1);
+    // (step 0's operands are waited for here: the loop is then entered with no load pending, as it is by its back edge, and the
+    // wait that a pending load at the loop's head would need -- one that also drains the stores of the step before -- is not there)
+    asm volatile("" : "+v"(h_next), "+v"(bX_next), "+v"(bZ_next));
     for (int t = 0; t < T - 1; ++t) {
       if (step(BoolTag<false>{}, BoolTag<true>{}, t)) { bad = 1; t_bad = t; break; }
       park_if(t);
@@ -460,7 +485,7 @@ __device__ __forceinline__ int spine_walk(const KernelArgs& A, const FamilyArgs&
     }
   }
   // (the tails LOAD the state.  A compile-only barrier is enough because every lane reloads exactly the addresses it stored itself
-  // -- slot + lane --, in program order of its own wavefront: a read of another lane's doubles would need more than this)
+  // -- its own chunk of the slot --, in program order of its own wavefront: a read of another lane's doubles would need more than this)
   asm volatile("" ::: "memory");
   // the row no lane certifies (it is noticed when it reaches the last lane); every row below it passed, and a slot whose row is at
   // or below it is complete: the last lane parked it when it finished the row before
@@ -489,8 +514,8 @@ __device__ __forceinline__ int spine_walk(const KernelArgs& A, const FamilyArgs&
   for (int k = 0; k < count; ++k) {
     if (k == spine) continue;
     const PairDesc* pp = A.pairs + first + k;
-    const int slot = uni((int)sp->slot_of[k]);
-    const int R = uni((int)sp->slot_row[slot]);
+    const int slot = uni(spl[kSpineLdsSlotOf + k]);
+    const int R = uni(spl[kSpineLdsRow + slot]);
     if (R > r_bad) {                                           // its slot is not complete: the spine's certificate failed below its park row
       if (lane == 0) { note[noted] = first + k; atomicAdd(F.stats + 2, 1u); }
       ++noted;
@@ -502,10 +527,14 @@ __device__ __forceinline__ int spine_walk(const KernelArgs& A, const FamilyArgs&
     nr = n - rb;                                               // >= 2: the host keeps every park row <= n - 1
     hs = A.hap_codes + uni64(pp->hap_off) - 63 + rb;
     hrs = __builtin_amdgcn_make_buffer_rsrc((void*)(uintptr_t)uni64((int64_t)(uintptr_t)hs), 0, 0x7fffffff, 0x00020000);
-    const double* sl = park + slot * kFamilySlotDoubles + lane;
+    const d2v_t* sl = (const d2v_t*)(chunk0 + slot * SLOT);
 #pragma unroll
-    for (int s = 0; s < W; ++s) { Xp[s] = sl[s * 64]; Yp[s] = sl[(W + s) * 64]; }
-    leftX = sl[2 * W * 64];
+    for (int i = 0; i <= W; ++i) {                             // my chunk as I stored it: W+1 16-byte loads
+      const d2v_t v = sl[i];
+      const int a = 2 * i, b = 2 * i + 1;
+      if (a < W) Xp[a < W ? a : 0] = v.x; else if (a < 2 * W) Yp[a < 2 * W ? a - W : 0] = v.x; else leftX = v.x;
+      if (b < W) Xp[b < W ? b : 0] = v.y; else if (b < 2 * W) Yp[b < 2 * W ? b - W : 0] = v.y;
+    }
     outX = Xp[W - 1];
     outZ = IMP;
     fmask = ~0ull;
@@ -533,23 +562,24 @@ __device__ __forceinline__ int spine_walk(const KernelArgs& A, const FamilyArgs&
 
 // The calls of a family with a spine (the reasons of family_walk_call; names of their own: the plain families' bodies stay what they were).
 template <int W>
-__device__ __forceinline__ int spine_walk_from_kernarg(int64_t kernarg_v, int fi_v, unsigned emit_lds_v, unsigned note_lds_v) {
+__device__ __forceinline__ int spine_walk_from_kernarg(int64_t kernarg_v, int fi_v, unsigned emit_lds_v, unsigned note_lds_v, unsigned spine_lds_v) {
   const KernelArgs& A = *(const KernelArgs*)(KernArgPtr)(uintptr_t)uni64(kernarg_v);
   const FamilyArgs& F = *(const FamilyArgs*)(FamArgPtr)(uintptr_t)(uni64(kernarg_v) + (int64_t)kFamilyArgsOffset);
   const int lane = threadIdx.x & 63;
   const int wave = uni((int)(threadIdx.x >> 6));
   const double* emit_tab = (const double*)(LdsDoubles)(uintptr_t)(unsigned)uni((int)emit_lds_v);
   int* note = (int*)(LdsInts)(uintptr_t)(unsigned)uni((int)note_lds_v);
+  int* spl = (int*)(LdsInts)(uintptr_t)(unsigned)uni((int)spine_lds_v);
   double* park = F.park + ((size_t)blockIdx.x * kBlockWaves + wave) * (size_t)kFamilyParkDoubles;
-  return spine_walk<W>(A, F, uni(fi_v), lane, emit_tab, note, park);
+  return spine_walk<W>(A, F, uni(fi_v), lane, emit_tab, note, spl, park);
 }
 template <int W>                                               // the wide band: W 11 .. 20
-__device__ __attribute__((noinline)) int spine_wide_call(int64_t kernarg_v, int fi_v, unsigned emit_lds_v, unsigned note_lds_v) {
-  return spine_walk_from_kernarg<W>(kernarg_v, fi_v, emit_lds_v, note_lds_v);
+__device__ __attribute__((noinline)) int spine_wide_call(int64_t kernarg_v, int fi_v, unsigned emit_lds_v, unsigned note_lds_v, unsigned spine_lds_v) {
+  return spine_walk_from_kernarg<W>(kernarg_v, fi_v, emit_lds_v, note_lds_v, spine_lds_v);
 }
 template <int W>                                               // the narrow band: W 6 .. 10
-__device__ __attribute__((noinline)) int spine_narrow_call(int64_t kernarg_v, int fi_v, unsigned emit_lds_v, unsigned note_lds_v) {
-  return spine_walk_from_kernarg<W>(kernarg_v, fi_v, emit_lds_v, note_lds_v);
+__device__ __attribute__((noinline)) int spine_narrow_call(int64_t kernarg_v, int fi_v, unsigned emit_lds_v, unsigned note_lds_v, unsigned spine_lds_v) {
+  return spine_walk_from_kernarg<W>(kernarg_v, fi_v, emit_lds_v, note_lds_v, spine_lds_v);
 }
 
 // Persistent: the families are dealt STATICALLY, wavefront w of G takes families w, 2G-1-w, 2G+w, .. of the list (sorted by
@@ -558,6 +588,7 @@ __global__ __launch_bounds__(64 * kBlockWaves, 3) void ltr_dp_family_kernel(Kern
   __shared__ __attribute__((aligned(16))) double s_emit[kEmitTabDoubles];
   __shared__ double s_pen[kPenTabDoubles];                     // the exact thresholds of the in-line redo (kModeThr)
   __shared__ int s_note[kBlockWaves][kFamilyMaxMembers];       // per wave: members waiting for the exact body
+  __shared__ int s_spine[kBlockWaves][kSpineLdsInts];          // per wave: the spine record of the family it runs (spine_walk)
   for (int idx = threadIdx.x; idx < kEmitTabDoubles; idx += 64 * kBlockWaves) {
     const int half = idx >> 11, hcode = (idx >> 9) & 3, quad = (idx >> 1) & 255, k = 2 * half + (idx & 1);
     s_emit[idx] = (hcode == ((quad >> (2 * k)) & 3)) ? (double)A.mc.match : (double)A.mc.mismatch;
@@ -568,9 +599,11 @@ __global__ __launch_bounds__(64 * kBlockWaves, 3) void ltr_dp_family_kernel(Kern
   const unsigned emit_lds = (unsigned)(uintptr_t)(LdsDoubles)s_emit;
   const unsigned pen_lds = (unsigned)(uintptr_t)(LdsDoubles)s_pen;
   const unsigned note_lds = (unsigned)(uintptr_t)(LdsInts)s_note[wave];
+  const unsigned spine_lds = (unsigned)(uintptr_t)(LdsInts)s_spine[wave];
   const int64_t kargs = (int64_t)(uintptr_t)__builtin_amdgcn_kernarg_segment_ptr();
   const int G = (int)gridDim.x * kBlockWaves, my_wave = (int)blockIdx.x * kBlockWaves + wave;
   const int n_f = F.n_fams;
+  const unsigned long long t_first = F.wave_clock ? wall_clock64() : 0ull;   // (measurement aid, as the plan kernel's: when this wavefront started ..)
   for (int64_t base = 0, round = 0; base < n_f; base += G, ++round) {
     const int64_t f64 = base + ((round & 1) ? (G - 1 - my_wave) : my_wave);
     if (f64 >= n_f) continue;
@@ -578,21 +611,21 @@ __global__ __launch_bounds__(64 * kBlockWaves, 3) void ltr_dp_family_kernel(Kern
     const int w = uni(F.fams[fi].W);
     int noted;
     if (uni((int)F.spines[fi].spine) >= 0) switch (w) {
-      case 6: noted = spine_narrow_call<6>(kargs, fi, emit_lds, note_lds); break;
-      case 7: noted = spine_narrow_call<7>(kargs, fi, emit_lds, note_lds); break;
-      case 8: noted = spine_narrow_call<8>(kargs, fi, emit_lds, note_lds); break;
-      case 9: noted = spine_narrow_call<9>(kargs, fi, emit_lds, note_lds); break;
-      case 10: noted = spine_narrow_call<10>(kargs, fi, emit_lds, note_lds); break;
-      case 11: noted = spine_wide_call<11>(kargs, fi, emit_lds, note_lds); break;
-      case 12: noted = spine_wide_call<12>(kargs, fi, emit_lds, note_lds); break;
-      case 13: noted = spine_wide_call<13>(kargs, fi, emit_lds, note_lds); break;
-      case 14: noted = spine_wide_call<14>(kargs, fi, emit_lds, note_lds); break;
-      case 15: noted = spine_wide_call<15>(kargs, fi, emit_lds, note_lds); break;
-      case 16: noted = spine_wide_call<16>(kargs, fi, emit_lds, note_lds); break;
-      case 17: noted = spine_wide_call<17>(kargs, fi, emit_lds, note_lds); break;
-      case 18: noted = spine_wide_call<18>(kargs, fi, emit_lds, note_lds); break;
-      case 19: noted = spine_wide_call<19>(kargs, fi, emit_lds, note_lds); break;
-      default: noted = spine_wide_call<20>(kargs, fi, emit_lds, note_lds); break;
+      case 6: noted = spine_narrow_call<6>(kargs, fi, emit_lds, note_lds, spine_lds); break;
+      case 7: noted = spine_narrow_call<7>(kargs, fi, emit_lds, note_lds, spine_lds); break;
+      case 8: noted = spine_narrow_call<8>(kargs, fi, emit_lds, note_lds, spine_lds); break;
+      case 9: noted = spine_narrow_call<9>(kargs, fi, emit_lds, note_lds, spine_lds); break;
+      case 10: noted = spine_narrow_call<10>(kargs, fi, emit_lds, note_lds, spine_lds); break;
+      case 11: noted = spine_wide_call<11>(kargs, fi, emit_lds, note_lds, spine_lds); break;
+      case 12: noted = spine_wide_call<12>(kargs, fi, emit_lds, note_lds, spine_lds); break;
+      case 13: noted = spine_wide_call<13>(kargs, fi, emit_lds, note_lds, spine_lds); break;
+      case 14: noted = spine_wide_call<14>(kargs, fi, emit_lds, note_lds, spine_lds); break;
+      case 15: noted = spine_wide_call<15>(kargs, fi, emit_lds, note_lds, spine_lds); break;
+      case 16: noted = spine_wide_call<16>(kargs, fi, emit_lds, note_lds, spine_lds); break;
+      case 17: noted = spine_wide_call<17>(kargs, fi, emit_lds, note_lds, spine_lds); break;
+      case 18: noted = spine_wide_call<18>(kargs, fi, emit_lds, note_lds, spine_lds); break;
+      case 19: noted = spine_wide_call<19>(kargs, fi, emit_lds, note_lds, spine_lds); break;
+      default: noted = spine_wide_call<20>(kargs, fi, emit_lds, note_lds, spine_lds); break;
     }
     else switch (w) {
       case 6: noted = family_narrow_call<6>(kargs, fi, emit_lds, note_lds); break;
@@ -616,5 +649,8 @@ __global__ __launch_bounds__(64 * kBlockWaves, 3) void ltr_dp_family_kernel(Kern
       const int pi = uni(s_note[wave][k]);
       redo_dispatch<true>(A, kargs, pi, uni(A.pairs[pi].m) - 1, emit_lds, pen_lds);
     }
+  }
+  if (F.wave_clock && (threadIdx.x & 63) == 0) {               // (.. and when it left: the spread of the static deal)
+    F.wave_clock[2 * my_wave] = t_first; F.wave_clock[2 * my_wave + 1] = wall_clock64();
   }
 }

@@ -136,12 +136,22 @@ struct FamilyArgs {        // the family kernel's second argument (KernelArgs st
   double* park;            // per wavefront of the launch: kFamilyParkDoubles (the stem's last row: X, Y of every column)
   uint32_t* stats;         // [0] families whose stem certificate failed, [1] members the acceptance rule sent to the exact body, [2] members whose tail certificate failed
   const FamilySpine* spines;   // per family, beside fams
+  unsigned long long* wave_clock;   // optional (ltr_ctx_set_debug "wave_clock"): per wavefront of the family launch {first, last wall clock (100 MHz)}
 };
 constexpr int kFamilyMaxMembers = 32;            // members of a family (the wave's note list)
 constexpr int kFamilyMinC = 641, kFamilyMaxC = 64 * LTR_WMAX;   // read columns of a family of the wide band: one wavefront, one column block, strips of 11 .. 20
 constexpr int kFamilyNarrowMinC = 321, kFamilyNarrowMaxC = 640; // ... and of the narrow band: the same geometry with strips of 6 .. 10 -- reads the class rule packs two to a wavefront
-constexpr int kFamilySlotDoubles = (2 * LTR_WMAX + 1) * 64;      // one park row: X, Y of every column and X of the column left of the lane's strip
-constexpr int kFamilyParkDoubles = kFamilyParkSlots * kFamilySlotDoubles;   // per wavefront (a plain family uses the head of slot 0)
+// One park row of a family with a spine, LANE-MAJOR: lane l's chunk is the 2W+2 consecutive doubles at slot + l * (2W+2) -- X and Y of
+// its W columns, X of the column left of its strip, one pad -- so that the one lane that parks on a step writes W+1 16-byte stores
+// from one address; a slot is 64 chunks, and the slots of a family are dense at its own width.  Sized here for the widest strip.
+constexpr int kFamilySlotDoubles = (2 * LTR_WMAX + 2) * 64;
+constexpr int kFamilyParkDoubles = kFamilyParkSlots * kFamilySlotDoubles;   // per wavefront (a plain family uses the head of the block: [2W][64], all lanes together)
+// The spine record as spine_walk keeps it in LDS, per wavefront (int32 words): slot_row[0 .. 16] (from n_slots on: never reached),
+// slot_dd_min[16], slot_dd_max[16], slot_of[32] -- what a lane reads with an index of its own inside the stream's loop (328 bytes a
+// wavefront; no vector-memory counter is involved in reading it).
+constexpr int kSpineLdsRow = 0, kSpineLdsDdMin = 17, kSpineLdsDdMax = 33, kSpineLdsSlotOf = 49, kSpineLdsInts = 82;
+constexpr int kSpineNoRow = 0x3fffffff;
+static_assert(kSpineLdsSlotOf + 32 <= kSpineLdsInts && kFamilyParkSlots <= 16, "the LDS copy holds up to 16 slots");
 constexpr int kFamilyArgsOffset = (int)((sizeof(KernelArgs) + alignof(FamilyArgs) - 1) / alignof(FamilyArgs) * alignof(FamilyArgs));   // where FamilyArgs sits in the kernel's argument segment
 constexpr int kInlineCountOff = 8;                // xcount[kInlineCountOff + c]: pairs of exact class c the plan kernel scored in line (statistics)
 constexpr int kWgStatOff = 16;                    // xcount[kWgStatOff]: pairs the FIRST pass of the workgroup classes could not finish (certificate pass: sent to an exact list; threshold pass: aborted, -700); [+ 1]: pairs it scored -- what the context learns its first pass from

@@ -241,7 +241,7 @@ struct DebugKnobs {
   int fold_rounds = 0;          // automatic mode: fold launch classes below this many rounds of resident waves (rule: ltrp::kFoldRounds)
   int short_lane_kernel = 0;    // short path: the lane-per-pair kernel even where the wavefront-per-pair kernel applies (A/B)
   int plan_kernel = 0;          // A/B: 1 = a launch per class / the multi-width launches as before round 5; 0 (and -1, kept for old scripts) = the rule: the plan kernel for every automatic-mode plan
-  int wave_clock = 0;           // 1: the plan kernel records every wavefront's first / last wall clock (ltr_plan_debug_wave_clocks)
+  int wave_clock = 0;           // 1: the plan kernel records every wavefront's first / last wall clock (ltr_plan_debug_wave_clocks), and so does the family launch (ltr_debug_family_wave_clocks)
   int chain = 0;                // 1 = the plan kernel's one-wave classes of strip widths 11 .. 20 by the chained walk (ltr_dp_chain.hpp; measured slower: off)
   int chain_min_w = 0, chain_max_w = 0;   // ... the chained walk for these strip widths only (0: 11 .. 20)
   int plan_share = 0;           // A/B: 1 = every wavefront of the plan kernel starts at the top of its table (default: spread over the entries in proportion to their work)

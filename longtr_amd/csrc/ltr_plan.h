@@ -428,6 +428,13 @@ int ltr_debug_plan_family_forks(const ltr_align_params* p, int mode, int n_cu, c
 // items (-1: on the device); returns the number of launches (which may exceed cap) or LTR_ERR_INVALID.
 struct ltr_plan; struct ltr_ctx;
 int ltr_debug_last_launches(const ltr_plan* plan, ltr_ctx* ctx, int cap, int64_t* out);
+// ltr_debug_family_wave_clocks (ltr_plan_run.hip; needs a device): a measurement aid beside ltr_plan_debug_wave_clocks (include/ltr_gpu.h).
+// With ltr_ctx_set_debug(ctx, "wave_clock", 1) set when the plan was created, the family launch (ltr_dp_family.hpp) records the wall
+// clock (100 MHz, the plan kernel's clock) at which every one of ITS wavefronts started and left, in a buffer of its own: out = {first,
+// last} per wavefront of the last execute -- how far apart the wavefronts of the static deal finish and, set against the plan kernel's
+// first clocks, whether the launch behind it starts before the family launch's last wavefront ends.  cap (64-bit words) must hold 2 x
+// wavefronts.  Returns the number of wavefronts written (0: not recorded, or a plan without a family launch), negative on error.
+int ltr_debug_family_wave_clocks(ltr_plan* plan, uint64_t* out, int64_t cap);
 }
 
 #endif

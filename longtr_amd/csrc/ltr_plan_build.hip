@@ -39,12 +39,12 @@ void release_plan_buffers(ltr_plan* plan, ltr_ctx* ctx) {
   void** bufs[] = {(void**)&plan->d_reads, (void**)&plan->d_haps, (void**)&plan->d_hap_codes, (void**)&plan->d_pairs,
                    (void**)&plan->d_ll, (void**)&plan->d_queue, (void**)&plan->d_scratch, (void**)&plan->d_redo_list,
                    (void**)&plan->d_ctrl_init, (void**)&plan->d_redo_init, (void**)&plan->d_pk_tabs, (void**)&plan->d_pl_entries, (void**)&plan->d_wave_clock,
-                   (void**)&plan->d_fams, (void**)&plan->d_fam_park, (void**)&plan->d_fam_stats, (void**)&plan->d_fam_spines};
+                   (void**)&plan->d_fams, (void**)&plan->d_fam_park, (void**)&plan->d_fam_stats, (void**)&plan->d_fam_spines, (void**)&plan->d_fam_wave_clock};
   if (plan->d_block || plan->h_ll) {
     // a compact plan: one block holds every array but the scratch strips and the family launch's; the scores are a pinned block of the context
-    void* const scr = plan->d_scratch; void* const fm = plan->d_fams; void* const fp = plan->d_fam_park; void* const fs = plan->d_fam_stats; void* const fsp = plan->d_fam_spines;
+    void* const scr = plan->d_scratch; void* const fm = plan->d_fams; void* const fp = plan->d_fam_park; void* const fs = plan->d_fam_stats; void* const fsp = plan->d_fam_spines; void* const fwc = plan->d_fam_wave_clock;
     for (void** p : bufs) *p = nullptr;
-    plan->d_scratch = (double*)scr; plan->d_fams = (FamilyDesc*)fm; plan->d_fam_park = (double*)fp; plan->d_fam_stats = (uint32_t*)fs; plan->d_fam_spines = (FamilySpine*)fsp;
+    plan->d_scratch = (double*)scr; plan->d_fams = (FamilyDesc*)fm; plan->d_fam_park = (double*)fp; plan->d_fam_stats = (uint32_t*)fs; plan->d_fam_spines = (FamilySpine*)fsp; plan->d_fam_wave_clock = (unsigned long long*)fwc;
     if (ctx) ctx->pool.release(plan->d_block); else if (plan->d_block) (void)hipFree(plan->d_block);
     plan->d_block = nullptr;
     ctx_give_pinned(ctx, plan->h_ll);
@@ -369,10 +369,16 @@ int PlanBuild::size_scratch_and_fan() {
       PLAN_TRY(hipMemcpy(plan->d_fams, plan->fams.data(), plan->fams.size() * sizeof(FamilyDesc), hipMemcpyHostToDevice));
       PLAN_TRY(ctx->pool.alloc((void**)&plan->d_fam_spines, plan->fam_spines.size() * sizeof(FamilySpine)));
       PLAN_TRY(hipMemcpy(plan->d_fam_spines, plan->fam_spines.data(), plan->fam_spines.size() * sizeof(FamilySpine), hipMemcpyHostToDevice));
-      // (kFamilyParkSlots park rows per wavefront: 8 x 41 x 64 doubles = 168 KB, 516 MB for the 3072 wavefronts of a full grid on 256 CUs)
+      // (kFamilyParkSlots park rows per wavefront, each sized for the widest strip: 8 x 42 x 64 doubles = 168 KB (172 032 bytes), 528 MB
+      // for the 3072 wavefronts of a full grid on 256 CUs; a family with a spine uses 8 x (2W+2) x 64 doubles of it, dense from the block's start)
       PLAN_TRY(ctx->pool.alloc((void**)&plan->d_fam_park, (size_t)fam_grid * kBlockWaves * kFamilyParkDoubles * sizeof(double)));
       PLAN_TRY(ctx->pool.alloc((void**)&plan->d_fam_stats, 4 * sizeof(uint32_t)));
       PLAN_TRY(hipMemset(plan->d_fam_stats, 0, 4 * sizeof(uint32_t)));
+      if (ctx->dbg.wave_clock > 0) {                           // (measurement aid: ltr_debug_family_wave_clocks)
+        const size_t nb = (size_t)fam_grid * kBlockWaves * 2 * sizeof(unsigned long long);
+        PLAN_TRY(ctx->pool.alloc((void**)&plan->d_fam_wave_clock, nb));
+        PLAN_TRY(hipMemset(plan->d_fam_wave_clock, 0, nb));
+      }
     }
     if (plan->fan_lanes > 1) {
       PLAN_TRY(hipEventCreateWithFlags(&plan->ev_fork, hipEventDisableTiming));

@@ -306,6 +306,7 @@ int Execute::launch_class(const Launch& L, int li) {
     case kLaunchFamily: {
       FamilyArgs FA;
       FA.fams = plan->d_fams; FA.n_fams = (int32_t)plan->fams.size(); FA.reserved = 0; FA.park = plan->d_fam_park; FA.stats = plan->d_fam_stats; FA.spines = plan->d_fam_spines;
+      FA.wave_clock = plan->d_fam_wave_clock; plan->fam_clock_waves = L.grid * kBlockWaves;
       ltrk::launch_family(grid, ls, A, FA);
       break;
     }
@@ -627,6 +628,18 @@ int ltr_plan_debug_wave_clocks(ltr_plan* plan, uint64_t* out, int64_t cap) {
   HIP_TRY(ctx, hipMemcpy(out, plan->d_wave_clock, ((size_t)n * 4 + 4096 + 256) * sizeof(uint64_t), hipMemcpyDeviceToHost));
   HIP_TRY(ctx, hipMemset(plan->d_wave_clock + 4 * n, 0, sizeof(uint64_t)));      // (the log's counter, for the next execute)
   HIP_TRY(ctx, hipMemset(plan->d_wave_clock + 4 * n + 4096, 0, 256 * sizeof(uint64_t)));   // (... and the per-entry sums)
+  return (int)n;
+}
+
+int ltr_debug_family_wave_clocks(ltr_plan* plan, uint64_t* out, int64_t cap) {
+  if (!plan || !plan->ctx || !out || cap < 0) return LTR_ERR_INVALID;
+  if (!plan->d_fam_wave_clock || !plan->executed || plan->fam_clock_waves <= 0) return 0;
+  ltr_ctx* ctx = plan->ctx;
+  const int64_t n = plan->fam_clock_waves;
+  if (cap < 2 * n) return LTR_ERR_INVALID;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(plan->last_stream));
+  HIP_TRY(ctx, hipMemcpy(out, plan->d_fam_wave_clock, (size_t)n * 2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
   return (int)n;
 }
 
