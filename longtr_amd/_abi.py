@@ -734,6 +734,29 @@ PLOIDY_SIGNATURES = {
 }
 
 
+class SnpRead(C.Structure):
+    """struct ltr_snp_read (include/ltr_snp.h)."""
+
+    _fields_ = [("pos", C.c_int32), ("end_pos", C.c_int32), ("length", C.c_int32), ("bases", C.c_char_p), ("quals", C.c_char_p),
+                ("n_cigar", C.c_int32), ("cigar_type", C.c_char_p), ("cigar_num", C.POINTER(C.c_int32))]
+
+
+# include/ltr_snp.h: libltr_snp.so, a host library of its own (longtr_amd/_snp.py loads it; tests/test_snp_phasing.py parses the
+# header and holds this table to it).  bind() below is libltr_gpu.so's and does not walk it.
+SNP_SIGNATURES = {
+    "ltr_snp_set_create": (_int, [_str, _str, _i64, _vp, _vp, _i32, _i32, _P(_vp), _str, _int]),
+    "ltr_snp_set_free": (None, [_vp]),
+    "ltr_snp_set_n_samples": (_i32, [_vp]),
+    "ltr_snp_set_sample_name": (_str, [_vp, _i32]),
+    "ltr_snp_set_sample_index": (_i32, [_vp, _str]),
+    "ltr_snp_set_n_valid_snps": (_i32, [_vp]),
+    "ltr_snp_set_n_snps": (_i32, [_vp, _i32]),
+    "ltr_snp_set_snps": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32]),
+    "ltr_snp_phasing_priors": (_int, [_vp, _i32, _P(SnpRead), _i32, _vp, _vp, _vp, _str, _int]),
+    "ltr_snp_debug_quality_tables": (None, [_vp, _vp]),
+}
+
+
 def bind(L):
     """Give every function of the loaded library its signature: the one walk over the tables."""
     for table in (SIGNATURES, PLOIDY_SIGNATURES, HOOK_SIGNATURES):

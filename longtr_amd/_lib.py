@@ -11,6 +11,7 @@ This module is the facade: every name is defined in one of the modules below, by
   _context     Context
   _genotype    Plan, GenotypeResult, the VCF record of a locus
   _filter      the reference's read filter for one region (libltr_filter.so, include/ltr_filter.h)
+  _snp         phasing priors of reads from a phased SNP VCF (libltr_snp.so, include/ltr_snp.h)
   _formats     region files, FASTA, VCF writer / panel / index, BAM
   _host        host-only helpers: trimming, pooling, pruning, remapping, phasing priors
   _haplotypes  ReadSet, edit distances, clustering, consensus
@@ -28,5 +29,6 @@ from ._haplotypes import ReadSet, _hap_result, cluster_sequences, edit_distances
 from ._host import (extract_genotypes, haplotype_seqs, haps_to_alleles, phasing_priors, pool_reads, prune_hap_blocks, remap_aln_probs,
                     remap_haplotypes, scatter_pool_probs, trim_alignment, unused_alleles)
 from ._loader import LtrError, _lib, _p, lib      # (_lib: the loader's cache as it was at import; _loader._lib is the live one)
+from ._snp import PhasedSnps, SnpSet
 
 EXPORTS = list(SIGNATURES)                        # every symbol include/ltr_gpu.h declares

@@ -4,9 +4,10 @@
 
 genotype_regions() is BamProcessor::process_regions (src/bam_processor.cpp:536-628) + process_reads / process_phased_reads +
 the gates of GenotyperBamProcessor::analyze_reads_and_phasing (src/genotyper_bam_processor.cpp:227-312) for the path the library
-covers: unpaired (long) reads, the reference's fixed stutter model, no SNP phasing.  The read filter is ltr_filter_reads
-(include/ltr_filter.h).  The filter and the gates are restatements: they cannot be pinned to the compiled reference, because
-bam_processor.cpp includes htslib.  Options carry the reference's names (hipstr_main.cpp:140-190) and defaults.
+covers: unpaired (long) reads, the reference's fixed stutter model.  The phasing priors of a read come from its HP tag
+(--phased-bam), from the heterozygous SNPs of a phased SNP VCF it overlaps (--phased-snps, the reference's --snp-vcf:
+include/ltr_snp.h) or are zero.  The read filter is ltr_filter_reads (include/ltr_filter.h).  The filter, the gates and the SNP
+priors are restatements: they cannot be pinned to the compiled reference, because these units include htslib.  Options carry the reference's names (hipstr_main.cpp:140-190) and defaults.
 """
 import argparse
 import queue
@@ -22,6 +23,7 @@ from ._formats import Bam, Fasta, VcfPanel, VcfWriter, read_regions, vcf_header
 from ._haplotypes import ReadSet
 from ._host import phasing_priors
 from ._loader import LtrError
+from ._snp import PhasedSnps
 
 MAX_MATE_DIST = 1000      # bam_processor.h: the records of a region are fetched this far either side (:586-587)
 CONTIG_END = 50           # bam_processor.cpp:580-583
@@ -31,7 +33,7 @@ STAGES = ("bam", "filter", "left_align", "haplotypes", "alignment", "genotype", 
 
 # the options of the reference this driver does not serve, each with its sentence
 REFUSED = {
-    "snp_vcf": "--snp-vcf is not supported: reads are phased by their HP tags (--phased-bam) or not at all.",
+    "snp_vcf": "--snp-vcf is not taken under that name: give the same file to --phased-snps.",
     "fam": "--fam is not supported: pedigree-based filtering of SNP phasing is out of scope.",
     "pass_bam": "--pass-bam is not supported: this driver writes no BAM files.",
     "filt_bam": "--filt-bam is not supported: this driver writes no BAM files.",
@@ -42,7 +44,7 @@ CRAM_REFUSAL = "CRAM input is not supported: convert to BAM with a .bai index."
 DEFAULTS = dict(chrom=None, phased_bam=False, haploid_chrs=(), bam_samps=None, bam_libs=None, ref_vcf=None, min_mapq=20, min_mean_qual=30.0,
                 max_tr_len=1000, min_reads=10, max_reads=1000000, max_haps=1000, indel_flank_len=5, alignment_params=None, stutter_align_len=0,
                 output_gls=False, output_pls=False, output_phased_gls=False, output_filters=False, alleles="exact", chunk_loci=1024,
-                chunk_read_bytes=256 << 20, overlap=True, full_command="longtr_amd.call", require_spanning=1, min_flank=5, sample_ploidy=None)
+                chunk_read_bytes=256 << 20, overlap=True, full_command="longtr_amd.call", require_spanning=1, min_flank=5, sample_ploidy=None, phased_snps=None)
 
 
 # ---- the reference sequence ---------------------------------------------------------------------------------------------------
@@ -224,6 +226,20 @@ def plan_chunks(sizes, chunk_loci, chunk_read_bytes):
 
 
 # ---- the driver ---------------------------------------------------------------------------------------------------------------
+def verify_vcf_chromosomes(snps, chroms):
+    """SNPBamProcessor::verify_vcf_chromosomes (snp_bam_processor.cpp:8-33): every chromosome of the region list is in the SNP
+    VCF's index, or LtrError(LTR_ERR_INVALID) with the reference's message and its chr / no-chr hint."""
+    for chrom in chroms:
+        if snps.has_chromosome(chrom):
+            continue
+        text = (f"No entries for chromosome {chrom} found in the SNP VCF file\n\tPlease ensure that the chromosome names in your BED file "
+                "match those in your SNP VCF file")
+        for alt in ["chr" + chrom] + ([chrom[3:]] if len(chrom) > 3 and chrom.startswith("chr") else []):
+            if snps.has_chromosome(alt):
+                text += f"\n\tNOTE: Found chromosome {alt} in the VCF, but not chromosome {chrom}"
+        raise LtrError(_abi.LTR_ERR_INVALID, text)
+
+
 def _check_options(options):
     for k, text in REFUSED.items():
         if options.get(k):
@@ -247,7 +263,32 @@ class _Prepared:
         self.entry, self.rs, self.reads, self.read_bytes = entry, None, None, 0
 
 
-def _prepare(bam, reference, reg, chrom_len, o, samples_arg, fopt, stage):
+def _snp_priors(snps, reg, raw, sample_names, entry):
+    """log_p1 / log_p2 of the passing raw reads from the phased SNPs within 1000 bp of the region (process_reads,
+    snp_bam_processor.cpp:52-117), sample by sample, and the numbers of its two log lines as entry["snp_info"]."""
+    p1, p2 = np.zeros(len(raw)), np.zeros(len(raw))
+    found = 0
+    with snps.handle.window(reg["chrom"], reg["start"], reg["stop"]) as snp_set:
+        for k, name in enumerate(sample_names):
+            mine = [j for j, r in enumerate(raw) if r["sample"] == k]
+            column = snp_set.sample_index(name)
+            found += column >= 0
+            p1[mine], p2[mine] = snp_set.priors(column, [raw[j] for j in mine], snps.counts)
+        n_valid = snp_set.n_valid_snps
+    differ = p1 != p2
+    entry["snp_info"] = dict(n_valid_snps=n_valid, samples_in_vcf=int(found), phased_reads=int(differ.sum()),
+                             phased_samples=len({raw[j]["sample"] for j in np.flatnonzero(differ)}))
+    return p1, p2
+
+
+class _SnpSource:
+    """The producer's side of --phased-snps: the open VCF, the match counters its calls add to, and the seconds they took."""
+
+    def __init__(self, path):
+        self.handle, self.counts, self.seconds = PhasedSnps(path), np.zeros(3, dtype=np.int32), 0.0
+
+
+def _prepare(bam, reference, reg, chrom_len, o, samples_arg, fopt, stage, snps=None):
     """BAM seek + read, filter, reference fetch, left alignment and priors of one locus (the producer's side)."""
     entry = dict(chrom=reg["chrom"], start=reg["start"], stop=reg["stop"], name=reg["name"], status="ok", gate=None, n_records=0,
                  n_reads=0, samples=[], filter_counters=None)
@@ -286,6 +327,12 @@ def _prepare(bam, reference, reg, chrom_len, o, samples_arg, fopt, stage):
     if o["phased_bam"]:                                          # process_phased_reads; otherwise both priors 0 (snp_bam_processor.cpp:93-103)
         hp = [raw[r["source"]]["hp"] for r in reads]
         p1, p2, _ = phasing_priors(sample, [h if h in (1, 2) else -1 for h in hp], len(fr["samples"]))
+    elif snps is not None:                                       # process_reads: the priors of the raw reads, carried to what left alignment kept
+        t = time.perf_counter()
+        raw_p1, raw_p2 = _snp_priors(snps, reg, raw, fr["samples"], entry)
+        source = [r["source"] for r in reads]
+        p1, p2 = raw_p1[source], raw_p2[source]
+        snps.seconds += time.perf_counter() - t
     else:
         p1, p2 = np.zeros(len(reads)), np.zeros(len(reads))
     p.rs, p.reads, p.read_bytes = rs, reads, sum(len(r["seq"]) for r in reads)
@@ -400,7 +447,10 @@ def genotype_regions(ctx, bams, reference, regions, out_vcf, **options):
     MOTIF [NAME], ltr_read_regions) or a list of the dicts read_regions gives.  out_vcf: the VCF (BGZF for *.gz).
 
     options, with the reference's names and defaults: chrom, phased_bam, haploid_chrs, sample_ploidy (ours: a path or {(sample, chrom):
-    1 | 2}, the ploidy of a sample on a chromosome where it differs from what haploid_chrs says -- chrX of a cohort of men and women), bam_samps, bam_libs (accepted; libraries are
+    1 | 2}, the ploidy of a sample on a chromosome where it differs from what haploid_chrs says -- chrX of a cohort of men and women),
+    phased_snps (the reference's snp_vcf under a name of ours: a bgzipped, tabix-indexed VCF of phased SNP genotypes of the samples; the
+    priors of a read are those of the heterozygous SNPs it overlaps within 1000 bp of the region; with phased_bam the HP tags win and
+    the file is not opened; every chromosome of the region list must be in its index), bam_samps, bam_libs (accepted; libraries are
     unused, duplicate removal is off in the reference, hipstr_main.cpp:383), ref_vcf, min_mapq 20, min_mean_qual 30, max_tr_len 1000,
     min_reads 10, max_reads 1000000, max_haps 1000, indel_flank_len 5, alignment_params (7 numbers), stutter_align_len 0, output_gls,
     output_pls, output_phased_gls, output_filters.  Ours: alleles = "exact" (ltr_build_haplotype) | "clustered" | "consensus" (the two
@@ -416,7 +466,10 @@ def genotype_regions(ctx, bams, reference, regions, out_vcf, **options):
 
     Returns the report: loci (per locus chrom, start, stop, name, status, gate, n_records, n_reads, samples, filter_counters, ...),
     counters (the reference's summary: too_long, too_few_reads, too_many_reads, genotype_success, genotype_fail, and one per gate),
-    columns, error (None or text), timing (stage_seconds over STAGES, timers = ltr_ctx_timers, wall_seconds, chunks)."""
+    columns, error (None or text), timing (stage_seconds over STAGES, timers = ltr_ctx_timers, wall_seconds, chunks).  With phased_snps:
+    per locus snp_info (n_valid_snps in the window, samples_in_vcf, phased_reads, phased_samples), the counters snp_match and
+    snp_mismatch, and timing["snp_seconds"] (part of the producer's time, beside STAGES); with phased_bam as well, only the key
+    phased_snps, the sentence that the file was ignored."""
     o = _check_options(options)
     if isinstance(bams, str):
         bams = bams.split(",")
@@ -428,9 +481,20 @@ def genotype_regions(ctx, bams, reference, regions, out_vcf, **options):
     regs = read_regions(regions, chrom_limit=o["chrom"], order=True)[0] if isinstance(regions, (str, bytes)) else \
         sorted((r for r in regions if not o["chrom"] or r["chrom"] == o["chrom"]), key=lambda r: (r["chrom"].encode(), r["start"], r["stop"]))
     bam = Bam(list(bams), merge_by_position=False)              # ORDER_ALNS_BY_FILE (bam_processor.cpp:193)
-    panel = writer = None
+    panel = writer = snps = None
     stage, n_chunks = dict.fromkeys(STAGES, 0.0), 0
     report = dict(loci=[], counters=dict.fromkeys(COUNTERS, 0), columns=None, error=None, timing=None)
+    if o["phased_snps"] and o["phased_bam"]:                     # the HP tags win and the file is never opened (hipstr_main.cpp:364-366)
+        report["phased_snps"] = "Using phased BAM tags to genotype and phase TRs (WARNING: Any arguments provided to --phased-snps will be ignored)"
+    elif o["phased_snps"]:                                       # an unusable file or a missing chromosome raises: nothing has been written yet
+        try:
+            snps = _SnpSource(o["phased_snps"])
+            verify_vcf_chromosomes(snps.handle, dict.fromkeys(r["chrom"] for r in regs))
+        except BaseException:
+            for h in (snps and snps.handle, bam) + ((ref,) if own_ref else ()):
+                if h is not None:
+                    h.close()
+            raise
     old_params = ctx.params
     try:
         read_groups = bam.read_groups()
@@ -458,7 +522,7 @@ def genotype_regions(ctx, bams, reference, regions, out_vcf, **options):
 
         def prepared():
             for reg in regs:
-                p = _prepare(bam, ref, reg, ref.length(reg["chrom"]), o, samples_arg, fopt, stage)
+                p = _prepare(bam, ref, reg, ref.length(reg["chrom"]), o, samples_arg, fopt, stage, snps)
                 p.entry["sample_ploidy"] = [sample_ploidy(o["sample_ploidy"], haploid_chrs, s, reg["chrom"]) for s in columns]
                 yield p
 
@@ -477,7 +541,7 @@ def genotype_regions(ctx, bams, reference, regions, out_vcf, **options):
         report["error"] = f"{type(e).__name__}: {e}"
     finally:
         ctx.set_params(old_params)
-        for h in (writer, panel, bam) + ((ref,) if own_ref else ()):
+        for h in (writer, panel, snps and snps.handle, bam) + ((ref,) if own_ref else ()):
             if h is not None:
                 h.close()
     for e in report["loci"]:
@@ -491,6 +555,9 @@ def genotype_regions(ctx, bams, reference, regions, out_vcf, **options):
             c["genotype_fail"] += 1
     report["timing"] = dict(stage_seconds=stage, timers=ctx.timers(), wall_seconds=time.perf_counter() - t_wall,
                             chunks=n_chunks if report["error"] is None else None)
+    if snps is not None:                                         # match_count_ / mismatch_count_ of the reference, and the time of the SNP step
+        report["counters"].update(snp_match=int(snps.counts[0] + snps.counts[1]), snp_mismatch=int(snps.counts[2]))
+        report["timing"]["snp_seconds"] = snps.seconds
     return report
 
 
@@ -551,6 +618,8 @@ def make_parser():
     ap.add_argument("--tr-vcf", required=True, metavar="<tr_gts.vcf.gz>", help="VCF to write (BGZF for *.gz)")
     ap.add_argument("--chrom", default=None, metavar="<chrom>", help="only consider regions on this chromosome")
     ap.add_argument("--phased-bam", action="store_true", help="use the reads' HP tags as phasing priors")
+    ap.add_argument("--phased-snps", default=None, metavar="<phased_snps.vcf.gz>", help="Bgzipped input VCF file containing phased SNP genotypes for the samples "
+                    "(LongTR's --snp-vcf), with its .tbi")
     ap.add_argument("--haploid-chrs", default="", metavar="<list_of_chroms>", help="comma separated list of chromosomes to treat as haploid")
     ap.add_argument("--sample-ploidy", default=None, metavar="<ploidy.tsv>", help="tab separated lines `sample chrom ploidy` (1 or 2, # comments): the copies of a "
                     "chromosome a sample has, e.g. chrX of a man; a pair not named is 1 on a chromosome of --haploid-chrs, else 2")
@@ -588,7 +657,7 @@ def options_from_args(args):
     if any(b.lower().endswith(".cram") for b in args.bams.split(",")):
         raise LtrError(_abi.LTR_ERR_UNSUPPORTED, CRAM_REFUSAL)
     split = lambda s: None if s is None else s.split(",")
-    return dict(chrom=args.chrom, phased_bam=args.phased_bam, haploid_chrs=tuple(c for c in args.haploid_chrs.split(",") if c),
+    return dict(chrom=args.chrom, phased_bam=args.phased_bam, phased_snps=args.phased_snps, haploid_chrs=tuple(c for c in args.haploid_chrs.split(",") if c),
                 bam_samps=split(args.bam_samps), bam_libs=split(args.bam_libs), ref_vcf=args.ref_vcf, min_mapq=args.min_mapq,
                 min_mean_qual=args.min_mean_qual, max_tr_len=args.max_tr_len, min_reads=args.min_reads, max_reads=args.max_reads,
                 max_haps=args.max_haps, indel_flank_len=args.indel_flank_len,
